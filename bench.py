@@ -3,8 +3,14 @@
 path-tracing hot path on BASELINE.json's metric config — cbox 640x480 spp=64 on one MI355X.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--scene cbox|bunny|scene1] [--traversal exact|pruned]
+                  [--dump-outputs DIR] [--full]
 
 One "step" = one full frame: trace kernel(s) + ordered resolve (+ gather to rank 0 when N>1).
+A plain run sets up, warms up, times K steps and prints the line.  --full adds what the headline figure does not need:
+the two untimed counting frames behind config.work, and the CPU oracle's baseline with its bit-for-bit check of the last
+timed frame (cpu_baseline, parity_rows).  --dump-outputs DIR writes the last timed frame (what a caller of the timed path
+receives) to DIR/frame.npy, float32 [H, W, 3]; the inputs are fixed (scene fixture, PCG seed 1984), so two builds can be
+compared output for output.
 N>1 (one rank per GPU): weak scaling — the frame stays 640x480 and the sample count grows to 64*N, rows are
 interleaved over ranks (rank r: rows r, r+N, ...), so every GPU traces the same 19.66 M paths as the 1-GPU run; the
 row bands are gathered to rank 0 over RCCL inside the timed region.  `python bench.py --gpus N` starts its own N
@@ -80,6 +86,13 @@ def parity_rows(frame, oracle_rows, k):
     return out
 
 
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: every array as DIR/<name>.npy, float32 (the largest frame, dragon 1920x1080, is 25 MB)."""
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
 # README.md FPS of the reference on an RTX 3080 at its UI default of 2 samples per frame, 640x480, INCLUDING per-frame CPU
 # tonemap + GL upload (README.md:10-11,112-113,121-124): the only numbers the reference publishes (BASELINE.md §1).
 REFERENCE_FPS = {"scene1": (65, 80), "cbox": (55, 65), "bunny": (45, 50)}
@@ -129,6 +142,8 @@ def progressive_mode(args, hs, desc, wl):
         frame(args.warmup + k)
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"accumulation": acc.cpu().numpy()})
     c = ds.counters()
     fps = args.steps / elapsed
     ref = REFERENCE_FPS.get(args.scene)
@@ -288,7 +303,7 @@ def main():
     ap.add_argument("--set", action="append", default=[], metavar="KEY=VALUE", help="pt_scene_set_option before rendering (tuning runs)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-work-frames", action="store_true",
-                    help="skip the two untimed counting frames behind config.work (profiling runs: only the timed kernel on the GPU)")
+                    help="--full: skip the two untimed counting frames behind config.work (profiling runs: only the timed kernel on the GPU)")
     ap.add_argument("--force-gather", action="store_true",
                     help="N=1 only: run every frame through the N>1 path — a one-rank nccl (RCCL) group, gather + de-interleave — "
                          "to measure what that step costs per frame")
@@ -302,7 +317,16 @@ def main():
     ap.add_argument("--progressive", type=int, default=0, metavar="SPF",
                     help="instead of the offline frame: time render_progressive-style frames of SPF samples each "
                          "(pt_render_accumulate; the reference UI's default is 2, main.cu:131) and report frames/s")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed to DIR/<name>.npy (frame.npy; "
+                         "--progressive: accumulation.npy)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the counting frames behind config.work and the CPU "
+                         "oracle's baseline + bit-for-bit check of the last timed frame (--no-work-frames / --no-cpu-baseline "
+                         "drop either leg)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         return launch_ranks(args)          # before anything in this process touches the GPU
@@ -391,6 +415,8 @@ def main():
         frame = step()
     fence()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"frame": frame.detach().cpu().numpy()})   # before the --full frames reuse the buffer
     c_last = R.scene.counters()
     if c_warm is not None and (c_warm.segments, c_warm.paths) != (c_last.segments, c_last.paths):
         raise SystemExit("bench.py: two frames of the same configuration traced different work")
@@ -413,7 +439,7 @@ def main():
     # Work the kernel really did per segment (one extra, untimed frame with the counting build of the kernel, rank 0's rows):
     # the algorithmic figures below price the REFERENCE's traversal of the REFERENCE's tree; this is what was traversed.
     work = None
-    if not stub and not args.no_work_frames:
+    if not stub and args.full and not args.no_work_frames:
         R.scene.set_option("stats", 1)
         R.render(params, rank, world)
         cw = R.scene.counters()
@@ -513,7 +539,7 @@ def main():
         if stub:
             out["stub"] = True
             out["config"]["frame_rows_ok"] = bool((frame[:, 0, 0] == torch.arange(wl["h"], dtype=torch.float32)).all())
-        if world == 1 and not args.no_cpu_baseline and not stub:
+        if world == 1 and args.full and not args.no_cpu_baseline and not stub:
             # the oracle's rows of the very frame that was timed: the CPU baseline AND the checker of the last timed GPU frame
             out["cpu_baseline"], oracle_rows, k = cpu_baseline(desc, hs.render_params(wl["w"], wl["h"], wl["spp"]), args.scene)
             out["parity_rows"] = parity_rows(frame, oracle_rows, k) if args.traversal == "exact" else None

@@ -50,3 +50,25 @@ def test_without_a_gpu_the_real_renderer_refuses_to_run():
         pass
     r = run_bench(["--steps", "1", "--warmup", "0"])
     assert r.returncode != 0 and "no CPU fallback" in (r.stderr + r.stdout)
+
+
+@pytest.mark.parametrize("n", [1, 2])
+def test_dump_outputs_writes_the_last_timed_frame(n, tmp_path):
+    import numpy as np
+    out_dir = tmp_path / "out"
+    r = run_bench(["--gpus", str(n), "--steps", "3", "--warmup", "1", "--stub-renderer", "--dump-outputs", str(out_dir)])
+    assert r.returncode == 0, r.stderr[-2000:]
+    out = json.loads(r.stdout.strip().splitlines()[-1])
+    assert out["steps"] == 3 and out["warmup"] == 1 and out["ms_per_step"] > 0
+    assert sorted(p.name for p in out_dir.iterdir()) == ["frame.npy"]
+    frame = np.load(out_dir / "frame.npy")
+    assert frame.dtype == np.float32 and frame.shape == (480, 640, 3)
+    assert (frame == np.arange(480, dtype=np.float32)[:, None, None]).all()      # the stub's frame: row j holds j
+
+
+def test_full_is_an_option_and_steps_must_be_positive():
+    r = run_bench(["--gpus", "1", "--steps", "2", "--warmup", "0", "--stub-renderer", "--full"])
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert json.loads(r.stdout.strip().splitlines()[-1])["steps"] == 2
+    r = run_bench(["--gpus", "1", "--steps", "0", "--stub-renderer"])
+    assert r.returncode != 0 and "--steps must be >= 1" in r.stderr

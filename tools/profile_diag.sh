@@ -8,7 +8,7 @@ ARGS="$@"
 OUT=gpurun_out/prof_$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
-BENCH="python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline $ARGS"
+BENCH="python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline $ARGS"
 # rocprofv3 aborts (and then hangs) when a pass asks for more counters than a block has slots: TA and TD take 2 per
 # pass, TCC and TCP 4, SQ 8 — and every pass runs under its own timeout.
 for PASS in "TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_32B_sum TCC_EA0_RDREQ_64B_sum TCC_EA0_RDREQ_128B_sum" \

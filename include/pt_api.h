@@ -300,6 +300,13 @@ int pt_debug_math(int op, const float* x, const float* y, float* out0, float* ou
  * library: lets CPU-only tests pin the shared arithmetic header without a GPU. */
 int pt_debug_math_host(int op, const float* x, const float* y, float* out0, float* out1, int n);
 
+/* The exact short sequences of csrc/pt_math.h (rcp_exact, div_pi_exact, sqrt_exact) evaluated ON THE DEVICE
+ * against the IEEE expressions they replace, over the fp32 bit patterns begin .. begin + count - 1
+ * (begin + count <= 2^32).  op: 0 rcp_exact(x) vs 1.0f / x   1 div_pi_exact(x) vs x / pi   2 sqrt_exact(x) vs sqrtf(x)
+ *     3 the bare hardware reciprocal vs 1.0f / x (a control for the checker: it is not correctly rounded).
+ * out: number of inputs whose result bits differ, and the first such bit pattern (-1 if none). */
+int pt_debug_exact_math(int op, uint32_t begin, uint64_t count, uint64_t* mismatches, int64_t* first_mismatch);
+
 /* Closest-hit query for explicit rays (tests / per-ray KATs).
  * rays: n x {org[3], dir[3], tnear, tfar}; out: n x {t,u,v} and prim id (-1 = miss). */
 int pt_debug_intersect(pt_scene* scene, const float* rays, int n, int traversal,

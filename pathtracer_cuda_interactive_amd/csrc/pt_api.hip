@@ -1538,6 +1538,35 @@ int pt_debug_math(int op, const float* x, const float* y, float* out0, float* ou
     return PT_OK;
 }
 
+int pt_debug_exact_math(int op, uint32_t begin, uint64_t count, uint64_t* mismatches, int64_t* first_mismatch) {
+    if (!mismatches || !first_mismatch || op < 0 || op > 3 || count > (1ull << 32) - begin)
+        return fail(PT_ERR_INVALID_ARG, "bad argument");
+    *mismatches = 0;
+    *first_mismatch = -1;
+    if (count == 0) return PT_OK;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(PT_ERR_NO_DEVICE, "no HIP device available");
+    DevBuf<unsigned long long> dbad;
+    DevBuf<uint32_t> dfirst;
+    int rc;
+    if ((rc = dbad.ensure(1)) || (rc = dfirst.ensure(1))) return rc;
+    unsigned long long nbad = 0;
+    uint32_t first = 0xffffffffu;
+    hipError_t e = hipMemcpy(dbad.p, &nbad, sizeof(nbad), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(dfirst.p, &first, sizeof(first), hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        const uint64_t blocks = std::min<uint64_t>((count + 255) / 256, 4096);
+        hipLaunchKernelGGL(exact_math_kernel, dim3((unsigned)blocks), dim3(256), 0, nullptr, op, begin, count, dbad.p, dfirst.p);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpy(&nbad, dbad.p, sizeof(nbad), hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(&first, dfirst.p, sizeof(first), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return fail(PT_ERR_DEVICE, std::string("pt_debug_exact_math: ") + hipGetErrorString(e));
+    *mismatches = nbad;
+    if (nbad) *first_mismatch = (int64_t)begin + first;
+    return PT_OK;
+}
+
 int pt_debug_math_host(int op, const float* x, const float* y, float* out0, float* out1, int n) {
     if (!x || !y || !out0 || !out1 || n < 0 || op < 0 || op > 2) return fail(PT_ERR_INVALID_ARG, "bad argument");
     for (int k = 0; k < n; k++) {

@@ -4,7 +4,7 @@
 //        traversal / shading scheduling (default).  Replaces render + setup_rand (main.cu:30-62) and all they call.
 //   trace_kernel<LDS_SCENE,PRUNE,STATS>   the simpler segment-synchronous schedule (option "kernel" = 1).
 //   resolve_kernel     ordered per-pixel sum of the per-sample radiances (main.cu:47,50 / 72-86).
-//   intersect_kernel, math_kernel   test hooks behind pt_debug_*.
+//   intersect_kernel, math_kernel, exact_math_kernel   test hooks behind pt_debug_*.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -707,6 +707,33 @@ __global__ void math_kernel(int op, const float* __restrict__ x, const float* __
         ptm::Pcg r = ptm::pcg_init((uint64_t)__builtin_bit_cast(uint32_t, x[k]), (uint64_t)__builtin_bit_cast(uint32_t, y[k]));
         o0[k] = ptm::pcg_float(r);
         o1[k] = ptm::pcg_float(r);
+    }
+}
+
+// pt_debug_exact_math: a fast sequence of pt_math.h against the IEEE expression it stands for, on the fp32 bit patterns
+// begin .. begin + count - 1 (grid-stride).  op 0: rcp_exact(x) vs 1.0f / x, 1: div_pi_exact(x) vs x / kPi,
+// 2: sqrt_exact(x) vs sqrtf(x), 3: the bare v_rcp_f32 vs 1.0f / x (a control: it must differ somewhere).
+// Counts the inputs whose result bits differ; *first = smallest such offset from begin.
+__global__ void exact_math_kernel(int op, uint32_t begin, uint64_t count, unsigned long long* __restrict__ bad,
+                                  uint32_t* __restrict__ first) {
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    unsigned long long nbad = 0;
+    uint32_t fb = 0xffffffffu;
+    for (uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; k < count; k += stride) {
+        const float x = __builtin_bit_cast(float, begin + (uint32_t)k);
+        float got, want;
+        if (op == 0) { got = ptm::rcp_exact(x); want = 1.0f / x; }
+        else if (op == 1) { got = ptm::div_pi_exact(x); want = x / ptm::kPi; }
+        else if (op == 2) { got = ptm::sqrt_exact(x); want = __builtin_sqrtf(x); }
+        else { got = __builtin_amdgcn_rcpf(x); want = 1.0f / x; }
+        if (__builtin_bit_cast(uint32_t, got) != __builtin_bit_cast(uint32_t, want)) {
+            nbad++;
+            fb = min(fb, (uint32_t)k);
+        }
+    }
+    if (nbad) {
+        atomicAdd(bad, nbad);
+        atomicMin(first, fb);
     }
 }
 

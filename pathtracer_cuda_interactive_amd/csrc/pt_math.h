@@ -4,7 +4,8 @@
 // FMA contraction (-ffp-contract=off), no fast-math, denormals kept.  Under that
 // contract a gfx950 lane and an x86-64 core produce the same bits, which is what
 // lets the image be compared bit-for-bit with the CPU oracle: a path tracer
-// amplifies a 1-ulp difference into a different path.
+// amplifies a 1-ulp difference into a different path.  The explicit fmas of rcp_exact / div_pi_exact /
+// sqrt_exact below are not contraction: each of those returns the bits of the IEEE operation it stands for.
 //
 // Replaces, for the hot path: cutil_math.h:295-425 (float3 ops), CUDA sinf/cosf/powf
 // (scene.h:342,353-354,350,397,402), pow(x,5) (scene.h:335), curand_uniform -> pcg.h:16-57.
@@ -27,17 +28,67 @@ PT_HD V3 operator*(V3 a, V3 b) { return {a.x * b.x, a.y * b.y, a.z * b.z}; }
 PT_HD V3 operator*(V3 a, float s) { return {a.x * s, a.y * s, a.z * s}; }
 PT_HD float dot(V3 a, V3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
 PT_HD V3 cross(V3 a, V3 b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
+
+constexpr float kPi = float(3.14159265358979323846);                        // torrey.cuh:33
+constexpr float kTwoPi = float(2.0) * kPi;                                  // torrey.cuh:35
+constexpr float kInvPi = 1.0f / kPi;                                        // RN(1/kPi)
+
+// ---- exact short sequences for 1/x, x/kPi and sqrt(x) ----
+// Each returns the bits of the IEEE expression it names (1.0f / x, x / kPi, __builtin_sqrtf(x)) for every fp32 input:
+// a short fma-corrected sequence on the input range where it was checked against the IEEE result over all 2^32 bit
+// patterns (pt_debug_exact_math, tests/test_exact_fast_math.py), the IEEE expression itself elsewhere (0, denormals,
+// huge values, inf, NaN).  The host build evaluates the IEEE expressions, so host code and the oracle are untouched.
+// The *_fast formulas are the fast paths alone; div_pi_fast uses only IEEE * and fma, so it is checked on the CPU too.
+PT_HD bool div_pi_in_range(float x) { const float a = __builtin_fabsf(x); return a >= 0x1p-100f && a <= 0x1p126f; }
+// Markstein: q = RN(x * RN(1/pi)) is within 1 ulp of x/pi, r = x - q*pi is exact, and q + r*RN(1/pi) rounds to x/pi.
+PT_HD float div_pi_fast(float x) {
+    const float q = x * kInvPi;
+    const float r = __builtin_fmaf(-q, kPi, x);
+    return __builtin_fmaf(r, kInvPi, q);
+}
+PT_HD float div_pi_exact(float x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    if (__builtin_expect(div_pi_in_range(x), 1)) return div_pi_fast(x);
+#endif
+    return x / kPi;
+}
+
+// 1/x: v_rcp_f32 (within 1 ulp) and one Newton step with an exact residual e = 1 - x*r.  Kept when the result is a normal
+// number (one v_cmp_class_f32): 0, inf and NaN inputs give NaN and huge inputs a denormal or 0, which all fall back.
+PT_HD float rcp_exact(float x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    const float r = __builtin_amdgcn_rcpf(x);
+    const float y = __builtin_fmaf(__builtin_fmaf(-x, r, 1.0f), r, r);
+    if (__builtin_expect(__builtin_amdgcn_classf(y, 0x108), 1)) return y;     // 0x108 = -normal | +normal
+#endif
+    return 1.0f / x;
+}
+
+// sqrt(x): v_sqrt_f32 (within 1 ulp), then the neighbour whose residual x - s*s says it is the rounded root.  Fast path:
+// x >= 2^-100, one compare (0, negatives and NaN fail it; +inf passes and comes out +inf: both residuals are NaN).
+PT_HD float sqrt_exact(float x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    if (__builtin_expect(x >= 0x1p-100f, 1)) {
+        float s = __builtin_amdgcn_sqrtf(x);
+        const uint32_t b = __builtin_bit_cast(uint32_t, s);
+        const float dn = __builtin_bit_cast(float, b - 1u);
+        const float up = __builtin_bit_cast(float, b + 1u);
+        if (__builtin_fmaf(-dn, s, x) <= 0.0f) s = dn;
+        if (__builtin_fmaf(-up, s, x) > 0.0f) s = up;
+        return s;
+    }
+#endif
+    return __builtin_sqrtf(x);
+}
+
 // cutil_math.h:401-405 with rsqrtf spelled as 1/sqrt (IEEE on both sides)
-PT_HD V3 normalize(V3 v) { float inv_len = 1.0f / __builtin_sqrtf(dot(v, v)); return v * inv_len; }
+PT_HD V3 normalize(V3 v) { float inv_len = rcp_exact(sqrt_exact(dot(v, v))); return v * inv_len; }
 
 // IEEE maxNum / minNum (v_max_f32 / v_min_f32)
 PT_HD float fmax2(float a, float b) { return __builtin_fmaxf(a, b); }
 PT_HD float fmin2(float a, float b) { return __builtin_fminf(a, b); }
 PT_HD float max_elem(V3 a) { return fmax2(fmax2(a.x, a.y), a.z); }        // radiance.cuh:14-16
 PT_HD float clamp01(float f) { return fmax2(0.0f, fmin2(f, 1.0f)); }      // cutil_math.h:65-68
-
-constexpr float kPi = float(3.14159265358979323846);                        // torrey.cuh:33
-constexpr float kTwoPi = float(2.0) * kPi;                                  // torrey.cuh:35
 
 // sin & cos of x >= 0 (used with x = 2*pi*u): Cody–Waite reduction by pi/2, cephes minimax polynomials.
 PT_HD void sincos_det(float x, float& sn, float& cs) {

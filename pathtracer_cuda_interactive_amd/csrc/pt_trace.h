@@ -84,7 +84,7 @@ template <class STK> __device__ __forceinline__ constexpr int32_t done_value() {
 template <class STK> __device__ __forceinline__ void stack_init(STK* stk) { stk[0] = (STK)done_value<STK>(); }
 
 __device__ __forceinline__ void trav_begin(const SceneView& sv, const Ray& ray, Trav& t) {
-    t.inv = mk(1.0f / ray.dir.x, 1.0f / ray.dir.y, 1.0f / ray.dir.z);
+    t.inv = mk(rcp_exact(ray.dir.x), rcp_exact(ray.dir.y), rcp_exact(ray.dir.z));
     t.best.t = FLT_MAX; t.best.u = 0.0f; t.best.v = 0.0f; t.best.prim = -1;
     t.cur = sv.root_ref;           // scene.h:256: the root is pushed without a box test
     t.sp = 1;                      // entry 0 is the kDone sentinel
@@ -240,7 +240,7 @@ __device__ __forceinline__ void leaf_test(const SceneView& sv, const Ray& ray, T
         const V3 s1 = cross(ray.dir, e2);
         const float divisor = dot(s1, e1);
         if (divisor != 0.0f) {
-            const float inv_divisor = 1.0f / divisor;
+            const float inv_divisor = rcp_exact(divisor);
             const V3 s = o - p0;
             const float u = dot(s, s1) * inv_divisor;
             const V3 s2 = cross(s, e1);
@@ -381,7 +381,7 @@ __device__ __forceinline__ V3 to_world_about(V3 n, V3 local) {
         fx = mk(0.0f, -1.0f, 0.0f);
         fy = mk(-1.0f, 0.0f, 0.0f);
     } else {
-        const float a = 1.0f / (1.0f + n.z);
+        const float a = rcp_exact(1.0f + n.z);
         const float b = -n.x * n.y * a;
         fx = mk(1.0f - n.x * n.x * a, b, -n.x);
         fy = mk(b, 1.0f - n.y * n.y * a, -n.y);
@@ -401,10 +401,10 @@ __device__ __forceinline__ V3 schlick(V3 F0, float cos_theta) {   // scene.h:333
 
 __device__ __forceinline__ V3 sample_cos_hemisphere(float ux, float uy) {   // scene.h:338-345
     const float phi = kTwoPi * ux;
-    const float tmp = __builtin_sqrtf(clamp01(1.0f - uy));
+    const float tmp = sqrt_exact(clamp01(1.0f - uy));
     float sn, cs;
     sincos_det(phi, sn, cs);
-    return mk(cs * tmp, sn * tmp, __builtin_sqrtf(clamp01(uy)));
+    return mk(cs * tmp, sn * tmp, sqrt_exact(clamp01(uy)));
 }
 
 __device__ __forceinline__ V3 sample_cos_n_hemisphere(float ux, float uy, float exponent) {   // scene.h:348-357
@@ -585,10 +585,10 @@ __device__ __forceinline__ bool shade_and_bounce(const SceneView& sv, const Surf
         const float ux = pcg_float(rng);
         const float uy = pcg_float(rng);
         wo = to_world_about(n, sample_cos_hemisphere(ux, uy));
-        const float c = fmax2(dot(wo, n), 0.0f) / kPi;
+        const float c = div_pi_exact(fmax2(dot(wo, n), 0.0f));
         const V3 value = refl * c;
         if (!(max_elem(value) > 0.0f && c > 0.0f)) ok = false;
-        else T = T * (value * (1.0f / c));
+        else T = T * (value * rcp_exact(c));
     } else if (mtype == 1) {                            // MIRROR: scene.h:434-438
         specular = true;
         wo = reflect_about(wi, n);
@@ -609,11 +609,11 @@ __device__ __forceinline__ bool shade_and_bounce(const SceneView& sv, const Surf
             const float ux = pcg_float(rng);
             const float uy = pcg_float(rng);
             wo = to_world_about(n, sample_cos_hemisphere(ux, uy));
-            const float c = fmax2(dot(wo, n), 0.0f) / kPi;
+            const float c = div_pi_exact(fmax2(dot(wo, n), 0.0f));
             const V3 value = ((mk(1.0f, 1.0f, 1.0f) - F) * refl) * c;
             const float pdf = (1.0f - F.x) * c;
             if (!(max_elem(value) > 0.0f && pdf > 0.0f)) ok = false;
-            else T = T * (value * (1.0f / pdf));
+            else T = T * (value * rcp_exact(pdf));
         }
     } else {                                            // PHONG: scene.h:455-460 + 390-408
         const float ux = pcg_float(rng);
@@ -645,7 +645,7 @@ __device__ __forceinline__ bool shade_and_bounce(const SceneView& sv, const Surf
         const float q = fmax2(0.5f, 1.0f - max_elem(T));
         const float xi = pcg_float(rng);
         if (xi < q) return false;
-        T = T * (1.0f / (1.0f - q));
+        T = T * rcp_exact(1.0f - q);
     }
     return true;
 }

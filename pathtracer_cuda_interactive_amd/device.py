@@ -17,6 +17,7 @@ EXPORTS = [
     "pt_api_version", "pt_last_error", "pt_scene_create", "pt_scene_destroy", "pt_render", "pt_render_async",
     "pt_render_accumulate", "pt_get_counters", "pt_scene_set_option", "pt_scene_get_info", "pt_debug_math",
     "pt_debug_intersect", "pt_debug_math_host", "pt_bvh_build_device", "pt_bvh_build_sweep", "pt_get_frame_times", "pt_bvh_build_sweep_device",
+    "pt_debug_exact_math",
 ]
 
 
@@ -44,6 +45,7 @@ def lib():
         L.pt_debug_math.argtypes = [C.c_int, fp, fp, fp, fp, C.c_int]
         L.pt_debug_intersect.argtypes = [vp, fp, C.c_int, C.c_int, fp, ip]
         L.pt_debug_math_host.argtypes = [C.c_int, fp, fp, fp, fp, C.c_int]
+        L.pt_debug_exact_math.argtypes = [C.c_int, C.c_uint32, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_int64)]
         L.pt_bvh_build_device.argtypes = [C.POINTER(PtSceneDesc), C.c_int, C.POINTER(PtBvhNode), ip, ip, C.POINTER(C.c_double)]
         L.pt_bvh_build_sweep.argtypes = [C.POINTER(PtSceneDesc), C.POINTER(PtBvhNode), ip, ip, C.POINTER(C.c_double)]
         L.pt_bvh_build_sweep_device.argtypes = [C.POINTER(PtSceneDesc), C.POINTER(PtBvhNode), ip, ip, C.POINTER(C.c_double)]
@@ -137,6 +139,15 @@ def debug_math(op, x, y=None, host=False):
     fn = lib().pt_debug_math_host if host else lib().pt_debug_math
     _check(fn(op, _fp(x), _fp(y), _fp(o0), _fp(o1), x.size))
     return o0, o1
+
+
+def debug_exact_math(op, begin=0, count=1 << 32):
+    """pt_debug_exact_math: the device's exact short sequence `op` (PT_EXACT_RCP / _DIV_PI / _SQRT, or the control
+    PT_EXACT_RAW_RCP) against the IEEE expression it replaces on the fp32 bit patterns begin .. begin + count - 1.
+    Returns (mismatches, first mismatching bit pattern or -1)."""
+    bad, first = C.c_uint64(), C.c_int64()
+    _check(lib().pt_debug_exact_math(op, begin, count, C.byref(bad), C.byref(first)))
+    return bad.value, first.value
 
 
 def build_bvh_sweep(desc, on_device=False):

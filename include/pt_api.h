@@ -198,6 +198,36 @@ int pt_render_async(pt_scene* scene, const pt_render_params* p, float* fb_dev, v
  * (same layout as fb; overwritten when sample_offset == 0).  Async on stream. */
 int pt_render_accumulate(pt_scene* scene, const pt_render_params* p, float* accum_dev, void* hip_stream);
 
+/* Adaptive sampling — an EXTENSION, like PT_RENDER_NEE: the reference gives every pixel the same spp.  Parameter names are
+ * borrowed from Mitsuba 0.6's `adaptive` integrator (maxError, pValue, maxSampleFactor); the semantics are this library's own.
+ * Never part of a parity or roofline number. */
+typedef struct pt_adaptive_params {
+    int32_t batch_spp;      /* samples added per round to every pixel still above target; 0 -> p->spp   */
+    int32_t max_spp;        /* most samples of one pixel; 0 -> 32 * p->spp; p->spp <= max_spp <= 2^20 */
+    float   max_error;      /* target: relative half-width of the confidence interval, > 0, finite   */
+    float   p_value;        /* two-sided, z = Phi^-1(1 - p/2); 0 -> 0.05; else in (0, 1)             */
+    float   min_luminance;  /* floor of the relative test's denominator, >= 0, used as given         */
+} pt_adaptive_params;       /* 20 bytes */
+
+/* Blocking render with per-pixel sample counts.  fb, spp_map and err_map use pt_render's [rows, W] packing of the rows selected by
+ * (row_begin, row_end, row_stride); spp_map and err_map may be NULL.  on_device != 0: all three are device pointers on the
+ * scene's GPU.
+ *   Rounds: p->spp is the first round, every selected pixel gets that many samples; every later round adds batch_spp samples to
+ *   each pixel still above target.  Checkpoints fall at n = spp, spp + batch, spp + 2 batch, ..., the last one cut to max_spp;
+ *   they depend on spp, batch_spp and max_spp only (a round that does not fit "scratch_bytes" runs in several passes before its
+ *   one check).  p->sample_offset must be 0; p->stream_stride is 0 (= max_spp) or >= max_spp; sample k of a pixel uses PCG stream
+ *   pixel_index * stride + k, so a pixel that stops at n samples holds exactly what pt_render gives it at spp = n with that stride.
+ *   Camera, seed, depths, traversal, PT_RENDER_NEE, row selection and every option mean what they mean in pt_render.
+ *   The rule at a checkpoint with n samples: Y_k = 0.2126 R_k + 0.7152 G_k + 0.0722 B_k in fp64 (left to right, no contraction);
+ *   S1 = sum Y_k, S2 = sum Y_k^2 in fp64 in sample order; mean = S1/n; var = max(0, (S2 - S1*S1/n)/(n-1)), +inf for n == 1;
+ *   half = z sqrt(var/n); err = half == 0 ? 0 : half / max(mean, min_luminance).  The pixel stops when err <= max_error (a NaN
+ *   never does) or n == max_spp.
+ *   Outputs: fb = (sum of the n samples) * (1/n) as in pt_render; spp_map = n; err_map = err at the stopping checkpoint (above
+ *   max_error only where n == max_spp).  pt_get_counters covers the whole call (paths = sum of spp_map; kernel_ms / resolve_ms
+ *   summed over all rounds); pt_scene_get_info "adaptive_rounds" = rounds of the last adaptive call.  Runs on the default stream. */
+int pt_render_adaptive(pt_scene* scene, const pt_render_params* p, const pt_adaptive_params* a,
+                       float* fb, int32_t* spp_map, float* err_map, int on_device);
+
 int pt_get_counters(pt_scene* scene, pt_counters* out);   /* synchronises the scene's last stream */
 
 /* HIP-event times of the last render calls on the scene, oldest first: kernel_ms[k] / resolve_ms[k] of up to max_frames calls,

@@ -172,6 +172,15 @@ struct pt_scene {
     // scratch
     DevBuf<float> accum;
     DevBuf<float> fb_tmp;
+    // pt_render_adaptive: per packed pixel the running fp32 sum and fp64 moments, the two ping-pong lists of pixels still
+    // sampled, the next list's length, and host-output staging for spp_map / err_map
+    DevBuf<float> ad_sum;
+    DevBuf<double> ad_mom;
+    DevBuf<uint32_t> ad_list[2];
+    DevBuf<uint32_t> ad_count;
+    DevBuf<int32_t> ad_spp_tmp;
+    DevBuf<float> ad_err_tmp;
+    int64_t info_adaptive_rounds = 0;
     // What a frame's trace kernel writes lives in a frame slot; render call k uses slot k % frames_in_flight.  With more than one
     // slot a single-pass frame runs on the slot's own stream: the trace kernel at once (it reads the immutable scene and writes
     // the slot only), the resolve — the one step that touches the caller's buffer — once the caller's stream has reached the
@@ -967,6 +976,47 @@ TraceFn pick_kernel(const pt_scene* S, int res, bool prune, bool stats, bool int
     return pick_kernel_v1(res == 1 || res == 2, prune, stats);
 }
 
+// Adaptive rounds after the first (RenderDev::list): the LIST variants of the trace kernels, compiled for the automatic schedule
+// of every residency only — the v2_* knobs change no bit, so these rounds ignore them, and option "kernel" = 3 runs them on 2.
+template <int RES, int THRESH, int INNER, int SPEC>
+TraceFn pick_list_rs(bool prune, bool stats, bool nee) {
+    if (nee) return stats ? trace_kernel_v2<RES, false, true, THRESH, INNER, 6, SPEC, true, true>
+                          : trace_kernel_v2<RES, false, false, THRESH, INNER, 6, SPEC, true, true>;
+    if (prune) return stats ? trace_kernel_v2<RES, true, true, THRESH, INNER, 6, SPEC, false, true>
+                            : trace_kernel_v2<RES, true, false, THRESH, INNER, 6, SPEC, false, true>;
+    return stats ? trace_kernel_v2<RES, false, true, THRESH, INNER, 6, SPEC, false, true>
+                 : trace_kernel_v2<RES, false, false, THRESH, INNER, 6, SPEC, false, true>;
+}
+template <int RES, int THRESH, int INNER>
+TraceFn pick_list_r(bool prune, bool stats, bool nee, int spec) {
+    if (spec == 2) return pick_list_rs<RES, THRESH, INNER, 2>(prune, stats, nee);
+    if (spec == 1 && !nee) return pick_list_rs<RES, THRESH, INNER, 1>(prune, stats, nee);
+    return pick_list_rs<RES, THRESH, INNER, 0>(prune, stats, nee);
+}
+TraceFn pick_kernel_list(const pt_scene* S, int res, bool prune, bool stats, bool internal_tree, bool nee) {
+    if (S->opt_kernel == 1) {
+        if (res == 1 || res == 2) {
+            if (prune) return stats ? trace_kernel<true, true, true, true> : trace_kernel<true, true, false, true>;
+            return stats ? trace_kernel<true, false, true, true> : trace_kernel<true, false, false, true>;
+        }
+        if (prune) return stats ? trace_kernel<false, true, true, true> : trace_kernel<false, true, false, true>;
+        return stats ? trace_kernel<false, false, true, true> : trace_kernel<false, false, false, true>;
+    }
+    const bool tri = S->tri_only && S->opt_specialize;
+    const int spec = !tri ? 0 : (S->diffuse_only ? 2 : 1);
+    // the automatic schedules of pick_kernel / pick_kernel_nee
+    if (nee) {
+        if (res == 3) return pick_list_r<3, 32, 4>(false, stats, true, spec);
+        if (res == 2) return pick_list_r<2, 40, 162>(false, stats, true, spec);
+        if (res == 1) return pick_list_r<1, 40, 162>(false, stats, true, spec);
+        return pick_list_r<0, 32, 4>(false, stats, true, spec);
+    }
+    if (res == 2) return pick_list_r<2, 40, 162>(prune, stats, false, spec);
+    if (res == 1) return pick_list_r<1, 40, 162>(prune, stats, false, spec);
+    if (res == 3) return internal_tree ? pick_list_r<3, 32, 1231>(prune, stats, false, spec) : pick_list_r<3, 32, 4>(prune, stats, false, spec);
+    return internal_tree ? pick_list_r<0, 32, 1231>(prune, stats, false, spec) : pick_list_r<0, 32, 4>(prune, stats, false, spec);
+}
+
 // Sums the kCounterSlots per-workgroup counter slots of the last frame (the caller has synchronised the stream).
 int read_slot_sums(const pt_scene* S, unsigned long long* out) {
     std::vector<unsigned long long> raw(kTimelineBase);
@@ -1002,8 +1052,18 @@ int select_rows(const pt_render_params* p, RowSel* out) {
     return PT_OK;
 }
 
-// mode: 0 = pt_render (fb = mean), 2 = pt_render_accumulate (accum (+)= sum)
-int launch_render(pt_scene* S, const pt_render_params* p, float* out_dev, int mode, hipStream_t stream) {
+// One round of pt_render_adaptive.  Round 0 opens a frame like any render call (slot, counters, timing record) and traces every
+// selected pixel; later rounds continue that frame — same slot, counters and timing record — and trace only the pixels of
+// args.list_in.  The resolve of every pass is adaptive_resolve_kernel.  Adaptive frames run on the caller's stream.
+struct AdaptiveRound {
+    int round;
+    uint32_t n_list;                 // rounds > 0: entries of args.list_in
+    AdaptiveArgs args;               // n, spp_pass, first and check are set per pass by launch_render
+};
+
+// mode: 0 = pt_render (fb = mean), 2 = pt_render_accumulate (accum (+)= sum); ad: a round of pt_render_adaptive (mode 0)
+int launch_render(pt_scene* S, const pt_render_params* p, float* out_dev, int mode, hipStream_t stream,
+                  const AdaptiveRound* ad = nullptr) {
     if (!S || !p || !out_dev) return fail(PT_ERR_INVALID_ARG, "null argument");
     if (p->width <= 0 || p->height <= 0 || p->spp <= 0) return fail(PT_ERR_INVALID_ARG, "width, height and spp must be positive");
     if (p->sample_offset < 0 || p->stream_stride < 0) return fail(PT_ERR_INVALID_ARG, "negative sample_offset / stream_stride");
@@ -1026,25 +1086,28 @@ int launch_render(pt_scene* S, const pt_render_params* p, float* out_dev, int mo
     // Is the previous call's frame still on the GPU?  If not there is nothing to overlap with, and this frame runs on the
     // caller's stream as with one slot: a caller that synchronises after every frame (a display loop) does not pay for two
     // event waits across streams per frame.
+    const bool cont = ad && ad->round > 0;               // a later adaptive round: continues the frame of round 0
     bool prev_busy = false;
-    if (in_flight > 1 && S->frame_seq > 0 && S->cur().used) {
+    if (!cont && in_flight > 1 && S->frame_seq > 0 && S->cur().used) {
         prev_busy = hipEventQuery(S->cur().free_ev) == hipErrorNotReady;
         (void)hipGetLastError();
     }
-    S->cur_slot = (int)(S->frame_seq % (uint64_t)in_flight);
+    if (!cont) S->cur_slot = (int)(S->frame_seq % (uint64_t)in_flight);
     pt_scene::FrameSlot& slot = S->cur();
     if ((rc = slot.ctl.ensure(kWorkWords + kNumCounters))) return rc;
     if (!slot.free_ev) HIP_TRY(hipEventCreateWithFlags(&slot.free_ev, hipEventDisableTiming));
     S->last_stream = stream;
     S->have_timing = false;
-    S->info_passes = 0;
-    {   // this call's slot of the timing ring
+    if (!cont) {
+        S->info_passes = 0;
+        // this call's slot of the timing ring
         const size_t ring = (size_t)std::max<int64_t>(1, S->opt_timing_frames);
         if (S->frames.size() != ring) { S->drop_events(); S->frames.resize(ring); }
+        S->frames[S->frame_seq % S->frames.size()].passes = 0;
+        S->frame_seq++;
     }
-    pt_scene::FrameRec& frec = S->frames[S->frame_seq % S->frames.size()];
-    frec.passes = 0;
-    S->frame_seq++;
+    pt_scene::FrameRec& frec = S->frames[(S->frame_seq - 1) % S->frames.size()];
+    const size_t pass_base = frec.passes;               // passes of earlier adaptive rounds of this frame
     if (rows.count == 0) {           // nothing to trace: the frame's counters read zero
         if (slot.used && slot.free_stream != stream) HIP_TRY(hipStreamWaitEvent(stream, slot.free_ev, 0));
         HIP_TRY(hipMemsetAsync(slot.ctl.p, 0, (kWorkWords + kTimelineBase) * sizeof(unsigned long long), stream));
@@ -1053,7 +1116,10 @@ int launch_render(pt_scene* S, const pt_render_params* p, float* out_dev, int mo
         return PT_OK;
     }
 
-    const uint64_t npix = (uint64_t)rows.count * (uint64_t)p->width;
+    // a listed adaptive round is a frame of n_list rows of width 1 (RenderDev::list)
+    const bool listed = ad && ad->args.list_in;
+    const int vrows = listed ? (int)ad->n_list : rows.count, vwidth = listed ? 1 : p->width;
+    const uint64_t npix = (uint64_t)vrows * (uint64_t)vwidth;
     if (npix > (1ull << 30)) return fail(PT_ERR_INVALID_ARG, "more than 2^30 pixels per call");
     // samples per pass: bounded by the scratch budget and by 2^30 work items per launch
     uint64_t scratch = S->opt_scratch_bytes > 0 ? (uint64_t)S->opt_scratch_bytes : kDefaultScratchBytes;
@@ -1077,7 +1143,7 @@ int launch_render(pt_scene* S, const pt_render_params* p, float* out_dev, int mo
     const int n_pass = (int)(((uint64_t)p->spp + spp_pass - 1) / spp_pass);
     if (mode == 2 && n_pass > 1)
         return fail(PT_ERR_UNSUPPORTED, "pt_render_accumulate: spp of one call must fit the scratch budget (single pass)");
-    if (n_pass > 1 && (rc = S->accum.ensure(npix * 3))) return rc;
+    if (n_pass > 1 && !ad && (rc = S->accum.ensure(npix * 3))) return rc;
 
     const int traversal = p->traversal == PT_TRAVERSAL_DEFAULT ? PT_TRAVERSAL_EXACT : p->traversal;
     if (traversal != PT_TRAVERSAL_EXACT && traversal != PT_TRAVERSAL_PRUNED) return fail(PT_ERR_INVALID_ARG, "unknown traversal mode");
@@ -1096,7 +1162,7 @@ int launch_render(pt_scene* S, const pt_render_params* p, float* out_dev, int mo
         return fail(PT_ERR_UNSUPPORTED, "PT_RENDER_NEE runs on the default kernel with exact traversal only");
     // kernel 3 (paths regrouped across the waves of a workgroup) serves exact traversal without next-event estimation; those run
     // on kernel 2
-    const bool use_q = S->opt_kernel == 3 && !nee && traversal == PT_TRAVERSAL_EXACT;
+    const bool use_q = S->opt_kernel == 3 && !nee && traversal == PT_TRAVERSAL_EXACT && !listed;
     QParams qp{};
     TraceFnQ fnq = nullptr;
     TraceFn fn = nullptr;
@@ -1105,7 +1171,8 @@ int launch_render(pt_scene* S, const pt_render_params* p, float* out_dev, int mo
         if (lp.total > S->lds_per_block_max) return fail(PT_ERR_DEVICE, "LDS plan exceeds the per-block limit");
         fnq = pick_kernel_q(S, res, which == 1);
     } else {
-        fn = nee ? pick_kernel_nee(res, S->opt_stats != 0, (S->tri_only && S->diffuse_only && S->opt_specialize) ? 2 : 0)
+        fn = listed ? pick_kernel_list(S, res, traversal == PT_TRAVERSAL_PRUNED, S->opt_stats != 0, which == 1, nee)
+           : nee ? pick_kernel_nee(res, S->opt_stats != 0, (S->tri_only && S->diffuse_only && S->opt_specialize) ? 2 : 0)
                  : pick_kernel(S, res, traversal == PT_TRAVERSAL_PRUNED, S->opt_stats != 0, which == 1);
         if (!fn) return fail(PT_ERR_INVALID_ARG, "no kernel variant compiled for these v2_thresh / v2_inner options");
     }
@@ -1130,7 +1197,7 @@ int launch_render(pt_scene* S, const pt_render_params* p, float* out_dev, int mo
     // With three slots a frame takes half of each CU — two frames are resident side by side, half a frame apart, the third
     // enters where the first leaves — with two slots all but one block per CU (cbox 2.55 ms per frame with full grids,
     // 2.50 with 5 + 1 of 6, 2.49 with 3 + 3 and three slots; bunny 4.64 / 4.53 / 4.39; profiles/r03_frames_in_flight.log).
-    const bool own_stream = in_flight > 1 && n_pass == 1 && prev_busy;
+    const bool own_stream = !ad && in_flight > 1 && n_pass == 1 && prev_busy;
     if (own_stream && S->opt_blocks_per_cu <= 0) bpc = std::max(1, in_flight >= 3 ? bpc / 2 : bpc - 1);
     S->info_kernel = use_q ? 3 : S->opt_kernel == 1 ? 1 : 2;
     S->info_occupancy = occ;
@@ -1171,7 +1238,8 @@ int launch_render(pt_scene* S, const pt_render_params* p, float* out_dev, int mo
     }
     if (slot.used && slot.free_stream != tstream) HIP_TRY(hipStreamWaitEvent(tstream, slot.free_ev, 0));   // the resolve that last read this slot's samples
     // one memset per frame: work counters + the 64 counter slots (+ timeline / histograms when a STATS kernel will run)
-    HIP_TRY(hipMemsetAsync(slot.ctl.p, 0, (kWorkWords + (S->opt_stats ? kNumCounters : kTimelineBase)) * sizeof(unsigned long long), tstream));
+    // (a later adaptive round clears the work counters only: the frame's statistics run on over all its rounds)
+    HIP_TRY(hipMemsetAsync(slot.ctl.p, 0, (kWorkWords + (cont ? 0 : S->opt_stats ? kNumCounters : kTimelineBase)) * sizeof(unsigned long long), tstream));
     for (int pass = 0; pass < n_pass; pass++) {
         const int s0 = pass * (int)spp_pass;
         const int sn = std::min<int>((int)spp_pass, p->spp - s0);
@@ -1180,8 +1248,11 @@ int launch_render(pt_scene* S, const pt_render_params* p, float* out_dev, int mo
         std::memcpy(rd.cam_top_left, p->cam_top_left, 12);
         std::memcpy(rd.cam_horizontal, p->cam_horizontal, 12);
         std::memcpy(rd.cam_vertical, p->cam_vertical, 12);
-        rd.width = p->width; rd.height = p->height;
-        rd.row_begin = rows.begin; rd.row_step = rows.step; rd.num_rows = rows.count;
+        rd.width = vwidth; rd.height = p->height;
+        rd.row_begin = rows.begin; rd.row_step = rows.step; rd.num_rows = vrows;
+        rd.list = listed ? ad->args.list_in : nullptr;
+        rd.img_width = p->width;
+        rd.div_img_width = make_fastdiv((uint32_t)p->width);
         rd.spp_pass = sn;
         rd.sample_base = p->sample_offset + s0;
         rd.stream_stride = p->stream_stride > 0 ? p->stream_stride : p->spp;
@@ -1191,15 +1262,15 @@ int launch_render(pt_scene* S, const pt_render_params* p, float* out_dev, int mo
         rd.npix = (uint32_t)npix;
         rd.total_work = (uint32_t)(npix * (uint64_t)sn);
         rd.num_regions = S->opt_xcd_regions > 0 ? (int)std::min<int64_t>(S->opt_xcd_regions, 8) : 8;
-        rd.rows_per_region = (rows.count + rd.num_regions - 1) / rd.num_regions;
-        rd.div_width = make_fastdiv((uint32_t)p->width);
+        rd.rows_per_region = (vrows + rd.num_regions - 1) / rd.num_regions;
+        rd.div_width = make_fastdiv((uint32_t)vwidth);
         rd.div_spp = make_fastdiv((uint32_t)sn);
         rd.row_major = S->opt_item_order == 1 ? 1 : 0;
-        rd.div_npix_full = make_fastdiv((uint32_t)rd.rows_per_region * (uint32_t)p->width);
+        rd.div_npix_full = make_fastdiv((uint32_t)rd.rows_per_region * (uint32_t)vwidth);
         {   // the band that holds the remainder rows (all bands after it are empty)
-            const int full = rows.count / rd.rows_per_region, rest = rows.count - full * rd.rows_per_region;
+            const int full = vrows / rd.rows_per_region, rest = vrows - full * rd.rows_per_region;
             rd.short_region = rest ? full : -1;
-            rd.div_npix_last = make_fastdiv((uint32_t)std::max(rest, 1) * (uint32_t)p->width);
+            rd.div_npix_last = make_fastdiv((uint32_t)std::max(rest, 1) * (uint32_t)vwidth);
         }
 
         const int grid = launch_grid(S->num_cus, bpc, rd.total_work, block_threads);
@@ -1216,7 +1287,8 @@ int launch_render(pt_scene* S, const pt_render_params* p, float* out_dev, int mo
                  : per_wave >= 4 * kMaxChunk ? kMaxChunk : (uint32_t)std::max<uint64_t>(64, std::min<uint64_t>(kMaxChunk, (per_wave / 64) * 64));
         if (S->opt_chunk > 0) rd.chunk = (uint32_t)std::min<int64_t>(kMaxChunk, std::max<int64_t>(64, (S->opt_chunk / 64) * 64));
 
-        if (timing && frec.ev.size() <= (size_t)pass) {
+        const size_t ev_pass = pass_base + (size_t)pass;
+        if (timing && frec.ev.size() <= ev_pass) {
             pt_scene::PassEvents fresh{};
             hipError_t ee = hipEventCreate(&fresh.t0);
             if (ee == hipSuccess && (ee = hipEventCreate(&fresh.t1)) != hipSuccess) (void)hipEventDestroy(fresh.t0);
@@ -1225,7 +1297,7 @@ int launch_render(pt_scene* S, const pt_render_params* p, float* out_dev, int mo
             if (ee != hipSuccess) return fail(PT_ERR_DEVICE, std::string("hipEventCreate: ") + hipGetErrorString(ee));
             frec.ev.push_back(fresh);
         }
-        const pt_scene::PassEvents pe = timing ? frec.ev[pass] : pt_scene::PassEvents{};
+        const pt_scene::PassEvents pe = timing ? frec.ev[ev_pass] : pt_scene::PassEvents{};
         if (pass > 0) HIP_TRY(hipMemsetAsync(slot.ctl.p, 0, kWorkBytes, tstream));
         if (timing) HIP_TRY(hipEventRecord(pe.t0, tstream));
         if (use_q)
@@ -1252,15 +1324,24 @@ int launch_render(pt_scene* S, const pt_render_params* p, float* out_dev, int mo
         } else {
             rmode = 1; rfirst = first ? 1 : 0;
         }
-        hipLaunchKernelGGL(resolve_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, tstream, slot.samples.p, accum,
-                           out_dev, (uint32_t)npix, sn, rmode, rfirst, scale);
+        if (ad) {
+            AdaptiveArgs aa = ad->args;
+            aa.n = (uint32_t)npix;
+            aa.spp_pass = sn;
+            aa.first = ad->round == 0 && first;
+            aa.check = last;
+            hipLaunchKernelGGL(adaptive_resolve_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, tstream, slot.samples.p, aa);
+        } else {
+            hipLaunchKernelGGL(resolve_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, tstream, slot.samples.p, accum,
+                               out_dev, (uint32_t)npix, sn, rmode, rfirst, scale);
+        }
         HIP_TRY(hipGetLastError());
         if (timing) HIP_TRY(hipEventRecord(pe.r1, tstream));
         HIP_TRY(hipEventRecord(slot.free_ev, tstream));
         slot.used = true; slot.free_stream = tstream;
         if (own_stream) HIP_TRY(hipStreamWaitEvent(stream, slot.free_ev, 0));
         S->info_passes++;
-        if (timing) frec.passes = (size_t)pass + 1;
+        if (timing) frec.passes = ev_pass + 1;
     }
     S->have_timing = timing;
     return PT_OK;
@@ -1327,6 +1408,8 @@ int pt_scene_destroy(pt_scene* S) {
     if (S->last_stream || S->have_timing) (void)hipDeviceSynchronize();
     for (auto& T : S->tree) { T.nodes.release(); T.nodes_oct.release(); } S->drop_slots(); S->prims.release(); S->normals.release(); S->materials.release(); S->emission.release();
     S->lights.release(); S->accum.release(); S->fb_tmp.release();
+    S->ad_sum.release(); S->ad_mom.release(); S->ad_list[0].release(); S->ad_list[1].release(); S->ad_count.release();
+    S->ad_spp_tmp.release(); S->ad_err_tmp.release();
     S->drop_events();
     delete S;
     return PT_OK;
@@ -1360,6 +1443,101 @@ int pt_render(pt_scene* S, const pt_render_params* p, float* fb, int fb_on_devic
     if (rc) return rc;
     HIP_TRY(hipMemcpy(fb, S->fb_tmp.p, n * sizeof(float), hipMemcpyDeviceToHost));
     return check_schedule_error(S);
+}
+
+int pt_render_adaptive(pt_scene* S, const pt_render_params* p, const pt_adaptive_params* a, float* fb, int32_t* spp_map,
+                       float* err_map, int on_device) {
+    if (!S || !p || !a || !fb) return fail(PT_ERR_INVALID_ARG, "null argument");
+    if (p->width <= 0 || p->height <= 0 || p->spp <= 0) return fail(PT_ERR_INVALID_ARG, "width, height and spp must be positive");
+    if (a->batch_spp < 0 || a->max_spp < 0) return fail(PT_ERR_INVALID_ARG, "negative batch_spp / max_spp");
+    const int64_t max_spp = a->max_spp > 0 ? a->max_spp : 32 * (int64_t)p->spp;
+    const int batch = a->batch_spp > 0 ? a->batch_spp : p->spp;
+    if (max_spp < p->spp) return fail(PT_ERR_INVALID_ARG, "max_spp below spp (the first round)");
+    if (max_spp > (1 << 20)) return fail(PT_ERR_INVALID_ARG, "max_spp above 2^20");
+    if (!(a->max_error > 0.0f) || !std::isfinite(a->max_error)) return fail(PT_ERR_INVALID_ARG, "max_error must be positive and finite");
+    if (a->p_value != 0.0f && !(a->p_value > 0.0f && a->p_value < 1.0f)) return fail(PT_ERR_INVALID_ARG, "p_value must lie in (0, 1)");
+    if (!(a->min_luminance >= 0.0f) || !std::isfinite(a->min_luminance))
+        return fail(PT_ERR_INVALID_ARG, "min_luminance must be finite and >= 0");
+    if (p->sample_offset != 0) return fail(PT_ERR_INVALID_ARG, "pt_render_adaptive: sample_offset must be 0");
+    if (p->stream_stride != 0 && p->stream_stride < max_spp)
+        return fail(PT_ERR_INVALID_ARG, "stream_stride below max_spp: PCG streams of neighbouring pixels would overlap");
+    RowSel rows;
+    int rc = select_rows(p, &rows);
+    if (rc) return rc;
+    const uint64_t npix = (uint64_t)rows.count * (uint64_t)p->width;
+    if (npix > (1ull << 30)) return fail(PT_ERR_INVALID_ARG, "more than 2^30 pixels per call");
+    // z = Phi^-1(1 - p/2): the root of erfc(z / sqrt 2) = p, by bisection (erfc falls monotonically)
+    const double pv = a->p_value != 0.0f ? (double)a->p_value : 0.05;
+    double zlo = 0.0, zhi = 64.0;
+    for (int k = 0; k < 200; k++) {
+        const double mid = 0.5 * (zlo + zhi);
+        (std::erfc(mid / std::sqrt(2.0)) > pv ? zlo : zhi) = mid;
+    }
+    DeviceGuard guard;
+    { int grc = guard.enter(S->device); if (grc) return grc; }
+    S->info_adaptive_rounds = 0;
+    pt_render_params pr = *p;
+    pr.stream_stride = p->stream_stride > 0 ? p->stream_stride : (int32_t)max_spp;
+    if (npix == 0) {                 // no rows selected: an empty frame (its counters read zero)
+        if ((rc = launch_render(S, &pr, fb, 0, nullptr))) return rc;
+        HIP_TRY(hipStreamSynchronize(nullptr));
+        return PT_OK;
+    }
+    if ((rc = S->ad_sum.ensure(npix * 3)) || (rc = S->ad_mom.ensure(npix * 2)) || (rc = S->ad_list[0].ensure(npix)) ||
+        (rc = S->ad_list[1].ensure(npix)) || (rc = S->ad_count.ensure(1)))
+        return rc;
+    float* fb_d = fb;
+    int32_t* spp_d = spp_map;
+    float* err_d = err_map;
+    if (!on_device) {
+        if ((rc = S->fb_tmp.ensure(npix * 3))) return rc;
+        fb_d = S->fb_tmp.p;
+        if (spp_map && (rc = S->ad_spp_tmp.ensure(npix))) return rc;
+        if (err_map && (rc = S->ad_err_tmp.ensure(npix))) return rc;
+        spp_d = spp_map ? S->ad_spp_tmp.p : nullptr;
+        err_d = err_map ? S->ad_err_tmp.p : nullptr;
+    }
+    AdaptiveRound ar{};
+    ar.args.z = 0.5 * (zlo + zhi);
+    ar.args.max_error = a->max_error;
+    ar.args.min_luminance = a->min_luminance;
+    ar.args.max_spp = (int)max_spp;
+    ar.args.sum = S->ad_sum.p;
+    ar.args.mom = S->ad_mom.p;
+    ar.args.count_out = S->ad_count.p;
+    ar.args.fb = fb_d;
+    ar.args.spp_map = spp_d;
+    ar.args.err_map = err_d;
+    // checkpoints n = spp, spp + batch, spp + 2 batch, ... cut at max_spp: they depend on these three numbers only (a round too
+    // big for the scratch budget runs in several sample passes before its one check)
+    int n = 0;
+    uint32_t n_list = (uint32_t)npix;
+    for (int round = 0;; round++) {
+        const int spp_r = round == 0 ? p->spp : (int)std::min<int64_t>(batch, max_spp - n);
+        pr.spp = spp_r;
+        pr.sample_offset = n;
+        ar.round = round;
+        ar.n_list = n_list;
+        ar.args.list_in = round == 0 ? nullptr : S->ad_list[(round - 1) & 1].p;
+        ar.args.list_out = S->ad_list[round & 1].p;
+        ar.args.n_total = n + spp_r;
+        HIP_TRY(hipMemsetAsync(S->ad_count.p, 0, sizeof(uint32_t), nullptr));
+        if ((rc = launch_render(S, &pr, fb_d, 0, nullptr, &ar))) return rc;
+        n += spp_r;
+        S->info_adaptive_rounds = round + 1;
+        HIP_TRY(hipMemcpy(&n_list, S->ad_count.p, sizeof(uint32_t), hipMemcpyDeviceToHost));   // the one read-back per round
+        if (n_list == 0) break;
+        if (n >= max_spp || n_list > npix) return fail(PT_ERR_DEVICE, "internal error: adaptive list after the last checkpoint");
+    }
+    if ((rc = check_schedule_error(S))) return rc;
+    if (!on_device) {
+        HIP_TRY(hipMemcpy(fb, fb_d, npix * 3 * sizeof(float), hipMemcpyDeviceToHost));
+        if (spp_map) HIP_TRY(hipMemcpy(spp_map, spp_d, npix * sizeof(int32_t), hipMemcpyDeviceToHost));
+        if (err_map) HIP_TRY(hipMemcpy(err_map, err_d, npix * sizeof(float), hipMemcpyDeviceToHost));
+    } else {
+        HIP_TRY(hipStreamSynchronize(nullptr));
+    }
+    return PT_OK;
 }
 
 int pt_get_counters(pt_scene* S, pt_counters* out) {
@@ -1443,6 +1621,7 @@ int pt_scene_get_info(pt_scene* S, const char* key, int64_t* value) {
     else if (k == "lds_scene") *value = S->info_lds_scene;
     else if (k == "residency") *value = scene_residency(S, which_tree(S));
     else if (k == "passes") *value = S->info_passes;
+    else if (k == "adaptive_rounds") *value = S->info_adaptive_rounds;
     else if (k == "occupancy") *value = S->info_occupancy;                // what the occupancy query allows
     else if (k == "blocks_per_cu") *value = S->info_blocks_per_cu;        // what the last launch used
     else if (k == "redo_segments") {                                     // STATS: segments rerun in reference order by the last render

@@ -91,6 +91,8 @@ struct PathStart {
 };
 
 // main.cu:32-44 for region-local work item `item` of `region`: (sample, pixel) -> PCG stream, jitter, primary ray.
+// LIST: an adaptive round after the first (RenderDev::list), a compile-time variant so that plain frames keep their code.
+template <bool LIST = false>
 __device__ __forceinline__ PathStart start_path(const RenderDev& rp, uint32_t region, uint32_t item) {
     const uint32_t npix_r = region_rows(rp, region) * (uint32_t)rp.width;
     uint32_t s_local, rr;
@@ -109,13 +111,22 @@ __device__ __forceinline__ PathStart start_path(const RenderDev& rp, uint32_t re
         i = (int)(pix_r - rr * (uint32_t)rp.width);
     }
     const uint32_t local_row = region * (uint32_t)rp.rows_per_region + rr;
-    const int j = rp.row_begin + (int)local_row * rp.row_step;
-    const uint64_t pixel_index = (uint64_t)j * (uint64_t)rp.width + (uint64_t)i;
+    // adaptive rounds: local_row is a position in the list of pixels still sampled (a frame of width 1, i == 0)
+    uint32_t img_row = local_row;
+    int col = i;
+    if (LIST) {
+        const uint32_t e = rp.list[local_row];
+        img_row = fastdiv(e, rp.div_img_width);
+        col = (int)(e - img_row * (uint32_t)rp.img_width);
+    }
+    const int32_t img_width = LIST ? rp.img_width : rp.width;
+    const int j = rp.row_begin + (int)img_row * rp.row_step;
+    const uint64_t pixel_index = (uint64_t)j * (uint64_t)img_width + (uint64_t)col;
     const uint64_t stream = pixel_index * (uint64_t)rp.stream_stride + (uint64_t)(rp.sample_base + (int)s_local);
     PathStart ps;
     ps.rng = ptm::pcg_init(stream, rp.seed);
     const float ru = ptm::pcg_float(ps.rng);
-    const float u = ((float)i + ru) / (float)rp.width;
+    const float u = ((float)col + ru) / (float)img_width;
     const float rv = ptm::pcg_float(ps.rng);
     const float v = ((float)j + rv) / (float)rp.height;
     ps.ray = ptd::primary_ray(rp, u, v);
@@ -219,7 +230,7 @@ __device__ __forceinline__ void flush_counters(unsigned long long* counters, int
     }
 }
 
-template <bool LDS_SCENE, bool PRUNE, bool STATS>
+template <bool LDS_SCENE, bool PRUNE, bool STATS, bool LIST = false>
 __global__ __launch_bounds__(kBlock) void trace_kernel(SceneDev scn, RenderDev rp, LdsPlan lp,
                                                        float4* __restrict__ samples,
                                                        uint32_t* __restrict__ work_counter,
@@ -255,7 +266,7 @@ __global__ __launch_bounds__(kBlock) void trace_kernel(SceneDev scn, RenderDev r
                 const uint32_t rank = lane_rank(need);
                 const uint32_t n = (uint32_t)__popcll(need);
                 if (!alive && rank < avail) {
-                    const PathStart ps = start_path(rp, feed.region, feed.cur + rank);
+                    const PathStart ps = start_path<LIST>(rp, feed.region, feed.cur + rank);
                     ray = ps.ray;
                     rng = ps.rng;
                     my_w = ps.sample_index;
@@ -307,7 +318,8 @@ __global__ __launch_bounds__(kBlock) void trace_kernel(SceneDev scn, RenderDev r
 // with the top of the tree cached in LDS.  MINW = minimum waves per SIMD the register allocation must allow.
 // NEE = built with next-event estimation (PT_RENDER_NEE): a lane alternates between closest-hit traversals and the
 // any-hit traversal of its light sample's shadow ray; the same step functions serve both.
-template <int RES, bool PRUNE, bool STATS, int THRESH, int INNER, int MINW, int SPEC, bool NEE = false>
+// LIST = adaptive rounds after the first (start_path).
+template <int RES, bool PRUNE, bool STATS, int THRESH, int INNER, int MINW, int SPEC, bool NEE = false, bool LIST = false>
 __global__ __launch_bounds__(kBlock, (kBlock > 256 ? 1 : MINW)) void trace_kernel_v2(SceneDev scn, RenderDev rp, LdsPlan lp,
                                                           float4* __restrict__ samples,
                                                           uint32_t* __restrict__ work_counter,
@@ -435,7 +447,7 @@ __global__ __launch_bounds__(kBlock, (kBlock > 256 ? 1 : MINW)) void trace_kerne
                     const uint32_t rank = lane_rank(need);
                     const uint32_t n = (uint32_t)__popcll(need);
                     if (idle && !alive && rank < avail) {
-                        const PathStart ps = start_path(rp, feed.region, feed.cur + rank);
+                        const PathStart ps = start_path<LIST>(rp, feed.region, feed.cur + rank);
                         ray = ps.ray;
                         rng = ps.rng;
                         my_w = ps.sample_index;
@@ -605,6 +617,85 @@ __global__ __launch_bounds__(256) void resolve_kernel(const float4* __restrict__
         }
         accum[3 * (size_t)pix] = sum.x; accum[3 * (size_t)pix + 1] = sum.y; accum[3 * (size_t)pix + 2] = sum.z;
     }
+}
+
+// pt_render_adaptive: one thread per entry of the round's pixel list (round 0: no list, entry = packed pixel id).  Continues the
+// pixel's fp32 sum (the order of resolve_kernel: ((0 + s0) + s1) + ...) and its fp64 moments S1 = sum Y, S2 = sum Y^2 over the
+// pass's samples [spp_pass][n], sample by sample.  On the last pass of a round (check) it applies the stopping rule at
+// n_total samples (pt_api.h): a pixel that stops gets fb = sum * (1/n), spp_map and err_map; the others are appended to
+// list_out, one atomic per wave.  The list order may differ from run to run; no output depends on it.
+struct AdaptiveArgs {
+    const uint32_t* list_in;        // nullptr = round 0 (entry t is pixel t)
+    uint32_t n;                     // entries of this round
+    int spp_pass;                   // samples of this pass
+    int first;                      // first pass of the first round: sums start from zero
+    int check;                      // last pass of a round: apply the rule at n_total
+    int n_total;                    // samples of every listed pixel after this round
+    int max_spp;
+    double z;                       // Phi^-1(1 - p/2)
+    double max_error, min_luminance;
+    float* sum;                     // [npix][3]
+    double* mom;                    // [npix][2]
+    uint32_t* list_out;
+    uint32_t* count_out;
+    float* fb;                      // [npix][3]
+    int32_t* spp_map;               // [npix] or nullptr
+    float* err_map;                 // [npix] or nullptr
+};
+
+__global__ __launch_bounds__(256) void adaptive_resolve_kernel(const float4* __restrict__ samples, AdaptiveArgs a) {
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    const bool in = t < a.n;
+    bool more = false;
+    uint32_t pix = 0;
+    if (in) {
+        pix = a.list_in ? a.list_in[t] : t;
+        ptm::V3 sum = ptm::mk(0, 0, 0);
+        double s1 = 0.0, s2 = 0.0;
+        if (!a.first) {
+            sum = ptm::mk(a.sum[3 * (size_t)pix], a.sum[3 * (size_t)pix + 1], a.sum[3 * (size_t)pix + 2]);
+            s1 = a.mom[2 * (size_t)pix]; s2 = a.mom[2 * (size_t)pix + 1];
+        }
+        for (int s = 0; s < a.spp_pass; s++) {
+            const float4 v = samples[(size_t)s * a.n + t];
+            sum = sum + ptm::mk(v.x, v.y, v.z);
+            const double y = 0.2126 * (double)v.x + 0.7152 * (double)v.y + 0.0722 * (double)v.z;   // no contraction (-ffp-contract=off)
+            s1 = s1 + y;
+            s2 = s2 + y * y;
+        }
+        bool stop = false;
+        double err = 0.0;
+        if (a.check) {
+            const double n = (double)a.n_total;
+            double var = __builtin_inf();
+            if (a.n_total > 1) {
+                const double v = (s2 - s1 * s1 / n) / (n - 1.0);
+                var = v < 0.0 ? 0.0 : v;                    // NaN stays NaN
+            }
+            const double half = a.z * sqrt(var / n);
+            const double mean = s1 / n;
+            const double den = mean < a.min_luminance ? a.min_luminance : mean;
+            err = half == 0.0 ? 0.0 : half / den;
+            stop = err <= a.max_error || a.n_total >= a.max_spp;
+        }
+        if (stop) {
+            sum = sum * (1.0f / (float)a.n_total);          // resolve_kernel / the oracle: sum * (1/spp), correctly rounded
+            a.fb[3 * (size_t)pix] = sum.x; a.fb[3 * (size_t)pix + 1] = sum.y; a.fb[3 * (size_t)pix + 2] = sum.z;
+            if (a.spp_map) a.spp_map[pix] = a.n_total;
+            if (a.err_map) a.err_map[pix] = (float)err;
+        } else {
+            a.sum[3 * (size_t)pix] = sum.x; a.sum[3 * (size_t)pix + 1] = sum.y; a.sum[3 * (size_t)pix + 2] = sum.z;
+            a.mom[2 * (size_t)pix] = s1; a.mom[2 * (size_t)pix + 1] = s2;
+            more = a.check != 0;
+        }
+    }
+    const unsigned long long mask = __ballot(more);
+    if (mask == 0ull) return;
+    const int lane = threadIdx.x & 63;
+    uint32_t base = 0;
+    if (lane == 0) base = atomicAdd(a.count_out, (uint32_t)__popcll(mask));
+    base = __shfl(base, 0, 64);
+    if (more) a.list_out[base + lane_rank(mask)] = pix;
 }
 
 template <bool PRUNE>

@@ -82,6 +82,12 @@ class PtCounters(C.Structure):
                 ("leaf_tests", C.c_uint64), ("kernel_ms", C.c_double), ("resolve_ms", C.c_double)]
 
 
+class PtAdaptiveParams(C.Structure):
+    """pt_adaptive_params (pt_api.h): per-pixel sample counts from a noise target (pt_render_adaptive)."""
+    _fields_ = [("batch_spp", C.c_int32), ("max_spp", C.c_int32), ("max_error", C.c_float), ("p_value", C.c_float),
+                ("min_luminance", C.c_float)]
+
+
 class PtCamera(C.Structure):
     _fields_ = [("lookfrom", c_float3), ("lookat", c_float3), ("up", c_float3), ("vfov", C.c_float),
                 ("width", C.c_int32), ("height", C.c_int32), ("spp", C.c_int32)]

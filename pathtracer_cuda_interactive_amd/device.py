@@ -9,7 +9,8 @@ import os
 import numpy as np
 
 from . import _build
-from .ctypes_defs import (PT_OK, PT_TRAVERSAL_DEFAULT, PtBvhNode, PtCounters, PtError, PtRenderParams, PtSceneDesc)
+from .ctypes_defs import (PT_OK, PT_TRAVERSAL_DEFAULT, PtAdaptiveParams, PtBvhNode, PtCounters, PtError, PtRenderParams,
+                          PtSceneDesc)
 
 _lib = None
 
@@ -17,7 +18,7 @@ EXPORTS = [
     "pt_api_version", "pt_last_error", "pt_scene_create", "pt_scene_destroy", "pt_render", "pt_render_async",
     "pt_render_accumulate", "pt_get_counters", "pt_scene_set_option", "pt_scene_get_info", "pt_debug_math",
     "pt_debug_intersect", "pt_debug_math_host", "pt_bvh_build_device", "pt_bvh_build_sweep", "pt_get_frame_times", "pt_bvh_build_sweep_device",
-    "pt_debug_exact_math",
+    "pt_debug_exact_math", "pt_render_adaptive",
 ]
 
 
@@ -38,6 +39,7 @@ def lib():
         L.pt_render.argtypes = [vp, C.POINTER(PtRenderParams), vp, C.c_int]
         L.pt_render_async.argtypes = [vp, C.POINTER(PtRenderParams), vp, vp]
         L.pt_render_accumulate.argtypes = [vp, C.POINTER(PtRenderParams), vp, vp]
+        L.pt_render_adaptive.argtypes = [vp, C.POINTER(PtRenderParams), C.POINTER(PtAdaptiveParams), vp, vp, vp, C.c_int]
         L.pt_get_counters.argtypes = [vp, C.POINTER(PtCounters)]
         L.pt_get_frame_times.argtypes = [vp, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int)]
         L.pt_scene_set_option.argtypes = [vp, C.c_char_p, C.c_int64]
@@ -104,6 +106,35 @@ class DeviceScene:
         if traversal is not None:
             p.traversal = traversal
         _check(lib().pt_render_async(self._h, C.byref(p), C.c_void_p(dev_ptr), C.c_void_p(stream or 0)))
+
+    @staticmethod
+    def adaptive_params(max_error, batch_spp=0, max_spp=0, p_value=0.05, min_luminance=0.01):
+        return PtAdaptiveParams(int(batch_spp), int(max_spp), float(max_error), float(p_value), float(min_luminance))
+
+    def render_adaptive(self, params, max_error, batch_spp=0, max_spp=0, p_value=0.05, min_luminance=0.01, traversal=None):
+        """Blocking adaptive render (pt_render_adaptive): returns host arrays (image [rows, W, 3] float32,
+        spp_map [rows, W] int32, err_map [rows, W] float32)."""
+        p = params.copy()
+        if traversal is not None:
+            p.traversal = traversal
+        a = self.adaptive_params(max_error, batch_spp, max_spp, p_value, min_luminance)
+        img = np.empty((p.num_rows(), p.width, 3), dtype=np.float32)
+        spp = np.empty((p.num_rows(), p.width), dtype=np.int32)
+        err = np.empty((p.num_rows(), p.width), dtype=np.float32)
+        _check(lib().pt_render_adaptive(self._h, C.byref(p), C.byref(a), img.ctypes.data_as(C.c_void_p),
+                                        spp.ctypes.data_as(C.c_void_p), err.ctypes.data_as(C.c_void_p), 0))
+        return img, spp, err
+
+    def render_adaptive_into(self, params, fb_ptr, spp_ptr, err_ptr, max_error, batch_spp=0, max_spp=0, p_value=0.05,
+                             min_luminance=0.01, traversal=None):
+        """Adaptive render into device memory (fb [rows, W, 3] float32, spp_map [rows, W] int32, err_map [rows, W] float32;
+        spp_ptr / err_ptr may be 0).  Blocking: it runs on the default stream and returns when the frame is done."""
+        p = params.copy()
+        if traversal is not None:
+            p.traversal = traversal
+        a = self.adaptive_params(max_error, batch_spp, max_spp, p_value, min_luminance)
+        _check(lib().pt_render_adaptive(self._h, C.byref(p), C.byref(a), C.c_void_p(fb_ptr), C.c_void_p(spp_ptr or 0),
+                                        C.c_void_p(err_ptr or 0), 1))
 
     def accumulate_into(self, params, dev_ptr, stream=None):
         _check(lib().pt_render_accumulate(self._h, C.byref(params), C.c_void_p(dev_ptr), C.c_void_p(stream or 0)))

@@ -2,6 +2,7 @@
 """Offline render front-end (what the reference's main.cu does up to line 266, minus the window):
    python tools/render.py <scene.xml|scene.pts|buddha_standin|dragon_standin> [-o out.pfm|out.ppm] [--width W --height H --spp S]
                           [--traversal exact|pruned] [--seed 1984] [--bvh reference|lbvh|sah] [--nee]
+                          [--adaptive MAX_ERROR [--batch-spp B] [--max-spp M] [--p-value P] [--min-luminance L] [--spp-map map.pfm]]
 Needs a GPU (no CPU fallback).  Multi-GPU: launch with torchrun; rows are interleaved over ranks, rank 0 writes."""
 import argparse
 import os
@@ -24,7 +25,16 @@ def main():
     ap.add_argument("--bvh", default="reference", choices=["reference", "lbvh", "sah"],
                     help="reference: the host's reproduction of the reference tree (default); lbvh / sah: built on the GPU")
     ap.add_argument("--nee", action="store_true", help="next-event estimation (an extension: the reference samples no light)")
+    ap.add_argument("--adaptive", type=float, metavar="MAX_ERROR",
+                    help="adaptive sampling (an extension): sample each pixel until the relative half-width of its confidence "
+                         "interval is at most MAX_ERROR; --spp is the first round")
+    ap.add_argument("--batch-spp", type=int, default=0, help="adaptive: samples per later round (0 = --spp)")
+    ap.add_argument("--max-spp", type=int, default=0, help="adaptive: most samples of one pixel (0 = 32 x --spp)")
+    ap.add_argument("--p-value", type=float, default=0.05, help="adaptive: two-sided p-value of the interval")
+    ap.add_argument("--min-luminance", type=float, default=0.01, help="adaptive: floor of the relative test's denominator")
+    ap.add_argument("--spp-map", metavar="PATH", help="adaptive: write the per-pixel sample counts (PFM, the count in all channels)")
     a = ap.parse_args()
+    import numpy as np
     import torch
     import torch.distributed as dist
 
@@ -48,6 +58,26 @@ def main():
     p.traversal = PT_TRAVERSAL_PRUNED if a.traversal == "pruned" else PT_TRAVERSAL_EXACT
     p.flags = PT_RENDER_NEE if a.nee else 0
     R = D.ShardedRenderer(desc)
+    if a.adaptive is not None:
+        t_r = time.perf_counter()
+        out = R.render_adaptive(p, a.adaptive, a.batch_spp, a.max_spp, a.p_value, a.min_luminance, rank, world)
+        c = R.scene.counters()
+        torch.cuda.synchronize()
+        t2 = time.perf_counter()
+        if rank == 0:
+            frame, spp_map, _ = out
+            spp_map = spp_map.cpu().numpy()
+            write_image(a.output, frame.cpu().numpy())
+            if a.spp_map:
+                write_image(a.spp_map, np.repeat(spp_map[..., None].astype(np.float32), 3, axis=2))
+            print(f"{a.scene}: adaptive {p.width}x{p.height}, max_error {a.adaptive}, first round {p.spp} spp: "
+                  f"mean {spp_map.mean():.2f} spp (min {spp_map.min()}, max {spp_map.max()}), "
+                  f"{R.scene.info('adaptive_rounds')} rounds and kernel {c.kernel_ms:.2f} ms on rank 0, {t2 - t_r:.3f} s -> {a.output}"
+                  + (f", {a.spp_map}" if a.spp_map else ""))
+        R.close()
+        if world > 1:
+            dist.destroy_process_group()
+        return
     frame = R.render(p, rank, world)
     c = R.scene.counters()
     torch.cuda.synchronize()

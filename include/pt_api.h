@@ -311,7 +311,13 @@ int pt_bvh_build_sweep_device(const pt_scene_desc* desc, pt_bvh_node* out_nodes,
  * topology in internal form: the sweep tree did not win the probe), "fast_tree_depth",
  * "fast_tree_cost_permille" (probe-ray node visits, internal / caller's x 1000; 0 = none built), "stack_entries" (per lane),
  * "redo_segments" (with "stats": segments of the last frame traced on the caller's tree), "debug_reruns" (same for pt_debug_intersect),
- * "kernel" / "block_threads" (what the last render ran on), "frames_in_flight", "sweep_on_device" (the internal tree was built on the GPU),
+ * "kernel" / "block_threads" (what the last render ran on), "trace_variant" (the template arguments of the trace kernel that call
+ * launched last — for pt_render_adaptive the LIST kernel of its last round; 0 = none launched — packed into one value:
+ *     bits  0-3  family: 1 trace_kernel, 2 trace_kernel_v2, 3 trace_kernel_q      bit  10  NEE
+ *     bits  4-5  RES (family 1: LDS_SCENE)                                      bit  11  LIST
+ *     bit   6    PRUNE       bit 7  STATS       bits 8-9  SPEC                    bit  12  POSTPONE
+ *     bits 16-23 THRESH      bits 24-39 INNER, 16-bit two's complement          bits 40-43 MINW
+ *   a field the family's template does not have is 0), "frames_in_flight", "sweep_on_device" (the internal tree was built on the GPU),
  * "create_us0".."create_us6" (wall microseconds of pt_scene_create: total, primitive records, caller's tree checked and re-laid,
  * internal tree built, ... re-laid, uploads + probe, tie tables). */
 int pt_scene_set_option(pt_scene* scene, const char* key, int64_t value);

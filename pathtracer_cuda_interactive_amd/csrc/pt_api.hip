@@ -238,7 +238,7 @@ struct pt_scene {
     // wall time of pt_scene_create's stages, microseconds: [0] total [1] primitive records [2] caller's tree checked and re-laid
     // [3] internal tree built [4] ... re-laid [5] uploads + probe [6] tie tables; built_on_device: the sweep ran on the GPU
     int64_t create_us[7] = {0, 0, 0, 0, 0, 0, 0}, sweep_on_device = 0;
-    int64_t info_grid = 0, info_lds_bytes = 0, info_lds_scene = 0, info_passes = 0, info_occupancy = 0, info_blocks_per_cu = 0, info_debug_reruns = 0, fast_cost_permille = 0, info_kernel = 0;
+    int64_t info_grid = 0, info_lds_bytes = 0, info_lds_scene = 0, info_passes = 0, info_occupancy = 0, info_blocks_per_cu = 0, info_debug_reruns = 0, fast_cost_permille = 0, info_kernel = 0, info_trace_variant = 0;
     struct PassEvents { hipEvent_t t0, t1, r0, r1; };            // trace begin, trace end (on the trace kernel's stream); resolve begin, end (caller's)
     // HIP events of the last `opt_timing_frames` render calls (a ring; default 1): a caller that enqueues frame after frame
     // without a host sync in between — bench.py's timed loop — reads every frame's kernel time afterwards (pt_get_frame_times)
@@ -821,30 +821,54 @@ LdsPlan make_plan(const pt_scene* S, int res, bool stack16, int which = 0) {
 
 using TraceFn = void (*)(SceneDev, RenderDev, LdsPlan, float4*, uint32_t*, unsigned long long*);
 
-TraceFn pick_kernel_v1(bool lds, bool prune, bool stats) {
+// Info "trace_variant": the template arguments of a trace kernel in one int64 (packing: include/pt_api.h).  The pick_*
+// functions hand it back next to the kernel, both made from the same template arguments (v1k / v2k / qk), so that the
+// value reported for a launch cannot disagree with the kernel launched.
+constexpr int64_t trace_variant(int family, int res, bool prune, bool stats, int spec, bool nee, bool list, bool postpone,
+                                int thresh, int inner, int minw) {
+    return (int64_t)family | (int64_t)res << 4 | (int64_t)prune << 6 | (int64_t)stats << 7 | (int64_t)spec << 8 |
+           (int64_t)nee << 10 | (int64_t)list << 11 | (int64_t)postpone << 12 | (int64_t)thresh << 16 |
+           (int64_t)(uint16_t)(int16_t)inner << 24 | (int64_t)minw << 40;
+}
+struct TracePick {
+    TraceFn fn;
+    int64_t variant;
+};
+template <bool LDS_SCENE, bool PRUNE, bool STATS, bool LIST = false>
+TracePick v1k() {
+    return {trace_kernel<LDS_SCENE, PRUNE, STATS, LIST>, trace_variant(1, LDS_SCENE, PRUNE, STATS, 0, false, LIST, false, 0, 0, 0)};
+}
+template <int RES, bool PRUNE, bool STATS, int THRESH, int INNER, int MINW, int SPEC, bool NEE = false, bool LIST = false>
+TracePick v2k() {
+    static_assert(INNER >= -32768 && INNER <= 32767 && THRESH >= 0 && THRESH < 256 && MINW >= 0 && MINW < 16, "trace_variant fields");
+    return {trace_kernel_v2<RES, PRUNE, STATS, THRESH, INNER, MINW, SPEC, NEE, LIST>,
+            trace_variant(2, RES, PRUNE, STATS, SPEC, NEE, LIST, false, THRESH, INNER, MINW)};
+}
+
+TracePick pick_kernel_v1(bool lds, bool prune, bool stats) {
     if (lds) {
-        if (prune) return stats ? trace_kernel<true, true, true> : trace_kernel<true, true, false>;
-        return stats ? trace_kernel<true, false, true> : trace_kernel<true, false, false>;
+        if (prune) return stats ? v1k<true, true, true>() : v1k<true, true, false>();
+        return stats ? v1k<true, false, true>() : v1k<true, false, false>();
     }
-    if (prune) return stats ? trace_kernel<false, true, true> : trace_kernel<false, true, false>;
-    return stats ? trace_kernel<false, false, true> : trace_kernel<false, false, false>;
+    if (prune) return stats ? v1k<false, true, true>() : v1k<false, true, false>();
+    return stats ? v1k<false, false, true>() : v1k<false, false, false>();
 }
 
 template <int RES, int THRESH, int INNER, int MINW, int SPEC>
-TraceFn pick_v2_rt(bool prune, bool stats) {
-    if (prune) return stats ? trace_kernel_v2<RES, true, true, THRESH, INNER, MINW, SPEC> : trace_kernel_v2<RES, true, false, THRESH, INNER, MINW, SPEC>;
-    return stats ? trace_kernel_v2<RES, false, true, THRESH, INNER, MINW, SPEC> : trace_kernel_v2<RES, false, false, THRESH, INNER, MINW, SPEC>;
+TracePick pick_v2_rt(bool prune, bool stats) {
+    if (prune) return stats ? v2k<RES, true, true, THRESH, INNER, MINW, SPEC>() : v2k<RES, true, false, THRESH, INNER, MINW, SPEC>();
+    return stats ? v2k<RES, false, true, THRESH, INNER, MINW, SPEC>() : v2k<RES, false, false, THRESH, INNER, MINW, SPEC>();
 }
 
 template <int RES, int THRESH, int INNER, int MINW>
-TraceFn pick_v2_r(bool prune, bool stats, int spec) {
+TracePick pick_v2_r(bool prune, bool stats, int spec) {
     if (spec == 2) return pick_v2_rt<RES, THRESH, INNER, MINW, 2>(prune, stats);
     if (spec == 1) return pick_v2_rt<RES, THRESH, INNER, MINW, 1>(prune, stats);
     return pick_v2_rt<RES, THRESH, INNER, MINW, 0>(prune, stats);
 }
 
 template <int THRESH, int INNER, int MINW>
-TraceFn pick_v2_ti(int res, bool prune, bool stats, int spec) {
+TracePick pick_v2_ti(int res, bool prune, bool stats, int spec) {
     if (res == 3) return pick_v2_r<3, THRESH, INNER, MINW>(prune, stats, spec);
     if (res == 2) return pick_v2_r<2, THRESH, INNER, MINW>(prune, stats, spec);
     if (res == 1) return pick_v2_r<1, THRESH, INNER, MINW>(prune, stats, spec);
@@ -861,23 +885,23 @@ TraceFn pick_v2_ti(int res, bool prune, bool stats, int spec) {
 // is 5-8 % slower.  Re-checked on the internal tree (fewer inner visits per leaf test): 6 + 2 still wins on LDS-resident scenes
 // (cbox: 5+2 +2.4 %, 4+2 +4.6 %, 3+2 +5.4 %, two rounds of 2+1 +13 %; thresholds 24 / 32 / 48 / 56: +1.7 / 0.0 / +1.2 / +7.5 %; profiles/r02_tune_round44_lds_bursts_rejected.log,
 // r02_tune_round46_thresh_rejected.log).
-TraceFn pick_kernel_v2(int res, bool prune, bool stats, int spec, int thresh, int inner, int minw) {
+TracePick pick_kernel_v2(int res, bool prune, bool stats, int spec, int thresh, int inner, int minw) {
 #define PT_V2(T, I, W) if (thresh == T && inner == I && minw == W) return pick_v2_ti<T, I, W>(res, prune, stats, spec);
     PT_V2(40, -6, 6) PT_V2(32, 4, 6) PT_V2(40, 4, 6) PT_V2(40, 3, 6) PT_V2(40, 162, 6)
     PT_V2(32, 1004, 6) PT_V2(32, 1231, 6)
     PT_V2(32, 1231, 5) PT_V2(40, 162, 5)        // 96 VGPRs, 5 waves per SIMD: for the instantiations that spill under the 80-VGPR cap
 #undef PT_V2
-    return nullptr;
+    return {nullptr, 0};
 }
 
 // Kernels with next-event estimation (PT_RENDER_NEE): exact traversal, the default schedule of the residency, generic
 // scene content or triangles-with-diffuse-materials only.
 template <int RES, int THRESH, int INNER>
-TraceFn pick_nee_r(bool stats, int spec) {
-    if (spec == 2) return stats ? trace_kernel_v2<RES, false, true, THRESH, INNER, 6, 2, true> : trace_kernel_v2<RES, false, false, THRESH, INNER, 6, 2, true>;
-    return stats ? trace_kernel_v2<RES, false, true, THRESH, INNER, 6, 0, true> : trace_kernel_v2<RES, false, false, THRESH, INNER, 6, 0, true>;
+TracePick pick_nee_r(bool stats, int spec) {
+    if (spec == 2) return stats ? v2k<RES, false, true, THRESH, INNER, 6, 2, true>() : v2k<RES, false, false, THRESH, INNER, 6, 2, true>();
+    return stats ? v2k<RES, false, true, THRESH, INNER, 6, 0, true>() : v2k<RES, false, false, THRESH, INNER, 6, 0, true>();
 }
-TraceFn pick_kernel_nee(int res, bool stats, int spec) {
+TracePick pick_kernel_nee(int res, bool stats, int spec) {
     if (res == 3) return pick_nee_r<3, 32, 4>(stats, spec);
     if (res == 2) return pick_nee_r<2, 40, 162>(stats, spec);
     if (res == 1) return pick_nee_r<1, 40, 162>(stats, spec);
@@ -886,14 +910,22 @@ TraceFn pick_kernel_nee(int res, bool stats, int spec) {
 
 // trace_kernel_q (option "kernel" = 3): LDS-resident scenes, exact traversal, no next-event estimation.
 using TraceFnQ = void (*)(SceneDev, RenderDev, LdsPlan, QParams, float4*, uint32_t*, unsigned long long*);
+struct TracePickQ {
+    TraceFnQ fn;
+    int64_t variant;
+};
+template <int RES, bool STATS, int SPEC, bool POSTPONE>
+TracePickQ qk() {
+    return {trace_kernel_q<RES, STATS, SPEC, POSTPONE>, trace_variant(3, RES, false, STATS, SPEC, false, false, POSTPONE, 0, 0, 0)};
+}
 template <int RES, bool POSTPONE>
-TraceFnQ pick_q_r(bool stats, int spec) {
-    if (spec == 2) return stats ? trace_kernel_q<RES, true, 2, POSTPONE> : trace_kernel_q<RES, false, 2, POSTPONE>;
-    if (spec == 1) return stats ? trace_kernel_q<RES, true, 1, POSTPONE> : trace_kernel_q<RES, false, 1, POSTPONE>;
-    return stats ? trace_kernel_q<RES, true, 0, POSTPONE> : trace_kernel_q<RES, false, 0, POSTPONE>;
+TracePickQ pick_q_r(bool stats, int spec) {
+    if (spec == 2) return stats ? qk<RES, true, 2, POSTPONE>() : qk<RES, false, 2, POSTPONE>();
+    if (spec == 1) return stats ? qk<RES, true, 1, POSTPONE>() : qk<RES, false, 1, POSTPONE>();
+    return stats ? qk<RES, true, 0, POSTPONE>() : qk<RES, false, 0, POSTPONE>();
 }
 // internal_tree: scenes in global memory set leaves aside (order-free leaf tests need the internal tree's tie handling)
-TraceFnQ pick_kernel_q(const pt_scene* S, int res, bool internal_tree) {
+TracePickQ pick_kernel_q(const pt_scene* S, int res, bool internal_tree) {
     const int spec = !(S->tri_only && S->opt_specialize) ? 0 : (S->diffuse_only ? 2 : 1);
     const bool stats = S->opt_stats != 0;
     if (res == 2) return pick_q_r<2, false>(stats, spec);
@@ -954,7 +986,7 @@ int scene_residency(const pt_scene* S, int which = 0) {
     return 1;
 }
 
-TraceFn pick_kernel(const pt_scene* S, int res, bool prune, bool stats, bool internal_tree) {
+TracePick pick_kernel(const pt_scene* S, int res, bool prune, bool stats, bool internal_tree) {
     if (S->opt_kernel >= 2) {
         int t = (int)S->opt_v2_thresh, i = (int)S->opt_v2_inner, w = (int)S->opt_v2_minw;
         const bool lds = res == 1 || res == 2;
@@ -968,7 +1000,7 @@ TraceFn pick_kernel(const pt_scene* S, int res, bool prune, bool stats, bool int
         // 3 + 1 and two of 2 + 1, and every set-aside shape on LDS-resident scenes: r02_tune_round50_more_bursts_rejected.log; 7 / 8 waves per
         // SIMD by register cap, with the blocks to match: +11..16 % / +28..41 % from the spills, r02_tune_round51_more_waves_rejected.log).
         if (i == 0) i = lds ? 162 : (internal_tree ? 1231 : 4);
-        if (i >= 1000 && !internal_tree) return nullptr;        // order-free leaf tests need the internal tree's tie handling
+        if (i >= 1000 && !internal_tree) return {nullptr, 0};   // order-free leaf tests need the internal tree's tie handling
         if (w == 0) w = 6;
         const int spec = !tri ? 0 : (S->diffuse_only ? 2 : 1);
         return pick_kernel_v2(res, prune, stats, spec, t, i, w);
@@ -978,43 +1010,49 @@ TraceFn pick_kernel(const pt_scene* S, int res, bool prune, bool stats, bool int
 
 // Adaptive rounds after the first (RenderDev::list): the LIST variants of the trace kernels, compiled for the automatic schedule
 // of every residency only — the v2_* knobs change no bit, so these rounds ignore them, and option "kernel" = 3 runs them on 2.
-template <int RES, int THRESH, int INNER, int SPEC>
-TraceFn pick_list_rs(bool prune, bool stats, bool nee) {
-    if (nee) return stats ? trace_kernel_v2<RES, false, true, THRESH, INNER, 6, SPEC, true, true>
-                          : trace_kernel_v2<RES, false, false, THRESH, INNER, 6, SPEC, true, true>;
-    if (prune) return stats ? trace_kernel_v2<RES, true, true, THRESH, INNER, 6, SPEC, false, true>
-                            : trace_kernel_v2<RES, true, false, THRESH, INNER, 6, SPEC, false, true>;
-    return stats ? trace_kernel_v2<RES, false, true, THRESH, INNER, 6, SPEC, false, true>
-                 : trace_kernel_v2<RES, false, false, THRESH, INNER, 6, SPEC, false, true>;
+// NEE is a template argument here so that only the schedules and scene specialisations pick_kernel_nee uses are compiled with it.
+template <int RES, int THRESH, int INNER, int SPEC, bool NEE>
+TracePick pick_list_rs(bool prune, bool stats) {
+    if constexpr (NEE) {
+        return stats ? v2k<RES, false, true, THRESH, INNER, 6, SPEC, true, true>()
+                     : v2k<RES, false, false, THRESH, INNER, 6, SPEC, true, true>();
+    } else {
+        if (prune) return stats ? v2k<RES, true, true, THRESH, INNER, 6, SPEC, false, true>()
+                                : v2k<RES, true, false, THRESH, INNER, 6, SPEC, false, true>();
+        return stats ? v2k<RES, false, true, THRESH, INNER, 6, SPEC, false, true>()
+                     : v2k<RES, false, false, THRESH, INNER, 6, SPEC, false, true>();
+    }
 }
-template <int RES, int THRESH, int INNER>
-TraceFn pick_list_r(bool prune, bool stats, bool nee, int spec) {
-    if (spec == 2) return pick_list_rs<RES, THRESH, INNER, 2>(prune, stats, nee);
-    if (spec == 1 && !nee) return pick_list_rs<RES, THRESH, INNER, 1>(prune, stats, nee);
-    return pick_list_rs<RES, THRESH, INNER, 0>(prune, stats, nee);
+template <int RES, int THRESH, int INNER, bool NEE>
+TracePick pick_list_r(bool prune, bool stats, int spec) {
+    if (spec == 2) return pick_list_rs<RES, THRESH, INNER, 2, NEE>(prune, stats);
+    if constexpr (!NEE) {
+        if (spec == 1) return pick_list_rs<RES, THRESH, INNER, 1, NEE>(prune, stats);
+    }
+    return pick_list_rs<RES, THRESH, INNER, 0, NEE>(prune, stats);
 }
-TraceFn pick_kernel_list(const pt_scene* S, int res, bool prune, bool stats, bool internal_tree, bool nee) {
+TracePick pick_kernel_list(const pt_scene* S, int res, bool prune, bool stats, bool internal_tree, bool nee) {
     if (S->opt_kernel == 1) {
         if (res == 1 || res == 2) {
-            if (prune) return stats ? trace_kernel<true, true, true, true> : trace_kernel<true, true, false, true>;
-            return stats ? trace_kernel<true, false, true, true> : trace_kernel<true, false, false, true>;
+            if (prune) return stats ? v1k<true, true, true, true>() : v1k<true, true, false, true>();
+            return stats ? v1k<true, false, true, true>() : v1k<true, false, false, true>();
         }
-        if (prune) return stats ? trace_kernel<false, true, true, true> : trace_kernel<false, true, false, true>;
-        return stats ? trace_kernel<false, false, true, true> : trace_kernel<false, false, false, true>;
+        if (prune) return stats ? v1k<false, true, true, true>() : v1k<false, true, false, true>();
+        return stats ? v1k<false, false, true, true>() : v1k<false, false, false, true>();
     }
     const bool tri = S->tri_only && S->opt_specialize;
     const int spec = !tri ? 0 : (S->diffuse_only ? 2 : 1);
     // the automatic schedules of pick_kernel / pick_kernel_nee
     if (nee) {
-        if (res == 3) return pick_list_r<3, 32, 4>(false, stats, true, spec);
-        if (res == 2) return pick_list_r<2, 40, 162>(false, stats, true, spec);
-        if (res == 1) return pick_list_r<1, 40, 162>(false, stats, true, spec);
-        return pick_list_r<0, 32, 4>(false, stats, true, spec);
+        if (res == 3) return pick_list_r<3, 32, 4, true>(false, stats, spec);
+        if (res == 2) return pick_list_r<2, 40, 162, true>(false, stats, spec);
+        if (res == 1) return pick_list_r<1, 40, 162, true>(false, stats, spec);
+        return pick_list_r<0, 32, 4, true>(false, stats, spec);
     }
-    if (res == 2) return pick_list_r<2, 40, 162>(prune, stats, false, spec);
-    if (res == 1) return pick_list_r<1, 40, 162>(prune, stats, false, spec);
-    if (res == 3) return internal_tree ? pick_list_r<3, 32, 1231>(prune, stats, false, spec) : pick_list_r<3, 32, 4>(prune, stats, false, spec);
-    return internal_tree ? pick_list_r<0, 32, 1231>(prune, stats, false, spec) : pick_list_r<0, 32, 4>(prune, stats, false, spec);
+    if (res == 2) return pick_list_r<2, 40, 162, false>(prune, stats, spec);
+    if (res == 1) return pick_list_r<1, 40, 162, false>(prune, stats, spec);
+    if (res == 3) return internal_tree ? pick_list_r<3, 32, 1231, false>(prune, stats, spec) : pick_list_r<3, 32, 4, false>(prune, stats, spec);
+    return internal_tree ? pick_list_r<0, 32, 1231, false>(prune, stats, spec) : pick_list_r<0, 32, 4, false>(prune, stats, spec);
 }
 
 // Sums the kCounterSlots per-workgroup counter slots of the last frame (the caller has synchronised the stream).
@@ -1109,6 +1147,7 @@ int launch_render(pt_scene* S, const pt_render_params* p, float* out_dev, int mo
     pt_scene::FrameRec& frec = S->frames[(S->frame_seq - 1) % S->frames.size()];
     const size_t pass_base = frec.passes;               // passes of earlier adaptive rounds of this frame
     if (rows.count == 0) {           // nothing to trace: the frame's counters read zero
+        S->info_trace_variant = 0;
         if (slot.used && slot.free_stream != stream) HIP_TRY(hipStreamWaitEvent(stream, slot.free_ev, 0));
         HIP_TRY(hipMemsetAsync(slot.ctl.p, 0, (kWorkWords + kTimelineBase) * sizeof(unsigned long long), stream));
         HIP_TRY(hipEventRecord(slot.free_ev, stream));
@@ -1166,14 +1205,17 @@ int launch_render(pt_scene* S, const pt_render_params* p, float* out_dev, int mo
     QParams qp{};
     TraceFnQ fnq = nullptr;
     TraceFn fn = nullptr;
+    int64_t variant = 0;
     if (use_q) {
         qp = make_plan_q(S, lp, which, res);
         if (lp.total > S->lds_per_block_max) return fail(PT_ERR_DEVICE, "LDS plan exceeds the per-block limit");
-        fnq = pick_kernel_q(S, res, which == 1);
+        const TracePickQ pq = pick_kernel_q(S, res, which == 1);
+        fnq = pq.fn; variant = pq.variant;
     } else {
-        fn = listed ? pick_kernel_list(S, res, traversal == PT_TRAVERSAL_PRUNED, S->opt_stats != 0, which == 1, nee)
-           : nee ? pick_kernel_nee(res, S->opt_stats != 0, (S->tri_only && S->diffuse_only && S->opt_specialize) ? 2 : 0)
-                 : pick_kernel(S, res, traversal == PT_TRAVERSAL_PRUNED, S->opt_stats != 0, which == 1);
+        const TracePick pk = listed ? pick_kernel_list(S, res, traversal == PT_TRAVERSAL_PRUNED, S->opt_stats != 0, which == 1, nee)
+                           : nee ? pick_kernel_nee(res, S->opt_stats != 0, (S->tri_only && S->diffuse_only && S->opt_specialize) ? 2 : 0)
+                                 : pick_kernel(S, res, traversal == PT_TRAVERSAL_PRUNED, S->opt_stats != 0, which == 1);
+        fn = pk.fn; variant = pk.variant;
         if (!fn) return fail(PT_ERR_INVALID_ARG, "no kernel variant compiled for these v2_thresh / v2_inner options");
     }
     const void* fn_any = use_q ? reinterpret_cast<const void*>(fnq) : reinterpret_cast<const void*>(fn);
@@ -1200,6 +1242,7 @@ int launch_render(pt_scene* S, const pt_render_params* p, float* out_dev, int mo
     const bool own_stream = !ad && in_flight > 1 && n_pass == 1 && prev_busy;
     if (own_stream && S->opt_blocks_per_cu <= 0) bpc = std::max(1, in_flight >= 3 ? bpc / 2 : bpc - 1);
     S->info_kernel = use_q ? 3 : S->opt_kernel == 1 ? 1 : 2;
+    S->info_trace_variant = variant;
     S->info_occupancy = occ;
     S->info_blocks_per_cu = bpc;
     S->info_lds_bytes = lp.total;
@@ -1648,6 +1691,7 @@ int pt_scene_get_info(pt_scene* S, const char* key, int64_t* value) {
     else if (k == "sweep_on_device") *value = S->sweep_on_device;         // the internal tree was built on the GPU (pt_sweep_build.hip)
     else if (k.rfind("create_us", 0) == 0 && k.size() == 10 && k[9] >= '0' && k[9] <= '6') *value = S->create_us[k[9] - '0'];
     else if (k == "kernel") *value = S->info_kernel;                      // the kernel the last render ran on (1, 2 or 3)
+    else if (k == "trace_variant") *value = S->info_trace_variant;        // ... and its template arguments (include/pt_api.h)
     else if (k == "block_threads") *value = S->info_kernel == 3 ? kQBlock : kBlock;
     else if (k == "frames_in_flight") *value = S->opt_frames_in_flight;
     else if (k.rfind("qdiag", 0) == 0 && k.size() >= 6 && k.size() <= 7 && k.find_first_not_of("0123456789", 5) == std::string::npos &&
@@ -1684,9 +1728,9 @@ int pt_scene_get_info(pt_scene* S, const char* key, int64_t* value) {
         const int res = scene_residency(S, w);
         const void* f;
         if (S->opt_kernel == 3 && k == "vgprs") {
-            f = reinterpret_cast<const void*>(pick_kernel_q(S, res, w == 1));
+            f = reinterpret_cast<const void*>(pick_kernel_q(S, res, w == 1).fn);
         } else {
-            TraceFn fn = pick_kernel(S, res, k == "vgprs_pruned", S->opt_stats != 0, w == 1);
+            TraceFn fn = pick_kernel(S, res, k == "vgprs_pruned", S->opt_stats != 0, w == 1).fn;
             if (!fn) return fail(PT_ERR_INVALID_ARG, "no such kernel variant");
             f = reinterpret_cast<const void*>(fn);
         }

@@ -228,6 +228,64 @@ typedef struct pt_adaptive_params {
 int pt_render_adaptive(pt_scene* scene, const pt_render_params* p, const pt_adaptive_params* a,
                        float* fb, int32_t* spp_map, float* err_map, int on_device);
 
+/* Guide buffers of the first hit ("AOVs") — an EXTENSION, like PT_RENDER_NEE: the reference's only per-pixel output is radiance.
+ * Never part of a parity or roofline number; no other entry point's output changes by a bit.
+ *   One ray per selected pixel through the pixel CENTRE, u = ((float)i + 0.5f) / (float)width, v = ((float)j + 0.5f) / (float)height,
+ *   the camera ray of camera.cuh:45-50 and the closest-hit query a camera segment of pt_render runs (tnear 0, tfar +inf).
+ *   p->traversal, "fast_tree" and every other option mean what they mean in pt_render (under PT_TRAVERSAL_EXACT none of them
+ *   changes an output bit); row selection and the [rows, W] packing are pt_render's.  spp, seed, sample_offset, stream_stride,
+ *   depths and flags are ignored.  Blocking, on the default stream.  Any output pointer may be NULL; on_device != 0: all of them
+ *   are device pointers on the scene's GPU.
+ *   prim    [rows, W]     shape id of the closest hit, -1 on a miss
+ *   depth   [rows, W]     the hit's t, 0 on a miss
+ *   normal  [rows, W, 3]  the shading normal (interpolated vertex normals / sphere normal, normalised), turned to the side the
+ *                         ray came from (negated when dot(-dir, n) < 0) as the renderer turns it; (0,0,0) on a miss
+ *   albedo  [rows, W, 3]  the hit material's reflectance; (1,1,1) for PT_MAT_MIRROR; (0,0,0) on a miss and where pt_render's first
+ *                         segment adds emission at this hit (light id in range, that light a diffuse area light, seen from the
+ *                         front).  "All three channels 0" is what pt_denoise reads as "leave this pixel alone". */
+int pt_render_aov(pt_scene* scene, const pt_render_params* p,
+                  float* albedo, float* normal, float* depth, int32_t* prim, int on_device);
+
+/* Edge-avoiding à-trous filter guided by those buffers — an EXTENSION: an image-space stage after pt_render /
+ * pt_render_accumulate / pt_render_adaptive, off unless called.  DESIGN.md §17. */
+typedef struct pt_denoise_params {
+    int32_t width, height;        /* full frame; the filter works on whole frames only                     */
+    int32_t iterations;           /* 0 -> 5; else 1..8; iteration k uses tap spacing 2^k                   */
+    int32_t normal_power_log2;    /* 0..10, used as given: normal weight = max(0, n_p.n_q)^(2^this); tools use 7 */
+    float   sigma_z;              /* 0 -> 0.05; else > 0, finite: relative depth difference at half weight  */
+    float   sigma_c;              /* 0 = no colour term; else > 0, finite: luminance difference at half weight in
+                                     iteration 0, halved per iteration */
+    float   scale;                /* 0 -> 1; else > 0, finite: input colour is multiplied by it first (1/n for a pt_render_accumulate sum) */
+    float   albedo_floor;         /* 0 -> 0.01; else > 0, finite                                            */
+} pt_denoise_params;              /* 32 bytes */
+
+/* color, albedo, normal [H, W, 3], depth [H, W] -> out [H, W, 3]; out may be color.  The handle supplies the device and owns the
+ * scratch records (48 bytes per pixel, allocated on first use, freed with the scene).  on_device != 0: device pointers, enqueued
+ * on hip_stream (NULL = default stream) without a host sync, so that it can follow pt_render_async / pt_render_accumulate on
+ * the caller's stream; on_device == 0: host pointers, blocking.  A parameter out of range -> PT_ERR_INVALID_ARG, pt_last_error()
+ * names the field.
+ *   The rule, in fp32, operations in the order written, no contraction.  lum(c) = 0.2126f c.r + 0.7152f c.g + 0.0722f c.b and dot
+ *   left to right; h = {1/16, 1/4, 3/8, 1/4, 1/16}.
+ *   A pixel is filterable iff max(albedo.r, albedo.g, albedo.b) > 0.  a' = max(albedo, albedo_floor) per channel.
+ *   x_0 = color * scale / a' (IEEE division) for filterable pixels, color * scale otherwise.
+ *   Iteration k = 0 .. iterations - 1, spacing s = 1 << k, reads x_k, writes x_{k+1}.  A pixel that is not filterable is copied.
+ *   For a filterable pixel p: sum = (0,0,0), wsum = 0; taps q = p + s (dx, dy) in the order dy = -2..2 (outer), dx = -2..2 (inner);
+ *   a tap outside the frame or not filterable is skipped; otherwise
+ *     wn = max(0, dot(n_p, n_q)), squared normal_power_log2 times;
+ *     rd = (z_p - z_q) * (1.0f / max(z_p, 1e-20f));  wz = 1.0f / (1.0f + (rd * rd) * kz),  kz = 1.0f / (sigma_z * sigma_z);
+ *     w = ((h[dy + 2] * h[dx + 2]) * wn) * wz;
+ *     with a colour term: dl = lum(x_k[p]) - lum(x_k[q]);  w = w * (1.0f / (1.0f + (dl * dl) * kc)),  kc = 1.0f / (sc * sc),
+ *     sc = sigma_c * 2^-k;
+ *     sum += x_k[q] * w per channel, wsum += w.
+ *   x_{k+1}[p] = sum * (1.0f / wsum).  out = x_last * a' for filterable pixels, x_last otherwise.
+ *   Weights are rational instead of exp so that every operation is a correctly rounded IEEE one: the device, pt_denoise_host and
+ *   a numpy fp32 restatement give the same bits.  Non-finite input propagates; what it does is unspecified. */
+int pt_denoise(pt_scene* scene, const pt_denoise_params* d, const float* color, const float* albedo,
+               const float* normal, const float* depth, float* out, int on_device, void* hip_stream);
+/* The same per-pixel source (csrc/pt_denoise.h) compiled for the HOST: needs no GPU and no scene. */
+int pt_denoise_host(const pt_denoise_params* d, const float* color, const float* albedo,
+                    const float* normal, const float* depth, float* out);
+
 int pt_get_counters(pt_scene* scene, pt_counters* out);   /* synchronises the scene's last stream */
 
 /* HIP-event times of the last render calls on the scene, oldest first: kernel_ms[k] / resolve_ms[k] of up to max_frames calls,

@@ -21,6 +21,7 @@
 #include "pt_tree_sweep.h"
 #include "pt_sweep_build.h"
 #include "pt_scene_prep.h"
+#include "pt_denoise.h"
 #include "pt_kernels.h"
 #include "pt_kernel_q.h"
 
@@ -181,6 +182,10 @@ struct pt_scene {
     DevBuf<int32_t> ad_spp_tmp;
     DevBuf<float> ad_err_tmp;
     int64_t info_adaptive_rounds = 0;
+    // pt_denoise: the guide record and the two ping-pong colour records per pixel (pt_denoise.h), and staging of a frame that
+    // comes in host memory (colour, albedo, normal, depth: 10 floats per pixel; the result goes back through its first 3)
+    DevBuf<float4> dn_guide, dn_x[2];
+    DevBuf<float> dn_host;
     // What a frame's trace kernel writes lives in a frame slot; render call k uses slot k % frames_in_flight.  With more than one
     // slot a single-pass frame runs on the slot's own stream: the trace kernel at once (it reads the immutable scene and writes
     // the slot only), the resolve — the one step that touches the caller's buffer — once the caller's stream has reached the
@@ -1453,6 +1458,7 @@ int pt_scene_destroy(pt_scene* S) {
     S->lights.release(); S->accum.release(); S->fb_tmp.release();
     S->ad_sum.release(); S->ad_mom.release(); S->ad_list[0].release(); S->ad_list[1].release(); S->ad_count.release();
     S->ad_spp_tmp.release(); S->ad_err_tmp.release();
+    S->dn_guide.release(); S->dn_x[0].release(); S->dn_x[1].release(); S->dn_host.release();
     S->drop_events();
     delete S;
     return PT_OK;
@@ -1579,6 +1585,103 @@ int pt_render_adaptive(pt_scene* S, const pt_render_params* p, const pt_adaptive
         if (err_map) HIP_TRY(hipMemcpy(err_map, err_d, npix * sizeof(float), hipMemcpyDeviceToHost));
     } else {
         HIP_TRY(hipStreamSynchronize(nullptr));
+    }
+    return PT_OK;
+}
+
+int pt_render_aov(pt_scene* S, const pt_render_params* p, float* albedo, float* normal, float* depth, int32_t* prim, int on_device) {
+    if (!S || !p) return fail(PT_ERR_INVALID_ARG, "null argument");
+    if (p->width <= 0 || p->height <= 0) return fail(PT_ERR_INVALID_ARG, "width and height must be positive");
+    const int traversal = p->traversal == PT_TRAVERSAL_DEFAULT ? PT_TRAVERSAL_EXACT : p->traversal;
+    if (traversal != PT_TRAVERSAL_EXACT && traversal != PT_TRAVERSAL_PRUNED) return fail(PT_ERR_INVALID_ARG, "unknown traversal mode");
+    RowSel rows;
+    int rc = select_rows(p, &rows);
+    if (rc) return rc;
+    const uint64_t npix = (uint64_t)rows.count * (uint64_t)p->width;
+    if (npix > (1ull << 30)) return fail(PT_ERR_INVALID_ARG, "more than 2^30 pixels per call");
+    if (npix == 0 || (!albedo && !normal && !depth && !prim)) return PT_OK;
+    DeviceGuard guard;
+    { int grc = guard.enter(S->device); if (grc) return grc; }
+    // host outputs are staged in buffers of this call
+    DevBuf<float> d_albedo, d_normal, d_depth;
+    DevBuf<int32_t> d_prim;
+    float *o_albedo = albedo, *o_normal = normal, *o_depth = depth;
+    int32_t* o_prim = prim;
+    if (!on_device) {
+        if ((albedo && (rc = d_albedo.ensure(npix * 3))) || (normal && (rc = d_normal.ensure(npix * 3))) ||
+            (depth && (rc = d_depth.ensure(npix))) || (prim && (rc = d_prim.ensure(npix))))
+            return rc;
+        o_albedo = albedo ? d_albedo.p : nullptr; o_normal = normal ? d_normal.p : nullptr;
+        o_depth = depth ? d_depth.p : nullptr; o_prim = prim ? d_prim.p : nullptr;
+    }
+    // the tree a render traverses (pt_debug_intersect's choice): the internal one with ties settled in the caller's visit order
+    // and reference-order reruns where scene creation kept one and "fast_tree" is on, else the caller's
+    const bool fast = S->have_fast && S->opt_fast_tree;
+    select_tree(S, fast ? 1 : 0, fast);
+    const int cap = fast && S->dev.redo_cap > S->dev.stack_cap ? S->dev.redo_cap : S->dev.stack_cap;
+    const uint32_t lds = (uint32_t)(kBlock / 64) * (uint32_t)cap * 64u * 4u;
+    RenderDev rd{};
+    std::memcpy(rd.cam_origin, p->cam_origin, sizeof rd.cam_origin);
+    std::memcpy(rd.cam_top_left, p->cam_top_left, sizeof rd.cam_top_left);
+    std::memcpy(rd.cam_horizontal, p->cam_horizontal, sizeof rd.cam_horizontal);
+    std::memcpy(rd.cam_vertical, p->cam_vertical, sizeof rd.cam_vertical);
+    rd.width = p->width; rd.height = p->height;
+    rd.row_begin = rows.begin; rd.row_step = rows.step; rd.num_rows = rows.count;
+    rd.npix = (uint32_t)npix;
+    rd.div_width = make_fastdiv((uint32_t)p->width);
+    const dim3 grid((unsigned)((npix + kBlock - 1) / kBlock));
+    if (traversal == PT_TRAVERSAL_PRUNED)
+        hipLaunchKernelGGL(aov_kernel<true>, grid, dim3(kBlock), lds, nullptr, S->dev, rd, o_albedo, o_normal, o_depth, o_prim);
+    else
+        hipLaunchKernelGGL(aov_kernel<false>, grid, dim3(kBlock), lds, nullptr, S->dev, rd, o_albedo, o_normal, o_depth, o_prim);
+    HIP_TRY(hipGetLastError());
+    if (on_device) {
+        HIP_TRY(hipStreamSynchronize(nullptr));
+        return PT_OK;
+    }
+    if (albedo) HIP_TRY(hipMemcpy(albedo, d_albedo.p, npix * 3 * sizeof(float), hipMemcpyDeviceToHost));
+    if (normal) HIP_TRY(hipMemcpy(normal, d_normal.p, npix * 3 * sizeof(float), hipMemcpyDeviceToHost));
+    if (depth) HIP_TRY(hipMemcpy(depth, d_depth.p, npix * sizeof(float), hipMemcpyDeviceToHost));
+    if (prim) HIP_TRY(hipMemcpy(prim, d_prim.p, npix * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return PT_OK;
+}
+
+int pt_denoise(pt_scene* S, const pt_denoise_params* d, const float* color, const float* albedo, const float* normal,
+               const float* depth, float* out, int on_device, void* hip_stream) {
+    if (!S || !d || !color || !albedo || !normal || !depth || !out) return fail(PT_ERR_INVALID_ARG, "null argument");
+    ptdn::Resolved r;
+    if (const char* bad = ptdn::resolve(d, &r)) return fail(PT_ERR_INVALID_ARG, std::string("pt_denoise_params.") + bad + " out of range");
+    DeviceGuard guard;
+    { int grc = guard.enter(S->device); if (grc) return grc; }
+    const size_t npix = (size_t)r.width * (size_t)r.height;
+    int rc;
+    if ((rc = S->dn_guide.ensure(npix)) || (rc = S->dn_x[0].ensure(npix)) || (rc = S->dn_x[1].ensure(npix))) return rc;
+    if (on_device) {
+        const hipError_t e = (hipError_t)ptdn::run_device(r, color, albedo, normal, depth, out, S->dn_guide.p, S->dn_x[0].p, S->dn_x[1].p, hip_stream);
+        if (e != hipSuccess) return fail(PT_ERR_DEVICE, std::string("pt_denoise: ") + hipGetErrorString(e));
+        return PT_OK;
+    }
+    if ((rc = S->dn_host.ensure(npix * 10))) return rc;
+    float* h = S->dn_host.p;
+    HIP_TRY(hipMemcpy(h, color, npix * 3 * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(h + npix * 3, albedo, npix * 3 * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(h + npix * 6, normal, npix * 3 * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(h + npix * 9, depth, npix * sizeof(float), hipMemcpyHostToDevice));
+    const hipError_t e = (hipError_t)ptdn::run_device(r, h, h + npix * 3, h + npix * 6, h + npix * 9, h, S->dn_guide.p, S->dn_x[0].p, S->dn_x[1].p, nullptr);
+    if (e != hipSuccess) return fail(PT_ERR_DEVICE, std::string("pt_denoise: ") + hipGetErrorString(e));
+    HIP_TRY(hipMemcpy(out, h, npix * 3 * sizeof(float), hipMemcpyDeviceToHost));
+    return PT_OK;
+}
+
+int pt_denoise_host(const pt_denoise_params* d, const float* color, const float* albedo, const float* normal, const float* depth,
+                    float* out) {
+    if (!d || !color || !albedo || !normal || !depth || !out) return fail(PT_ERR_INVALID_ARG, "null argument");
+    ptdn::Resolved r;
+    if (const char* bad = ptdn::resolve(d, &r)) return fail(PT_ERR_INVALID_ARG, std::string("pt_denoise_params.") + bad + " out of range");
+    try {
+        ptdn::run_host(r, color, albedo, normal, depth, out);
+    } catch (const std::exception& e) {
+        return fail(PT_ERR_DEVICE, std::string("pt_denoise_host: ") + e.what());
     }
     return PT_OK;
 }

@@ -738,6 +738,71 @@ __global__ __launch_bounds__(kBlock) void intersect_kernel(SceneDev scn, const f
     out_tuv[3 * k + 2] = h.prim < 0 ? 0.0f : h.v;
 }
 
+// pt_render_aov: guide buffers of the first hit, one lane per selected pixel.  The ray goes through the pixel CENTRE and is
+// traced like a camera segment of a render (primary_ray, tnear 0, tfar +inf) with intersect_kernel's traversal: the internal
+// tree with ties settled in the caller's visit order where there is one, else the caller's; stack columns in LDS.
+// rp carries the camera, width / height and the row selection only.  Any output may be null.
+//   prim    shape id, -1 on a miss                 depth   t, 0 on a miss
+//   normal  make_surface's shading normal turned towards the camera as shade_and_bounce turns it; 0 on a miss
+//   albedo  the material's reflectance, (1,1,1) for a mirror; 0 on a miss and where a render adds emission at this hit
+template <bool PRUNE>
+__global__ __launch_bounds__(kBlock) void aov_kernel(SceneDev scn, RenderDev rp, float* __restrict__ albedo,
+                                                     float* __restrict__ normal, float* __restrict__ depth,
+                                                     int32_t* __restrict__ prim) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    ptd::SceneView sv;
+    sv.nodes = scn.nodes; sv.prims = scn.prims; sv.normals = scn.normals;
+    sv.materials = scn.materials; sv.emission = scn.emission; sv.lights = scn.lights;
+    sv.top_nodes = nullptr; sv.top_count = 0;
+    sv.node_stride = sizeof(DNode);
+    sv.num_emission = scn.num_emission; sv.root_ref = scn.root_ref; sv.fixed_order = scn.fixed_order;
+    sv.ref_nodes = scn.ref_nodes; sv.ref_path = scn.ref_path; sv.ref_anc = scn.ref_anc; sv.ref_levels = scn.ref_levels;
+    sv.bg = ptm::mk(0, 0, 0);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int cap = scn.fallback && scn.redo_cap > scn.stack_cap ? scn.redo_cap : scn.stack_cap;   // one column serves both trees
+    int32_t* stk = reinterpret_cast<int32_t*>(smem) + (size_t)wave * cap * 64 + lane;
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= rp.npix) return;
+    const uint32_t row = fastdiv(k, rp.div_width);
+    const int i = (int)(k - row * (uint32_t)rp.width);
+    const int j = rp.row_begin + (int)row * rp.row_step;
+    const float u = ((float)i + 0.5f) / (float)rp.width;
+    const float v = ((float)j + 0.5f) / (float)rp.height;
+    const ptd::Ray r = ptd::primary_ray(rp, u, v);
+    ptd::TravStats st;
+    ptd::Hit h;
+    if (scn.fallback) {
+        ptd::SceneView sv_ref = sv;
+        sv_ref.nodes = scn.ref_nodes; sv_ref.root_ref = scn.ref_root_ref; sv_ref.fixed_order = 0;
+        bool rerun;
+        h = ptd::intersect_any_tree<PRUNE>(sv, sv_ref, r, stk, rerun);
+    } else {
+        h = ptd::intersect<PRUNE, false>(sv, r, stk, st);
+    }
+    ptm::V3 n = ptm::mk(0.0f, 0.0f, 0.0f), a = n;
+    float t = 0.0f;
+    if (h.prim >= 0) {
+        const ptd::Surface sf = ptd::make_surface<false>(sv, r, h);
+        t = h.t;
+        n = sf.n;
+        const float wi_n = ptm::dot(-r.dir, n);
+        bool emits = false;                              // shade_and_bounce's emission test (radiance.cuh:35-43)
+        if (sf.light >= 0 && sf.light < sv.num_emission) {
+            const float4 e = ptd::ld4(sv.emission + sf.light, 0);
+            emits = __builtin_bit_cast(int32_t, e.w) != 0 && wi_n > 0.0f;
+        }
+        if (wi_n < 0.0f) n = -n;
+        if (!emits) {
+            const float4 m0 = ptd::ld4(sv.materials + sf.material, 0);
+            a = __builtin_bit_cast(int32_t, m0.x) == 1 ? ptm::mk(1.0f, 1.0f, 1.0f) : ptm::mk(m0.y, m0.z, m0.w);
+        }
+    }
+    if (prim) prim[k] = h.prim < 0 ? -1 : h.prim;
+    if (depth) depth[k] = t;
+    if (normal) { normal[3 * (size_t)k] = n.x; normal[3 * (size_t)k + 1] = n.y; normal[3 * (size_t)k + 2] = n.z; }
+    if (albedo) { albedo[3 * (size_t)k] = a.x; albedo[3 * (size_t)k + 1] = a.y; albedo[3 * (size_t)k + 2] = a.z; }
+}
+
 // Inner-node visits of a fixed set of probe rays through the tree `scn` points at (pt_api.hip: validate_and_build chooses
 // between the caller's tree and the internal one by this count).  Ray k starts on primitive hash(k) mod N — its centroid,
 // or the point of a sphere facing the direction — and leaves into a uniform direction: the shape of a segment after a bounce.

@@ -88,6 +88,12 @@ class PtAdaptiveParams(C.Structure):
                 ("min_luminance", C.c_float)]
 
 
+class PtDenoiseParams(C.Structure):
+    """pt_denoise_params (pt_api.h): edge-avoiding a-trous filter guided by albedo, normal and depth (pt_denoise)."""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("iterations", C.c_int32), ("normal_power_log2", C.c_int32),
+                ("sigma_z", C.c_float), ("sigma_c", C.c_float), ("scale", C.c_float), ("albedo_floor", C.c_float)]
+
+
 class PtCamera(C.Structure):
     _fields_ = [("lookfrom", c_float3), ("lookat", c_float3), ("up", c_float3), ("vfov", C.c_float),
                 ("width", C.c_int32), ("height", C.c_int32), ("spp", C.c_int32)]

@@ -9,8 +9,8 @@ import os
 import numpy as np
 
 from . import _build
-from .ctypes_defs import (PT_OK, PT_TRAVERSAL_DEFAULT, PtAdaptiveParams, PtBvhNode, PtCounters, PtError, PtRenderParams,
-                          PtSceneDesc)
+from .ctypes_defs import (PT_OK, PT_TRAVERSAL_DEFAULT, PtAdaptiveParams, PtBvhNode, PtCounters, PtDenoiseParams, PtError,
+                          PtRenderParams, PtSceneDesc)
 
 _lib = None
 
@@ -18,7 +18,7 @@ EXPORTS = [
     "pt_api_version", "pt_last_error", "pt_scene_create", "pt_scene_destroy", "pt_render", "pt_render_async",
     "pt_render_accumulate", "pt_get_counters", "pt_scene_set_option", "pt_scene_get_info", "pt_debug_math",
     "pt_debug_intersect", "pt_debug_math_host", "pt_bvh_build_device", "pt_bvh_build_sweep", "pt_get_frame_times", "pt_bvh_build_sweep_device",
-    "pt_debug_exact_math", "pt_render_adaptive",
+    "pt_debug_exact_math", "pt_render_adaptive", "pt_render_aov", "pt_denoise", "pt_denoise_host",
 ]
 
 
@@ -40,6 +40,9 @@ def lib():
         L.pt_render_async.argtypes = [vp, C.POINTER(PtRenderParams), vp, vp]
         L.pt_render_accumulate.argtypes = [vp, C.POINTER(PtRenderParams), vp, vp]
         L.pt_render_adaptive.argtypes = [vp, C.POINTER(PtRenderParams), C.POINTER(PtAdaptiveParams), vp, vp, vp, C.c_int]
+        L.pt_render_aov.argtypes = [vp, C.POINTER(PtRenderParams), vp, vp, vp, vp, C.c_int]
+        L.pt_denoise.argtypes = [vp, C.POINTER(PtDenoiseParams), vp, vp, vp, vp, vp, C.c_int, vp]
+        L.pt_denoise_host.argtypes = [C.POINTER(PtDenoiseParams), vp, vp, vp, vp, vp]
         L.pt_get_counters.argtypes = [vp, C.POINTER(PtCounters)]
         L.pt_get_frame_times.argtypes = [vp, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int)]
         L.pt_scene_set_option.argtypes = [vp, C.c_char_p, C.c_int64]
@@ -136,6 +139,50 @@ class DeviceScene:
         _check(lib().pt_render_adaptive(self._h, C.byref(p), C.byref(a), C.c_void_p(fb_ptr), C.c_void_p(spp_ptr or 0),
                                         C.c_void_p(err_ptr or 0), 1))
 
+    def render_aov(self, params, traversal=None, albedo=True, normal=True, depth=True, prim=True):
+        """Guide buffers of the first hit (pt_render_aov), one ray through every selected pixel's centre: a dict of host arrays
+        "albedo" / "normal" [rows, W, 3] float32, "depth" [rows, W] float32, "prim" [rows, W] int32 (those asked for)."""
+        p = params.copy()
+        if traversal is not None:
+            p.traversal = traversal
+        rows, W = p.num_rows(), p.width
+        out = {}
+        if albedo:
+            out["albedo"] = np.empty((rows, W, 3), dtype=np.float32)
+        if normal:
+            out["normal"] = np.empty((rows, W, 3), dtype=np.float32)
+        if depth:
+            out["depth"] = np.empty((rows, W), dtype=np.float32)
+        if prim:
+            out["prim"] = np.empty((rows, W), dtype=np.int32)
+        ptr = [out[k].ctypes.data_as(C.c_void_p) if k in out else None for k in ("albedo", "normal", "depth", "prim")]
+        _check(lib().pt_render_aov(self._h, C.byref(p), ptr[0], ptr[1], ptr[2], ptr[3], 0))
+        return out
+
+    def render_aov_into(self, params, albedo_ptr=0, normal_ptr=0, depth_ptr=0, prim_ptr=0, traversal=None):
+        """pt_render_aov into device memory (albedo / normal [rows, W, 3] float32, depth [rows, W] float32, prim [rows, W]
+        int32; a pointer of 0 skips that buffer).  Blocking: it runs on the default stream and returns when the buffers are written."""
+        p = params.copy()
+        if traversal is not None:
+            p.traversal = traversal
+        _check(lib().pt_render_aov(self._h, C.byref(p), C.c_void_p(albedo_ptr or 0), C.c_void_p(normal_ptr or 0),
+                                   C.c_void_p(depth_ptr or 0), C.c_void_p(prim_ptr or 0), 1))
+
+    def denoise(self, color, albedo, normal, depth, **kw):
+        """pt_denoise on host arrays (color, albedo, normal [H, W, 3], depth [H, W], float32): the filtered frame as a new
+        array.  Keywords: the fields of pt_denoise_params (denoise_params)."""
+        color, albedo, normal, depth, d = _denoise_args(color, albedo, normal, depth, kw)
+        out = np.empty_like(color)
+        _check(lib().pt_denoise(self._h, C.byref(d), *(a.ctypes.data_as(C.c_void_p) for a in (color, albedo, normal, depth, out)),
+                                0, None))
+        return out
+
+    def denoise_into(self, width, height, color_ptr, albedo_ptr, normal_ptr, depth_ptr, out_ptr, stream=None, **kw):
+        """pt_denoise on device memory, enqueued on a HIP stream without a host sync (out_ptr may be color_ptr)."""
+        d = denoise_params(width, height, **kw)
+        _check(lib().pt_denoise(self._h, C.byref(d), C.c_void_p(color_ptr), C.c_void_p(albedo_ptr), C.c_void_p(normal_ptr),
+                                C.c_void_p(depth_ptr), C.c_void_p(out_ptr), 1, C.c_void_p(stream or 0)))
+
     def accumulate_into(self, params, dev_ptr, stream=None):
         _check(lib().pt_render_accumulate(self._h, C.byref(params), C.c_void_p(dev_ptr), C.c_void_p(stream or 0)))
 
@@ -159,6 +206,33 @@ class DeviceScene:
         _check(lib().pt_debug_intersect(self._h, _fp(rays), rays.shape[0], traversal, _fp(tuv),
                                         prim.ctypes.data_as(C.POINTER(C.c_int32))))
         return tuv, prim
+
+
+def denoise_params(width, height, iterations=0, normal_power_log2=7, sigma_z=0.0, sigma_c=0.0, scale=0.0, albedo_floor=0.0):
+    """pt_denoise_params; 0 = the library's default (5 iterations, sigma_z 0.05, no colour term, scale 1, albedo_floor 0.01)."""
+    return PtDenoiseParams(int(width), int(height), int(iterations), int(normal_power_log2), float(sigma_z), float(sigma_c),
+                           float(scale), float(albedo_floor))
+
+
+def _denoise_args(color, albedo, normal, depth, kw):
+    color, albedo, normal = (np.ascontiguousarray(a, dtype=np.float32) for a in (color, albedo, normal))
+    depth = np.ascontiguousarray(depth, dtype=np.float32)
+    H, W = depth.shape
+    if not (color.shape == albedo.shape == normal.shape == (H, W, 3)):
+        raise ValueError("denoise: color, albedo, normal must be [H, W, 3] and depth [H, W]")
+    return color, albedo, normal, depth, denoise_params(W, H, **kw)
+
+
+def denoise_host(color, albedo, normal, depth, out=None, **kw):
+    """pt_denoise_host: the filter of pt_denoise run by the host half of the library (no GPU needed).  out: an [H, W, 3]
+    float32 array to write (it may be `color` itself); default a new one."""
+    color, albedo, normal, depth, d = _denoise_args(color, albedo, normal, depth, kw)
+    if out is None:
+        out = np.empty_like(color)
+    if out.dtype != np.float32 or out.shape != color.shape or not out.flags.c_contiguous:
+        raise ValueError("denoise_host: out must be a contiguous [H, W, 3] float32 array")
+    _check(lib().pt_denoise_host(C.byref(d), *(a.ctypes.data_as(C.c_void_p) for a in (color, albedo, normal, depth, out))))
+    return out
 
 
 def debug_math(op, x, y=None, host=False):

@@ -3,6 +3,7 @@
    python tools/render.py <scene.xml|scene.pts|buddha_standin|dragon_standin> [-o out.pfm|out.ppm] [--width W --height H --spp S]
                           [--traversal exact|pruned] [--seed 1984] [--bvh reference|lbvh|sah] [--nee]
                           [--adaptive MAX_ERROR [--batch-spp B] [--max-spp M] [--p-value P] [--min-luminance L] [--spp-map map.pfm]]
+                          [--denoise [--denoise-iterations N --sigma-z Z --sigma-c C]] [--aov PREFIX]
 Needs a GPU (no CPU fallback).  Multi-GPU: launch with torchrun; rows are interleaved over ranks, rank 0 writes."""
 import argparse
 import os
@@ -33,6 +34,12 @@ def main():
     ap.add_argument("--p-value", type=float, default=0.05, help="adaptive: two-sided p-value of the interval")
     ap.add_argument("--min-luminance", type=float, default=0.01, help="adaptive: floor of the relative test's denominator")
     ap.add_argument("--spp-map", metavar="PATH", help="adaptive: write the per-pixel sample counts (PFM, the count in all channels)")
+    ap.add_argument("--denoise", action="store_true",
+                    help="filter the finished frame (an extension): edge-avoiding a-trous filter guided by first-hit albedo, normal and depth")
+    ap.add_argument("--denoise-iterations", type=int, default=0, help="denoise: filter iterations, 1..8 (0 = 5)")
+    ap.add_argument("--sigma-z", type=float, default=0.0, help="denoise: relative depth difference at half weight (0 = 0.05)")
+    ap.add_argument("--sigma-c", type=float, default=0.0, help="denoise: luminance difference at half weight (0 = no colour term)")
+    ap.add_argument("--aov", metavar="PREFIX", help="write the first-hit guide buffers: PREFIX_albedo.pfm, _normal.pfm, _depth.pfm")
     a = ap.parse_args()
     import numpy as np
     import torch
@@ -58,6 +65,33 @@ def main():
     p.traversal = PT_TRAVERSAL_PRUNED if a.traversal == "pruned" else PT_TRAVERSAL_EXACT
     p.flags = PT_RENDER_NEE if a.nee else 0
     R = D.ShardedRenderer(desc)
+
+    def finish(frame):
+        """Rank 0, after the frame is assembled: guide buffers of the whole frame on this rank's GPU (one ray per pixel),
+        the filter, the files.  Without --denoise / --aov the frame is returned as it is."""
+        if not (a.denoise or a.aov):
+            return frame, ""
+        torch.cuda.synchronize()
+        t_d = time.perf_counter()
+        g = {k: torch.empty((p.height, p.width) + ((3,) if k != "depth" else ()), dtype=torch.float32, device=frame.device)
+             for k in ("albedo", "normal", "depth")}
+        R.scene.render_aov_into(p, g["albedo"].data_ptr(), g["normal"].data_ptr(), g["depth"].data_ptr(), 0)
+        note = ""
+        if a.denoise:
+            frame = frame.contiguous()
+            out = torch.empty_like(frame)
+            R.scene.denoise_into(p.width, p.height, frame.data_ptr(), g["albedo"].data_ptr(), g["normal"].data_ptr(),
+                                 g["depth"].data_ptr(), out.data_ptr(), torch.cuda.current_stream().cuda_stream,
+                                 iterations=a.denoise_iterations, sigma_z=a.sigma_z, sigma_c=a.sigma_c)
+            torch.cuda.synchronize()
+            frame = out
+            note = f"; guide buffers + denoise {(time.perf_counter() - t_d) * 1e3:.2f} ms"
+        if a.aov:
+            write_image(a.aov + "_albedo.pfm", g["albedo"].cpu().numpy())
+            write_image(a.aov + "_normal.pfm", g["normal"].cpu().numpy())
+            write_image(a.aov + "_depth.pfm", np.repeat(g["depth"].cpu().numpy()[..., None], 3, axis=2))
+            note += f"; guide buffers -> {a.aov}_albedo.pfm, _normal.pfm, _depth.pfm"
+        return frame, note
     if a.adaptive is not None:
         t_r = time.perf_counter()
         out = R.render_adaptive(p, a.adaptive, a.batch_spp, a.max_spp, a.p_value, a.min_luminance, rank, world)
@@ -66,6 +100,7 @@ def main():
         t2 = time.perf_counter()
         if rank == 0:
             frame, spp_map, _ = out
+            frame, note = finish(frame)
             spp_map = spp_map.cpu().numpy()
             write_image(a.output, frame.cpu().numpy())
             if a.spp_map:
@@ -73,7 +108,7 @@ def main():
             print(f"{a.scene}: adaptive {p.width}x{p.height}, max_error {a.adaptive}, first round {p.spp} spp: "
                   f"mean {spp_map.mean():.2f} spp (min {spp_map.min()}, max {spp_map.max()}), "
                   f"{R.scene.info('adaptive_rounds')} rounds and kernel {c.kernel_ms:.2f} ms on rank 0, {t2 - t_r:.3f} s -> {a.output}"
-                  + (f", {a.spp_map}" if a.spp_map else ""))
+                  + (f", {a.spp_map}" if a.spp_map else "") + note)
         R.close()
         if world > 1:
             dist.destroy_process_group()
@@ -83,10 +118,11 @@ def main():
     torch.cuda.synchronize()
     t2 = time.perf_counter()
     if rank == 0:
+        frame, note = finish(frame)
         write_image(a.output, frame.cpu().numpy())
         print(f"{a.scene}: {desc.num_shapes} primitives, {a.bvh} BVH of depth {depth}; parse+build {t1 - t0:.2f} s; "
               f"{p.width}x{p.height} spp={p.spp}: kernel {c.kernel_ms:.2f} ms on rank 0 ({c.segments / c.kernel_ms / 1e3:.0f} Msamples/s), "
-              f"upload+render+gather {t2 - t1:.3f} s -> {a.output}")
+              f"upload+render+gather {t2 - t1:.3f} s -> {a.output}" + note)
     R.close()
     if world > 1:
         dist.destroy_process_group()

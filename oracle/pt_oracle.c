@@ -233,6 +233,14 @@ int pt_oracle_intersect(const pt_scene_desc* sc, const float* rays, int n, int m
     return intersect_rays_det(sc, rays, n, out_tuv, out_prim);
 }
 
+int pt_oracle_intersect_full(const pt_scene_desc* sc, const float* rays, int n, int math_mode,
+                             float* out_hit, int32_t* out_ids) {
+    if (!sc || !rays || !out_hit || !out_ids || n < 0) return PT_ERR_INVALID_ARG;
+    if (sc->num_nodes <= 0 || sc->root < 0 || sc->root >= sc->num_nodes) return PT_ERR_BAD_SCENE;
+    if (math_mode == PT_ORACLE_MATH_LIBM) return intersect_rays_full_libm(sc, rays, n, out_hit, out_ids);
+    return intersect_rays_full_det(sc, rays, n, out_hit, out_ids);
+}
+
 int pt_oracle_intersect_work(const pt_scene_desc* sc, const float* rays, int n, int math_mode, uint32_t* out_inner,
                              uint32_t* out_leaf, uint64_t* out_leaf_set) {
     if (!sc || !rays || !out_inner || !out_leaf || !out_leaf_set || n < 0) return PT_ERR_INVALID_ARG;

@@ -11,14 +11,14 @@
  * cutil_math.h:295-425, pcg.h:16-57), on the reference's own data layout, fed
  * through the same pt_scene_desc / pt_render_params the C ABI takes.
  *
- * Pinning status (see DESIGN.md "Oracle"): the reference cannot be built in this
- * image (every first-party header pulls <cuda_runtime.h>/<curand_kernel.h>, and
- * stand-in headers are not allowed), and it ships no tests or golden vectors.
- * The oracle is pinned against the values SURVEY.md §8c recorded from a host
- * build of the reference's headers (PCG known-answer vectors; scene1 / cbox
- * image statistics and pixel bit patterns under per-pixel-sequential PCG +
- * glibc math): tests/test_oracle_pins.py.  Parity with the literal CUDA/cuRAND
- * binary is unpinned (XORWOW stream not reproducible).
+ * Pinning status (see DESIGN.md "Oracle"): the reference itself is compiled as host C++ by oracle/ref_build/ (stand-in CUDA
+ * headers and a driver of our own around its unmodified sources, built into oracle/_ref/ by __graft_entry__.build() where the
+ * reference is present), and what that build computes is recorded under tests/golden/ref/.  tests/test_reference_recordings.py
+ * holds both flavours of this oracle to those recordings bit for bit: frames (glibc math x per-pixel / per-sample streams,
+ * deterministic math x per-sample streams), intersect() on explicit rays, and the scene the host pipeline hands in.  Older,
+ * weaker pins remain: the reference's screenshots (statistical), SURVEY.md §8c's hand-recorded values, the published PCG vector
+ * (tests/test_reference_images.py, tests/test_oracle_pins.py).  Parity with the literal CUDA/cuRAND binary is unpinned (XORWOW
+ * stream not reproducible).
  */
 #ifndef PT_ORACLE_H
 #define PT_ORACLE_H
@@ -75,13 +75,20 @@ int pt_oracle_trace_pixels(const pt_scene_desc* scene, const pt_render_params* p
 int pt_oracle_intersect(const pt_scene_desc* scene, const float* rays, int n, int math_mode,
                         float* out_tuv, int32_t* out_prim);
 
+/* The same query, returning the whole Intersection record (intersection.h) for comparison with the reference's own
+ * intersect(): out_hit n x {distance, position[3], shading normal[3], geometric normal[3]}, out_ids n x {prim, material id,
+ * area light id}; all 0 / -1 on a miss. */
+int pt_oracle_intersect_full(const pt_scene_desc* scene, const float* rays, int n, int math_mode,
+                             float* out_hit, int32_t* out_ids);
+
 /* Work of intersect() per ray, primitive tests left out: inner pops, leaves reached, and an order-independent hash of the
  * ids of the primitives whose leaves were reached (the reference never prunes, so this set does not depend on hits). */
 int pt_oracle_intersect_work(const pt_scene_desc* scene, const float* rays, int n, int math_mode, uint32_t* out_inner,
                              uint32_t* out_leaf, uint64_t* out_leaf_set);
 
 /* TEST HOOK: mutations of the estimator (bit mask; 0 = none = the reference's algorithm).  Used only to demonstrate that the
- * statistical pin on the reference's screenshots fails for a wrong estimator (tests/test_reference_images.py).  Process-wide,
+ * pins fail for a wrong estimator: the statistical one on the reference's screenshots (tests/test_reference_images.py) and the
+ * bit-exact one on the reference's recorded frames (tests/test_reference_recordings.py, which must reject the control too).  Process-wide,
  * not thread-safe against a running render.  Returns the previous mask.
  *   DIFFUSE_NO_INV_PI  eval_brdf's diffuse value without the 1/pi (scene.h:370-375), pdf unchanged
  *   RR_NO_WEIGHT       Russian-roulette survivors keep their throughput (radiance.cuh:68-74 without the division)

@@ -604,6 +604,32 @@ static int FN(intersect_rays)(const pt_scene_desc* sc, const float* rays, int n,
     return 0;
 }
 
+/* The whole Intersection record of the closest hit (intersection.h), not just t: out_hit = {distance, position[3], shading
+ * normal[3], geometric normal[3]}, out_ids = {prim, material, area light}; a miss is all 0 / -1. */
+static int FN(intersect_rays_full)(const pt_scene_desc* sc, const float* rays, int n, float* out_hit, int32_t* out_ids) {
+    o_counters cnt;
+    memset(&cnt, 0, sizeof cnt);
+    for (int k = 0; k < n; k++) {
+        o_ray r;
+        r.org = v3ld(&rays[8 * k]); r.dir = v3ld(&rays[8 * k + 3]);
+        r.tnear = rays[8 * k + 6]; r.tfar = rays[8 * k + 7];
+        o_isect h; int prim = -1;
+        float* o = &out_hit[10 * k];
+        int32_t* id = &out_ids[3 * k];
+        if (FN(intersect)(sc, &r, &h, &prim, &cnt)) {
+            o[0] = h.distance;
+            o[1] = h.position.x; o[2] = h.position.y; o[3] = h.position.z;
+            o[4] = h.shading_normal.x; o[5] = h.shading_normal.y; o[6] = h.shading_normal.z;
+            o[7] = h.geometric_normal.x; o[8] = h.geometric_normal.y; o[9] = h.geometric_normal.z;
+            id[0] = prim; id[1] = h.material_id; id[2] = h.area_light_id;
+        } else {
+            for (int c = 0; c < 10; c++) o[c] = 0;
+            id[0] = -1; id[1] = -1; id[2] = -1;
+        }
+    }
+    return 0;
+}
+
 /* Work of one intersect() call without the primitive tests: which leaves the traversal of scene.h:246-301 reaches (it never
  * prunes, so that does not depend on what the primitives return), as a count and as an order-independent hash of the
  * primitive ids; and the inner pops.  For the tests of "any tree over the same leaf boxes tests the same leaves". */

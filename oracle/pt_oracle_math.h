@@ -17,8 +17,8 @@
  *                  max()/fmaxf resolve to, and what v_max_f32 does).
  *
  * The deterministic functions are an independent restatement of the ones in
- * pathtracer_cuda_interactive_amd/csrc/pt_math.h; tests/test_math_parity.py checks
- * the two agree bit-for-bit.  Build with -ffp-contract=off.
+ * pathtracer_cuda_interactive_amd/csrc/pt_math.h; tests/test_math_cpu.py (host half) and
+ * tests/test_gpu_math.py (device) check the two agree bit-for-bit.  Build with -ffp-contract=off.
  */
 #ifndef PT_ORACLE_MATH_H
 #define PT_ORACLE_MATH_H

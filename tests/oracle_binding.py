@@ -69,6 +69,7 @@ def lib():
         L.pt_oracle_render_pixels.argtypes = [C.POINTER(PtSceneDesc), C.POINTER(PtRenderParams), C.POINTER(OracleOpts),
                                               ip, C.c_int, fp, C.POINTER(OracleCounters)]
         L.pt_oracle_intersect.argtypes = [C.POINTER(PtSceneDesc), fp, C.c_int, C.c_int, fp, ip]
+        L.pt_oracle_intersect_full.argtypes = [C.POINTER(PtSceneDesc), fp, C.c_int, C.c_int, fp, ip]
         L.pt_oracle_trace_pixels.argtypes = [C.POINTER(PtSceneDesc), C.POINTER(PtRenderParams), ip, C.c_int, C.c_char_p,
                                              C.c_uint64, C.POINTER(C.c_uint64)]
         L.pt_oracle_math.argtypes = [C.c_int, C.c_int, fp, fp, fp, fp, C.c_int]
@@ -113,6 +114,16 @@ def intersect(desc, rays, math_mode=MATH_DET):
     _chk(lib().pt_oracle_intersect(C.byref(desc), _fp(rays), rays.shape[0], math_mode, _fp(tuv),
                                    prim.ctypes.data_as(C.POINTER(C.c_int32))), "oracle intersect")
     return tuv, prim
+
+
+def intersect_full(desc, rays, math_mode=MATH_DET):
+    """Per ray: hit [n, 10] = distance, position, shading normal, geometric normal; ids [n, 3] = prim, material, area light."""
+    rays = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 8)
+    hit = np.zeros((rays.shape[0], 10), dtype=np.float32)
+    ids = np.zeros((rays.shape[0], 3), dtype=np.int32)
+    _chk(lib().pt_oracle_intersect_full(C.byref(desc), _fp(rays), rays.shape[0], math_mode, _fp(hit),
+                                        ids.ctypes.data_as(C.POINTER(C.c_int32))), "oracle intersect_full")
+    return hit, ids
 
 
 def intersect_work(desc, rays, math_mode=MATH_DET):

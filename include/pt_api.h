@@ -177,6 +177,39 @@ typedef struct pt_scene pt_scene;    /* opaque: owns all device memory of one sc
 int pt_scene_create(const pt_scene_desc* desc, pt_scene** out);
 int pt_scene_destroy(pt_scene* scene);
 
+/* New geometry and / or new shading values on a live handle — an EXTENSION, like PT_RENDER_NEE: the reference builds everything
+ * anew for every scene it loads.  The handle keeps its scratch memory, frame slots, options and timing rings; both of its trees
+ * keep the TOPOLOGY pt_scene_create gave them and get exact new boxes on the device (csrc/pt_scene_refit.hip): a leaf's box is
+ * the host pipeline's shape box (sphere: centre -/+ radius; triangle: per axis min(min(p0, p1), p2) / max, `a < b ? a : b`),
+ * an inner node's box the union of its two children's.  That is the tree pt_host_refit_bvh writes, and an updated handle
+ * renders, bit for bit and through every entry point, what a fresh pt_scene_create of the new desc with those nodes renders
+ * (no other entry point's output changes by a bit on a handle that was never updated).
+ *   Blocking: waits for every frame of this handle that is still in flight (a device synchronise, as in pt_scene_create), works
+ *   on the default stream and synchronises again before it returns.
+ *   desc->nodes, num_nodes and root are ignored.  num_shapes must be pt_scene_create's; with PT_UPDATE_SHADING num_materials and
+ *   num_lights too (PT_ERR_INVALID_ARG otherwise, pt_last_error() names the field).
+ *   PT_UPDATE_GEOMETRY  shapes and meshes are read again in full (positions, normals, indices, material and light ids, sphere
+ *                       data; the number of meshes may differ), ids checked with pt_scene_create's messages (PT_ERR_BAD_SCENE).
+ *                       A vertex coordinate, sphere centre or radius that a shape uses and that is not finite, or a new leaf
+ *                       box that is not finite (an overflowing centre + radius): PT_ERR_UNSUPPORTED.  This is stricter than
+ *                       pt_scene_create, which takes the caller's boxes as they are.
+ *                       PT_ERR_UNSUPPORTED also on the first geometry update of a handle one of whose trees is deeper than
+ *                       256 levels (the caller's tree: at most 64 by the traversal stack; the library's own: logarithmic in
+ *                       num_shapes), before anything is changed: such a handle cannot be updated at all.
+ *   PT_UPDATE_SHADING   materials, lights and background are read again with pt_scene_create's checks.
+ *   A call that fails leaves the handle exactly as it was: new records and leaf boxes are made and checked in staging memory
+ *   (kept with the handle: 96 bytes per shape, 24 more for scenes beyond a few thousand shapes) before anything is replaced.
+ *   Decided at pt_scene_create and not revisited: whether an internal tree exists and which topology it has, the stack caps, the
+ *   order of the top-of-tree prefix kept in LDS (it stays parent-before-child; only its "largest boxes first" choice ages) and
+ *   "fast_tree_cost_permille".  Boxes stay exact however far the geometry moves, their quality does not: a caller whose geometry
+ *   has drifted far from what the trees were built for should create a new handle.
+ *   pt_scene_get_info: "updates" = successful updates so far; "update_us0".."update_us3" = wall microseconds of the last one:
+ *   total, records including uploads, refit of both trees with their octant tables (host time up to its last enqueue: what the
+ *   level launches of a large tree still have to execute ends inside the closing synchronise and is in the total alone), the
+ *   one-time plan build (0 after the first).  That first update costs more than a pt_scene_create. */
+enum { PT_UPDATE_GEOMETRY = 1, PT_UPDATE_SHADING = 2 };
+int pt_scene_update(pt_scene* scene, const pt_scene_desc* desc, int flags);
+
 /* Blocking render.  `fb` receives rows x width x 3 floats, rows = the rows
  * selected by (row_begin,row_end,row_stride), packed in increasing row order;
  * fb[(r*W+i)*3+c], linear radiance, row 0 = top (main.cu:35,50).

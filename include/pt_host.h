@@ -66,6 +66,18 @@ int pt_host_scene_finalize(pt_host_scene* s, int bvh_sort_mode);
 int pt_host_scene_get_desc(const pt_host_scene* s, pt_scene_desc* out);
 int pt_host_scene_bvh_depth(const pt_host_scene* s);       /* computeMaxDepth, bvh.cu:56-65 */
 
+/* The node pool of desc with its TOPOLOGY kept (left, right, prim of every node as they are) and every box made anew from
+ * desc's shapes and meshes: a leaf's box is its shape's box as pt_host_scene_finalize computes it (sphere: centre -/+ radius;
+ * triangle: per axis min(min(p0, p1), p2) / max, `a < b ? a : b`), an inner node's box the union of its two children's, left
+ * child's value first.  On an unedited finalized scene that is the pool itself, byte for byte.  out_nodes receives
+ * desc->num_nodes nodes (it may be desc->nodes).  It is the tree pt_scene_update (pt_api.h) refits a handle to: what a caller
+ * uses to keep their own pool in step with a live handle.  PT_ERR_BAD_SCENE for ids or child indices out of range. */
+int pt_host_refit_bvh(const pt_scene_desc* desc, pt_bvh_node* out_nodes);
+/* The vertex normals pt_host_scene_add_mesh(normals = NULL) computes (compute_normals.cpp:13-51), for a caller whose mesh
+ * deforms: out_normals [num_vertices*3]. */
+int pt_host_compute_normals(const float* positions, int num_vertices, const int32_t* indices, int num_faces,
+                            float* out_normals);
+
 /* compute_camera_ray_data: out = origin, top_left_corner, horizontal, vertical */
 void pt_host_camera_ray_data(const pt_camera* cam, int width, int height, float out12[12]);
 /* Convenience: fill cam_* / width / height / spp / seed=1984 of *p from the camera (other fields zeroed). */

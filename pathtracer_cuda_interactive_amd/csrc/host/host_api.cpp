@@ -164,6 +164,61 @@ int pt_host_scene_get_desc(const pt_host_scene* s, pt_scene_desc* out) {
     return PT_OK;
 }
 
+int pt_host_refit_bvh(const pt_scene_desc* d, pt_bvh_node* out) {
+    if (!d || !out || !d->nodes || !d->shapes || d->num_shapes <= 0 || d->num_nodes <= 0 || d->root < 0 || d->root >= d->num_nodes) {
+        g_err = "bad argument";
+        return PT_ERR_INVALID_ARG;
+    }
+    return guard([&] {
+        const int n = d->num_nodes;
+        if (out != d->nodes) std::memmove(out, d->nodes, sizeof(pt_bvh_node) * size_t(n));
+        // children before parents: nodes in the order a depth-first walk from the root meets them, taken backwards
+        std::vector<int32_t> walk, open{d->root};
+        walk.reserve(size_t(n));
+        while (!open.empty()) {
+            const int32_t k = open.back();
+            open.pop_back();
+            if (walk.size() >= size_t(n)) throw Error(PT_ERR_BAD_SCENE, "BVH is not a tree (cycle)");
+            walk.push_back(k);
+            const pt_bvh_node& nd = out[k];
+            if (nd.prim != -1) continue;
+            if (nd.left < 0 || nd.left >= n || nd.right < 0 || nd.right >= n) throw Error(PT_ERR_BAD_SCENE, "BVH child index out of range");
+            open.push_back(nd.left);
+            open.push_back(nd.right);
+        }
+        for (size_t w = walk.size(); w-- > 0;) {
+            pt_bvh_node& nd = out[walk[w]];
+            if (nd.prim != -1) {
+                if (nd.prim < 0 || nd.prim >= d->num_shapes) throw Error(PT_ERR_BAD_SCENE, "leaf primitive id out of range");
+                f3 lo, hi;
+                shape_box(*d, nd.prim, lo, hi);
+                std::memcpy(nd.bmin, &lo, 12);
+                std::memcpy(nd.bmax, &hi, 12);
+            } else {
+                const pt_bvh_node &l = out[nd.left], &r = out[nd.right];
+                for (int c = 0; c < 3; c++) { nd.bmin[c] = tmin(l.bmin[c], r.bmin[c]); nd.bmax[c] = tmax(l.bmax[c], r.bmax[c]); }
+            }
+        }
+        return PT_OK;
+    });
+}
+
+int pt_host_compute_normals(const float* positions, int num_vertices, const int32_t* indices, int num_faces, float* out_normals) {
+    if (!positions || !indices || !out_normals || num_vertices <= 0 || num_faces <= 0) { g_err = "bad mesh arguments"; return PT_ERR_INVALID_ARG; }
+    return guard([&] {
+        std::vector<f3> P((size_t)num_vertices);
+        std::vector<i3> I((size_t)num_faces);
+        std::memcpy(P.data(), positions, sizeof(f3) * P.size());
+        std::memcpy(I.data(), indices, sizeof(i3) * I.size());
+        for (const i3& f : I)
+            for (int v : {f.x, f.y, f.z})
+                if (v < 0 || v >= num_vertices) throw Error(PT_ERR_BAD_SCENE, "face index out of range");
+        const std::vector<f3> nrm = compute_normals(P, I);
+        std::memcpy(out_normals, nrm.data(), sizeof(f3) * nrm.size());
+        return PT_OK;
+    });
+}
+
 int pt_host_scene_bvh_depth(const pt_host_scene* s) { return (s && s->s.finalized) ? s->s.depth : -1; }
 
 // camera.cuh:28-43

@@ -58,6 +58,9 @@ struct HostScene {
 };
 
 std::vector<f3> compute_normals(const std::vector<f3>& vertices, const std::vector<i3>& indices);
+// the box of a flattened shape as HostScene::finalize computes it (scene_build.cpp); the second form checks the ids it follows
+void shape_box(const pt_shape& s, const float* positions, const int32_t* indices, f3& lo, f3& hi);
+void shape_box(const pt_scene_desc& d, int i, f3& lo, f3& hi);
 
 // mesh_io.cpp
 void load_obj(const std::string& path, const Mat4& to_world, ParsedShape& out);

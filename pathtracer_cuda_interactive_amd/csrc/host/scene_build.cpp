@@ -43,6 +43,38 @@ std::vector<f3> compute_normals(const std::vector<f3>& vertices, const std::vect
     return sum;
 }
 
+// The box of one flattened shape; P, I: the positions and indices of a triangle's mesh (unused for a sphere).
+void shape_box(const pt_shape& s, const float* P, const int32_t* I, f3& lo, f3& hi) {
+    if (s.type == PT_SHAPE_SPHERE) {
+        f3 c{s.center[0], s.center[1], s.center[2]};
+        lo = f3{c.x - s.radius, c.y - s.radius, c.z - s.radius};
+        hi = f3{c.x + s.radius, c.y + s.radius, c.z + s.radius};
+    } else {
+        I += 3 * size_t(s.face_index);
+        f3 p0{P[3 * I[0]], P[3 * I[0] + 1], P[3 * I[0] + 2]};
+        f3 p1{P[3 * I[1]], P[3 * I[1] + 1], P[3 * I[1] + 2]};
+        f3 p2{P[3 * I[2]], P[3 * I[2] + 1], P[3 * I[2] + 2]};
+        // float3_min/max: scene.h:466-472 (fminf/fmaxf per component)
+        lo = f3{tmin(tmin(p0.x, p1.x), p2.x), tmin(tmin(p0.y, p1.y), p2.y), tmin(tmin(p0.z, p1.z), p2.z)};
+        hi = f3{tmax(tmax(p0.x, p1.x), p2.x), tmax(tmax(p0.y, p1.y), p2.y), tmax(tmax(p0.z, p1.z), p2.z)};
+    }
+}
+
+// ... of shape i of a flattened scene, ids checked
+void shape_box(const pt_scene_desc& d, int i, f3& lo, f3& hi) {
+    const pt_shape& s = d.shapes[i];
+    if (s.type == PT_SHAPE_SPHERE) return shape_box(s, nullptr, nullptr, lo, hi);
+    if (s.type != PT_SHAPE_TRIANGLE) throw Error(PT_ERR_BAD_SCENE, "unknown shape type");
+    if (s.mesh_index < 0 || s.mesh_index >= d.num_meshes || !d.meshes) throw Error(PT_ERR_BAD_SCENE, "triangle mesh index out of range");
+    const pt_mesh& me = d.meshes[s.mesh_index];
+    if (s.face_index < 0 || s.face_index >= me.num_faces || !me.positions || !me.indices) throw Error(PT_ERR_BAD_SCENE, "triangle face index out of range");
+    for (int k = 0; k < 3; k++) {
+        const int32_t v = me.indices[3 * size_t(s.face_index) + k];
+        if (v < 0 || v >= me.num_vertices) throw Error(PT_ERR_BAD_SCENE, "vertex index out of range");
+    }
+    shape_box(s, me.positions, me.indices, lo, hi);
+}
+
 namespace {
 
 struct BoxId {
@@ -217,21 +249,9 @@ void HostScene::finalize(int sort_mode) {
     std::vector<BoxId> boxes(flat_shapes.size());
     for (int i = 0; i < int(boxes.size()); i++) {
         const pt_shape& s = flat_shapes[i];
-        if (s.type == PT_SHAPE_SPHERE) {
-            f3 c{s.center[0], s.center[1], s.center[2]};
-            boxes[i] = {f3{c.x - s.radius, c.y - s.radius, c.z - s.radius},
-                        f3{c.x + s.radius, c.y + s.radius, c.z + s.radius}, i};
-        } else {
-            const float* P = mesh_positions[s.mesh_index].data();
-            const int32_t* I = &mesh_indices[s.mesh_index][3 * size_t(s.face_index)];
-            f3 p0{P[3 * I[0]], P[3 * I[0] + 1], P[3 * I[0] + 2]};
-            f3 p1{P[3 * I[1]], P[3 * I[1] + 1], P[3 * I[1] + 2]};
-            f3 p2{P[3 * I[2]], P[3 * I[2] + 1], P[3 * I[2] + 2]};
-            // float3_min/max: scene.h:466-472 (fminf/fmaxf per component)
-            f3 lo{tmin(tmin(p0.x, p1.x), p2.x), tmin(tmin(p0.y, p1.y), p2.y), tmin(tmin(p0.z, p1.z), p2.z)};
-            f3 hi{tmax(tmax(p0.x, p1.x), p2.x), tmax(tmax(p0.y, p1.y), p2.y), tmax(tmax(p0.z, p1.z), p2.z)};
-            boxes[i] = {lo, hi, i};
-        }
+        const bool tri = s.type != PT_SHAPE_SPHERE;
+        boxes[i].id = i;
+        shape_box(s, tri ? mesh_positions[s.mesh_index].data() : nullptr, tri ? mesh_indices[s.mesh_index].data() : nullptr, boxes[i].lo, boxes[i].hi);
     }
     nodes.assign(2 * boxes.size() - 1, pt_bvh_node{});
     BvhBuilder b{boxes, nodes, sort_mode};

@@ -21,6 +21,7 @@
 #include "pt_tree_sweep.h"
 #include "pt_sweep_build.h"
 #include "pt_scene_prep.h"
+#include "pt_scene_refit.h"
 #include "pt_denoise.h"
 #include "pt_kernels.h"
 #include "pt_kernel_q.h"
@@ -168,6 +169,14 @@ struct pt_scene {
     DevBuf<DLight> lights;
     SceneDev dev{};
     uint32_t scene_bytes = 0;
+    // pt_scene_update: new primitive records and leaf boxes are made and checked in staging memory before the handle changes
+    // (the record buffers then trade places with prims / normals); one refit plan per tree, made on the first geometry update
+    DevBuf<DPrim> st_prims;
+    DevBuf<DNormals> st_normals;
+    DevBuf<float> st_boxes;
+    DevBuf<unsigned int> st_status;
+    ptf::Plan refit_plan[2];
+    int64_t updates = 0, update_us[4] = {0, 0, 0, 0};   // [0] total [1] records + uploads [2] refit + octant tables [3] plan build
     bool tri_only = false;           // the scene holds no sphere
     bool diffuse_only = false;       // every material is DIFFUSE
     // scratch
@@ -437,6 +446,53 @@ int convert_tree(const pt_bvh_node* in, int num_nodes, int root, int N, TreeHost
     return PT_OK;
 }
 
+// ---- checks and conversions pt_scene_create and pt_scene_update share -------------------------------------------------------
+int check_materials(const pt_scene_desc* d) {
+    for (int m = 0; m < d->num_materials; m++)
+        if (d->materials[m].type < PT_MAT_DIFFUSE || d->materials[m].type > PT_MAT_PHONG)
+            return fail(PT_ERR_BAD_SCENE, "unknown material type (scene.h:410 asserts)");
+    return PT_OK;
+}
+int check_meshes(const pt_scene_desc* d, int num_materials) {
+    for (int m = 0; m < d->num_meshes; m++) {
+        const pt_mesh& me = d->meshes[m];
+        if (me.num_vertices <= 0 || me.num_faces <= 0 || !me.positions || !me.indices)
+            return fail(PT_ERR_BAD_SCENE, "empty mesh");
+        if (!me.normals) return fail(PT_ERR_BAD_SCENE, "mesh without vertex normals (required, SURVEY H5a)");
+        if (me.material_id < 0 || me.material_id >= num_materials) return fail(PT_ERR_BAD_SCENE, "mesh material id out of range");
+    }
+    return PT_OK;
+}
+bool all_diffuse(const pt_scene_desc* d) {
+    for (int m = 0; m < d->num_materials; m++)
+        if (d->materials[m].type != PT_MAT_DIFFUSE) return false;
+    return true;
+}
+// materials and lights as the kernels read them; N = number of shapes (an area light names its emitting shape)
+int pack_shading(const pt_scene_desc* d, int N, std::vector<DMaterial>& mats, std::vector<DEmission>& emis, std::vector<DLight>& dlights) {
+    mats.resize(d->num_materials);
+    for (int m = 0; m < d->num_materials; m++) {
+        const pt_material& src = d->materials[m];
+        mats[m] = DMaterial{src.type, src.reflectance[0], src.reflectance[1], src.reflectance[2], src.eta, src.exponent, 0.0f, 0.0f};
+    }
+    emis.resize(std::max(d->num_lights, 1));
+    std::memset(emis.data(), 0, sizeof(DEmission) * emis.size());
+    for (int l = 0; l < d->num_lights; l++) {
+        const pt_light& src = d->lights[l];
+        emis[l] = DEmission{src.radiance[0], src.radiance[1], src.radiance[2], src.type == PT_LIGHT_DIFFUSE_AREA ? 1 : 0};
+    }
+    dlights.resize(std::max(d->num_lights, 1));
+    std::memset(dlights.data(), 0, sizeof(DLight) * dlights.size());
+    for (int l = 0; l < d->num_lights; l++) {
+        const pt_light& src = d->lights[l];
+        dlights[l] = DLight{src.radiance[0], src.radiance[1], src.radiance[2], src.type == PT_LIGHT_DIFFUSE_AREA ? 1 : 0,
+                            src.position[0], src.position[1], src.position[2], src.shape_id};
+        if (src.type == PT_LIGHT_DIFFUSE_AREA && (src.shape_id < 0 || src.shape_id >= N))
+            return fail(PT_ERR_BAD_SCENE, "area light refers to a shape that does not exist");
+    }
+    return PT_OK;
+}
+
 int validate_and_build(const pt_scene_desc* d, pt_scene* S) {
     if (!d) return fail(PT_ERR_INVALID_ARG, "null scene description");
     if (d->num_shapes <= 0 || !d->shapes) return fail(PT_ERR_BAD_SCENE, "scene has no shapes");
@@ -446,16 +502,8 @@ int validate_and_build(const pt_scene_desc* d, pt_scene* S) {
     if (d->num_materials <= 0 || !d->materials) return fail(PT_ERR_BAD_SCENE, "scene has no materials");
     if (d->num_meshes < 0 || (d->num_meshes > 0 && !d->meshes)) return fail(PT_ERR_BAD_SCENE, "bad mesh array");
     if (d->num_lights < 0 || (d->num_lights > 0 && !d->lights)) return fail(PT_ERR_BAD_SCENE, "bad light array");
-    for (int m = 0; m < d->num_materials; m++)
-        if (d->materials[m].type < PT_MAT_DIFFUSE || d->materials[m].type > PT_MAT_PHONG)
-            return fail(PT_ERR_BAD_SCENE, "unknown material type (scene.h:410 asserts)");
-    for (int m = 0; m < d->num_meshes; m++) {
-        const pt_mesh& me = d->meshes[m];
-        if (me.num_vertices <= 0 || me.num_faces <= 0 || !me.positions || !me.indices)
-            return fail(PT_ERR_BAD_SCENE, "empty mesh");
-        if (!me.normals) return fail(PT_ERR_BAD_SCENE, "mesh without vertex normals (required, SURVEY H5a)");
-        if (me.material_id < 0 || me.material_id >= d->num_materials) return fail(PT_ERR_BAD_SCENE, "mesh material id out of range");
-    }
+    int crc;
+    if ((crc = check_materials(d)) || (crc = check_meshes(d, d->num_materials))) return crc;
 
     // ---- primitives
     using clk = std::chrono::steady_clock;
@@ -504,9 +552,7 @@ int validate_and_build(const pt_scene_desc* d, pt_scene* S) {
     }
     }
 
-    S->diffuse_only = true;
-    for (int m = 0; m < d->num_materials; m++)
-        if (d->materials[m].type != PT_MAT_DIFFUSE) { S->diffuse_only = false; break; }
+    S->diffuse_only = all_diffuse(d);
 
     S->create_us[1] = us_since(t_stage); t_stage = clk::now();
     // ---- BVH: the caller's tree (validated), and the internal tree over the same leaf boxes
@@ -616,27 +662,11 @@ int validate_and_build(const pt_scene_desc* d, pt_scene* S) {
     S->create_us[4] = us_since(t_stage); t_stage = clk::now();
     // trees the device path made are in S->tree[] already; what the host made is uploaded below
     const TreeHost* hosts[2] = {trees_on_device ? nullptr : &ref, (have_fast && !S->sweep_on_device) ? &fast : nullptr};
-    std::vector<DMaterial> mats(d->num_materials);
-    for (int m = 0; m < d->num_materials; m++) {
-        const pt_material& src = d->materials[m];
-        mats[m] = DMaterial{src.type, src.reflectance[0], src.reflectance[1], src.reflectance[2], src.eta, src.exponent, 0.0f, 0.0f};
-    }
-    std::vector<DEmission> emis(std::max(d->num_lights, 1));
-    std::memset(emis.data(), 0, sizeof(DEmission) * emis.size());
-    for (int l = 0; l < d->num_lights; l++) {
-        const pt_light& src = d->lights[l];
-        emis[l] = DEmission{src.radiance[0], src.radiance[1], src.radiance[2], src.type == PT_LIGHT_DIFFUSE_AREA ? 1 : 0};
-    }
-    std::vector<DLight> dlights(std::max(d->num_lights, 1));
-    std::memset(dlights.data(), 0, sizeof(DLight) * dlights.size());
-    for (int l = 0; l < d->num_lights; l++) {
-        const pt_light& src = d->lights[l];
-        dlights[l] = DLight{src.radiance[0], src.radiance[1], src.radiance[2], src.type == PT_LIGHT_DIFFUSE_AREA ? 1 : 0,
-                            src.position[0], src.position[1], src.position[2], src.shape_id};
-        if (src.type == PT_LIGHT_DIFFUSE_AREA && (src.shape_id < 0 || src.shape_id >= N))
-            return fail(PT_ERR_BAD_SCENE, "area light refers to a shape that does not exist");
-    }
+    std::vector<DMaterial> mats;
+    std::vector<DEmission> emis;
+    std::vector<DLight> dlights;
     int rc;
+    if ((rc = pack_shading(d, N, mats, emis, dlights))) return rc;
     auto upload_tree = [&](int t, const TreeHost& H) -> int {
         const std::vector<DNode>& nodes = H.nodes;
         pt_scene::Tree& T = S->tree[t];
@@ -1420,6 +1450,97 @@ int frame_times(const pt_scene::FrameRec& f, double* kernel_ms, double* resolve_
     return PT_OK;
 }
 
+
+// pt_scene_update (include/pt_api.h).  Order of events: everything that can be refused is made and checked first — argument
+// counts and the desc on the host, primitive records and leaf boxes in staging memory on the device — and only then does the
+// handle change: node arrays written, record buffers traded, shading tables overwritten.
+int update_scene(pt_scene* S, const pt_scene_desc* d, int flags) {
+    using clk = std::chrono::steady_clock;
+    auto us_since = [](clk::time_point t0) { return (int64_t)std::chrono::duration_cast<std::chrono::microseconds>(clk::now() - t0).count(); };
+    const bool geometry = (flags & PT_UPDATE_GEOMETRY) != 0, shading = (flags & PT_UPDATE_SHADING) != 0;
+    const int N = S->dev.num_prims;
+    if (geometry && d->num_shapes != N) return fail(PT_ERR_INVALID_ARG, "pt_scene_update: num_shapes differs from pt_scene_create's");
+    if (shading && d->num_materials != S->dev.num_materials) return fail(PT_ERR_INVALID_ARG, "pt_scene_update: num_materials differs from pt_scene_create's");
+    if (shading && d->num_lights != S->dev.num_emission) return fail(PT_ERR_INVALID_ARG, "pt_scene_update: num_lights differs from pt_scene_create's");
+    int rc;
+    std::vector<DMaterial> mats;
+    std::vector<DEmission> emis;
+    std::vector<DLight> dlights;
+    if (shading) {
+        if (!d->materials) return fail(PT_ERR_BAD_SCENE, "scene has no materials");
+        if (d->num_lights > 0 && !d->lights) return fail(PT_ERR_BAD_SCENE, "bad light array");
+        if ((rc = check_materials(d)) || (rc = pack_shading(d, N, mats, emis, dlights))) return rc;
+    }
+    if (geometry) {
+        if (!d->shapes) return fail(PT_ERR_BAD_SCENE, "scene has no shapes");
+        if (d->num_meshes < 0 || (d->num_meshes > 0 && !d->meshes)) return fail(PT_ERR_BAD_SCENE, "bad mesh array");
+        if ((rc = check_meshes(d, S->dev.num_materials))) return rc;
+    }
+    DeviceGuard guard;
+    { int grc = guard.enter(S->device); if (grc) return grc; }
+    // frames of this handle that are still in flight, on the caller's streams and on the slots' own, read the scene
+    HIP_TRY(hipDeviceSynchronize());
+    const clk::time_point t_all = clk::now();
+    int64_t us_records = 0, us_refit = 0, us_plan = 0;
+    if (geometry) {
+        clk::time_point t_stage = clk::now();
+        pt_scene_desc dg = *d;                                // material ids are checked against the handle's table
+        dg.num_materials = S->dev.num_materials;
+        int has_sphere = 0;
+        if ((rc = S->st_prims.ensure((size_t)N)) || (rc = S->st_normals.ensure((size_t)N)) || (rc = S->st_status.ensure(1))) return rc;
+        if ((rc = ptp::prims_device(&dg, S->st_prims.p, S->st_normals.p, &has_sphere))) return rc;
+        us_records = us_since(t_stage); t_stage = clk::now();
+        const int n_trees = N > 1 ? (S->have_fast ? 2 : 1) : 0;   // one shape: a dummy node, the root is never box-tested
+        bool whole = true, planned = false;
+        for (int t = 0; t < n_trees; t++) {
+            ptf::Plan& pl = S->refit_plan[t];
+            if (!pl.built) {
+                if ((rc = ptf::plan_build(S->tree[t].nodes.p, S->tree[t].num_nodes, N, &pl))) return rc;
+                planned = true;
+            }
+            whole = whole && pl.whole_tree;
+            // octant tables are made by the single-workgroup launch alone; they exist only for trees far smaller than its reach
+            if (S->tree[t].have_oct && !pl.whole_tree) return fail(PT_ERR_UNSUPPORTED, "pt_scene_update: octant tables on a tree of wide levels");
+        }
+        if (planned) { us_plan = std::max<int64_t>(us_since(t_stage), 1); t_stage = clk::now(); }
+        HIP_TRY(hipMemsetAsync(S->st_status.p, 0, sizeof(unsigned int), nullptr));
+        unsigned int bad = 0;
+        if (!whole || n_trees == 0) {
+            // the leaf boxes, checked before any node array is written (a tree done by one launch checks for itself)
+            if ((rc = S->st_boxes.ensure((size_t)N * 6)) || (rc = ptf::leaf_boxes(S->st_prims.p, N, S->st_boxes.p, S->st_status.p))) return rc;
+            HIP_TRY(hipMemcpy(&bad, S->st_status.p, sizeof bad, hipMemcpyDeviceToHost));
+        }
+        for (int t = 0; t < n_trees && !bad; t++) {
+            pt_scene::Tree& T = S->tree[t];
+            if ((rc = ptf::refit_tree(S->refit_plan[t], T.nodes.p, T.have_oct ? T.nodes_oct.p : nullptr, T.num_nodes, S->st_prims.p,
+                                      whole ? nullptr : S->st_boxes.p, N, S->st_status.p)))
+                return rc;
+        }
+        if (whole && n_trees) HIP_TRY(hipMemcpy(&bad, S->st_status.p, sizeof bad, hipMemcpyDeviceToHost));
+        if (bad) return fail(PT_ERR_UNSUPPORTED, "pt_scene_update: a new coordinate, radius or leaf box is not finite");
+        std::swap(S->prims.p, S->st_prims.p); std::swap(S->prims.n, S->st_prims.n);
+        std::swap(S->normals.p, S->st_normals.p); std::swap(S->normals.n, S->st_normals.n);
+        S->dev.prims = S->prims.p; S->dev.normals = S->normals.p;
+        S->tri_only = !has_sphere;
+        us_refit = us_since(t_stage);
+    }
+    if (shading) {
+        const clk::time_point t_stage = clk::now();
+        HIP_TRY(hipMemcpy(S->materials.p, mats.data(), mats.size() * sizeof(DMaterial), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(S->emission.p, emis.data(), emis.size() * sizeof(DEmission), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(S->lights.p, dlights.data(), dlights.size() * sizeof(DLight), hipMemcpyHostToDevice));
+        S->dev.bg[0] = d->background[0]; S->dev.bg[1] = d->background[1]; S->dev.bg[2] = d->background[2];
+        S->diffuse_only = all_diffuse(d);
+        us_records += us_since(t_stage);
+    }
+    // the handle's own streams do not synchronise with the default stream the kernels above ran on
+    HIP_TRY(hipDeviceSynchronize());
+    select_tree(S, 0);
+    S->updates++;
+    S->update_us[0] = us_since(t_all); S->update_us[1] = us_records; S->update_us[2] = us_refit; S->update_us[3] = us_plan;
+    return PT_OK;
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------------------------------
@@ -1459,9 +1580,19 @@ int pt_scene_destroy(pt_scene* S) {
     S->ad_sum.release(); S->ad_mom.release(); S->ad_list[0].release(); S->ad_list[1].release(); S->ad_count.release();
     S->ad_spp_tmp.release(); S->ad_err_tmp.release();
     S->dn_guide.release(); S->dn_x[0].release(); S->dn_x[1].release(); S->dn_host.release();
+    S->st_prims.release(); S->st_normals.release(); S->st_boxes.release(); S->st_status.release();
+    for (auto& pl : S->refit_plan) ptf::plan_release(&pl);
     S->drop_events();
     delete S;
     return PT_OK;
+}
+
+int pt_scene_update(pt_scene* S, const pt_scene_desc* desc, int flags) {
+    if (!S) return fail(PT_ERR_INVALID_ARG, "pt_scene_update: null scene");
+    if (!desc) return fail(PT_ERR_INVALID_ARG, "pt_scene_update: null scene description");
+    if (flags == 0 || (flags & ~(PT_UPDATE_GEOMETRY | PT_UPDATE_SHADING)))
+        return fail(PT_ERR_INVALID_ARG, "pt_scene_update: flags must be PT_UPDATE_GEOMETRY, PT_UPDATE_SHADING or both");
+    return update_scene(S, desc, flags);
 }
 
 int pt_render_async(pt_scene* S, const pt_render_params* p, float* fb_dev, void* hip_stream) {
@@ -1793,6 +1924,8 @@ int pt_scene_get_info(pt_scene* S, const char* key, int64_t* value) {
     else if (k == "device") *value = S->device;
     else if (k == "sweep_on_device") *value = S->sweep_on_device;         // the internal tree was built on the GPU (pt_sweep_build.hip)
     else if (k.rfind("create_us", 0) == 0 && k.size() == 10 && k[9] >= '0' && k[9] <= '6') *value = S->create_us[k[9] - '0'];
+    else if (k == "updates") *value = S->updates;                         // successful pt_scene_update calls so far
+    else if (k.rfind("update_us", 0) == 0 && k.size() == 10 && k[9] >= '0' && k[9] <= '3') *value = S->update_us[k[9] - '0'];
     else if (k == "kernel") *value = S->info_kernel;                      // the kernel the last render ran on (1, 2 or 3)
     else if (k == "trace_variant") *value = S->info_trace_variant;        // ... and its template arguments (include/pt_api.h)
     else if (k == "block_threads") *value = S->info_kernel == 3 ? kQBlock : kBlock;

@@ -16,6 +16,7 @@ PT_LIGHT_POINT, PT_LIGHT_DIFFUSE_AREA = 0, 1
 PT_TRAVERSAL_DEFAULT, PT_TRAVERSAL_EXACT, PT_TRAVERSAL_PRUNED = 0, 1, 2
 PT_BVH_SORT_TOTAL, PT_BVH_SORT_REFERENCE = 0, 1
 PT_RENDER_NEE = 1
+PT_UPDATE_GEOMETRY, PT_UPDATE_SHADING = 1, 2                                  # pt_scene_update flags
 PT_EXACT_RCP, PT_EXACT_DIV_PI, PT_EXACT_SQRT, PT_EXACT_RAW_RCP = 0, 1, 2, 3   # pt_debug_exact_math ops
 
 STATUS_NAMES = {

@@ -9,8 +9,10 @@ import os
 import numpy as np
 
 from . import _build
-from .ctypes_defs import (PT_OK, PT_TRAVERSAL_DEFAULT, PtAdaptiveParams, PtBvhNode, PtCounters, PtDenoiseParams, PtError,
-                          PtRenderParams, PtSceneDesc)
+from .ctypes_defs import (PT_OK, PT_SHAPE_SPHERE, PT_TRAVERSAL_DEFAULT, PT_UPDATE_GEOMETRY, PT_UPDATE_SHADING, PtAdaptiveParams,
+                          PtBvhNode, PtCounters, PtDenoiseParams, PtError, PtLight, PtMaterial, PtMesh, PtRenderParams, PtSceneDesc,
+                          PtShape)
+from .host import NODE_DTYPE  # noqa: F401  (one definition; callers also read it from here)
 
 _lib = None
 
@@ -18,7 +20,7 @@ EXPORTS = [
     "pt_api_version", "pt_last_error", "pt_scene_create", "pt_scene_destroy", "pt_render", "pt_render_async",
     "pt_render_accumulate", "pt_get_counters", "pt_scene_set_option", "pt_scene_get_info", "pt_debug_math",
     "pt_debug_intersect", "pt_debug_math_host", "pt_bvh_build_device", "pt_bvh_build_sweep", "pt_get_frame_times", "pt_bvh_build_sweep_device",
-    "pt_debug_exact_math", "pt_render_adaptive", "pt_render_aov", "pt_denoise", "pt_denoise_host",
+    "pt_debug_exact_math", "pt_render_adaptive", "pt_render_aov", "pt_denoise", "pt_denoise_host", "pt_scene_update",
 ]
 
 
@@ -36,6 +38,7 @@ def lib():
         L.pt_last_error.restype = C.c_char_p
         L.pt_scene_create.argtypes = [C.POINTER(PtSceneDesc), C.POINTER(vp)]
         L.pt_scene_destroy.argtypes = [vp]
+        L.pt_scene_update.argtypes = [vp, C.POINTER(PtSceneDesc), C.c_int]
         L.pt_render.argtypes = [vp, C.POINTER(PtRenderParams), vp, C.c_int]
         L.pt_render_async.argtypes = [vp, C.POINTER(PtRenderParams), vp, vp]
         L.pt_render_accumulate.argtypes = [vp, C.POINTER(PtRenderParams), vp, vp]
@@ -85,6 +88,13 @@ class DeviceScene:
             self.close()
         except Exception:
             pass
+
+    def update(self, desc, geometry=True, shading=False):
+        """pt_scene_update: new geometry (shapes and meshes of `desc`) and / or new shading values (materials, lights, background)
+        on this handle; both trees keep their topology and are refitted on the device.  Blocking.  `desc` must have the
+        shape count the handle was created with (see edited_desc); its nodes are ignored."""
+        flags = (PT_UPDATE_GEOMETRY if geometry else 0) | (PT_UPDATE_SHADING if shading else 0)
+        _check(lib().pt_scene_update(self._h, C.byref(desc), flags))
 
     def set_option(self, key, value):
         _check(lib().pt_scene_set_option(self._h, key.encode(), int(value)))
@@ -273,8 +283,60 @@ def build_bvh_sweep(desc, on_device=False):
     return d2, {"root": root.value, "depth": depth.value, "build_ms": ms.value, "nodes": nodes}
 
 
+def edited_desc(desc, meshes=None, spheres=None, materials=None, lights=None, background=None):
+    """A copy of `desc` with some of its arrays replaced, for DeviceScene.update and host.refit_bvh.
+      meshes      {mesh_index: (positions [V, 3], normals [V, 3] or None = keep the mesh's normals)}
+      spheres     {shape_id: (center, radius)}
+      materials   a sequence of PtMaterial, as many as desc has       lights   the same with PtLight
+      background  (r, g, b)
+    Topology (indices, shape list, node pool) is shared with `desc`; the copy keeps the new arrays, and `desc`, alive."""
+    d2 = PtSceneDesc()
+    C.memmove(C.byref(d2), C.byref(desc), C.sizeof(PtSceneDesc))
+    keep = [desc]
+    if meshes:
+        arr = (PtMesh * desc.num_meshes)()
+        C.memmove(arr, desc.meshes, C.sizeof(arr))
+        for m, (pos, nrm) in meshes.items():
+            if not 0 <= m < desc.num_meshes:
+                raise ValueError(f"mesh index {m} out of range")
+            P = np.ascontiguousarray(pos, dtype=np.float32).reshape(-1, 3)
+            if P.shape[0] != arr[m].num_vertices:
+                raise ValueError(f"mesh {m} has {arr[m].num_vertices} vertices, got {P.shape[0]}")
+            arr[m].positions = _fp(P)
+            keep.append(P)
+            if nrm is not None:
+                Nn = np.ascontiguousarray(nrm, dtype=np.float32).reshape(-1, 3)
+                if Nn.shape != P.shape:
+                    raise ValueError("normals must match positions")
+                arr[m].normals = _fp(Nn)
+                keep.append(Nn)
+        d2.meshes = arr
+        keep.append(arr)
+    if spheres:
+        arr = (PtShape * desc.num_shapes)()
+        C.memmove(arr, desc.shapes, C.sizeof(arr))
+        for i, (center, radius) in spheres.items():
+            if not 0 <= i < desc.num_shapes or arr[i].type != PT_SHAPE_SPHERE:
+                raise ValueError(f"shape {i} is not a sphere")
+            arr[i].center[:] = [float(x) for x in center]
+            arr[i].radius = float(radius)
+        d2.shapes = arr
+        keep.append(arr)
+    for name, ctype, seq in (("materials", PtMaterial, materials), ("lights", PtLight, lights)):
+        if seq is not None:
+            seq = list(seq)
+            if len(seq) != getattr(desc, "num_" + name):
+                raise ValueError(f"{name}: the count must stay {getattr(desc, 'num_' + name)}")
+            arr = (ctype * max(len(seq), 1))(*seq)
+            setattr(d2, name, arr)
+            keep.append(arr)
+    if background is not None:
+        d2.background[:] = [float(x) for x in background]
+    d2._keep = keep
+    return d2
+
+
 PT_BVH_DEVICE_LBVH, PT_BVH_DEVICE_SAH = 0, 1
-NODE_DTYPE = np.dtype([("bmin", "<f4", 3), ("bmax", "<f4", 3), ("left", "<i4"), ("right", "<i4"), ("prim", "<i4")])
 
 
 def build_bvh_device(desc, method=PT_BVH_DEVICE_SAH):

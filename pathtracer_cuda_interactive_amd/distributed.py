@@ -116,5 +116,9 @@ class ShardedRenderer:
             return None
         return frame[..., :3], frame[..., 3].to(torch.int32), frame[..., 4]
 
+    def update(self, desc, geometry=True, shading=False):
+        """DeviceScene.update on this rank's scene (every rank applies the same edit before the next frame)."""
+        self.scene.update(desc, geometry=geometry, shading=shading)
+
     def close(self):
         self.scene.close()

@@ -9,7 +9,7 @@ import os
 import numpy as np
 
 from . import _build
-from .ctypes_defs import (PT_BVH_SORT_TOTAL, PT_OK, PtCamera, PtError, PtMaterial, PtRenderParams, PtSceneDesc,
+from .ctypes_defs import (PT_BVH_SORT_TOTAL, PT_OK, PtBvhNode, PtCamera, PtError, PtMaterial, PtRenderParams, PtSceneDesc,
                           c_float3)
 
 _lib = None
@@ -38,6 +38,8 @@ def lib():
         L.pt_host_scene_finalize.argtypes = [vp, C.c_int]
         L.pt_host_scene_get_desc.argtypes = [vp, C.POINTER(PtSceneDesc)]
         L.pt_host_scene_bvh_depth.argtypes = [vp]
+        L.pt_host_refit_bvh.argtypes = [C.POINTER(PtSceneDesc), C.POINTER(PtBvhNode)]
+        L.pt_host_compute_normals.argtypes = [C.POINTER(C.c_float), C.c_int, C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_float)]
         L.pt_host_camera_ray_data.argtypes = [C.POINTER(PtCamera), C.c_int, C.c_int, C.POINTER(C.c_float)]
         L.pt_host_camera_ray_data.restype = None
         L.pt_host_default_params.argtypes = [C.POINTER(PtCamera), C.c_int, C.c_int, C.c_int, C.POINTER(PtRenderParams)]
@@ -178,6 +180,31 @@ class HostScene:
         lib().pt_host_default_params(C.byref(cam), w, h, s, C.byref(p))
         p.seed = int(seed)
         return p
+
+
+NODE_DTYPE = np.dtype([("bmin", "<f4", 3), ("bmax", "<f4", 3), ("left", "<i4"), ("right", "<i4"), ("prim", "<i4")])
+
+
+def refit_bvh(desc):
+    """pt_host_refit_bvh: a copy of `desc` whose node pool keeps desc's topology and has every box made anew from desc's shapes
+    and meshes — the tree DeviceScene.update refits a handle to.  The copy keeps the new pool (d2._keep[0], a structured numpy
+    array) and `desc` alive.  Needs no GPU."""
+    nodes = np.zeros(max(desc.num_nodes, 1), dtype=NODE_DTYPE)
+    _check(lib().pt_host_refit_bvh(C.byref(desc), nodes.ctypes.data_as(C.POINTER(PtBvhNode))))
+    d2 = PtSceneDesc()
+    C.memmove(C.byref(d2), C.byref(desc), C.sizeof(PtSceneDesc))
+    d2.nodes = nodes.ctypes.data_as(C.POINTER(PtBvhNode))
+    d2._keep = (nodes, desc)
+    return d2
+
+
+def compute_normals(P, I):
+    """pt_host_compute_normals: the vertex normals add_mesh(normals=None) stores, [V, 3] float32."""
+    P = np.ascontiguousarray(P, dtype=np.float32).reshape(-1, 3)
+    I = np.ascontiguousarray(I, dtype=np.int32).reshape(-1, 3)
+    out = np.empty_like(P)
+    _check(lib().pt_host_compute_normals(_fptr(P), P.shape[0], I.ctypes.data_as(C.POINTER(C.c_int32)), I.shape[0], _fptr(out)))
+    return out
 
 
 def camera_ray_data(cam, width, height):

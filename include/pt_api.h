@@ -198,7 +198,9 @@ int pt_scene_destroy(pt_scene* scene);
  *                       num_shapes), before anything is changed: such a handle cannot be updated at all.
  *   PT_UPDATE_SHADING   materials, lights and background are read again with pt_scene_create's checks.
  *   A call that fails leaves the handle exactly as it was: new records and leaf boxes are made and checked in staging memory
- *   (kept with the handle: 96 bytes per shape, 24 more for scenes beyond a few thousand shapes) before anything is replaced.
+ *   (kept with the handle: 144 bytes per shape — records and vertex normals in staging, and the records that were live before
+ *   the last geometry update, which pt_render_guides reads; the three record buffers rotate, none is copied — 24 more for scenes
+ *   beyond a few thousand shapes) before anything is replaced.
  *   Decided at pt_scene_create and not revisited: whether an internal tree exists and which topology it has, the stack caps, the
  *   order of the top-of-tree prefix kept in LDS (it stays parent-before-child; only its "largest boxes first" choice ages) and
  *   "fast_tree_cost_permille".  Boxes stay exact however far the geometry moves, their quality does not: a caller whose geometry
@@ -319,6 +321,88 @@ int pt_denoise(pt_scene* scene, const pt_denoise_params* d, const float* color, 
 int pt_denoise_host(const pt_denoise_params* d, const float* color, const float* albedo,
                     const float* normal, const float* depth, float* out);
 
+/* Motion vectors with the guide buffers, and temporal accumulation along them — an EXTENSION: off unless called, never part of
+ * a parity or roofline number, no other entry point's output changes by a bit.  DESIGN.md §19.
+ *   pt_render_guides is pt_render_aov (same rays, same traversal, same row selection and packing, the same four buffers bit for
+ *   bit) with two more outputs from the same traversal, in one kernel launch: where each pixel's surface point was in the
+ *   PREVIOUS frame, as seen by the previous camera.  The previous frame has the same width and height.  Blocking, on the default
+ *   stream.  NULL p, m or out, or a geometry value other than the two below: PT_ERR_INVALID_ARG, pt_last_error() names it.
+ *   "Previous geometry" = the primitive records that were live before the most recent successful PT_UPDATE_GEOMETRY; a handle
+ *   that was never updated has previous = current; a shading-only update and a failed update change neither set.
+ *   pt_scene_get_info "prev_geometry" = 1 when a distinct previous record set exists, else 0.
+ *   Arithmetic: fp32 throughout, operations in the order written, no contraction; dot left to right;
+ *   cross(a,b).x = a.y*b.z - a.z*b.y, cyclic for .y and .z; / is IEEE division; sqrt correctly rounded.
+ *   A hit pixel has ray (o, d) and hit (k, t, u, v): what pt_debug_intersect returns for the pixel-centre ray.  Primed records
+ *   are those `geometry` selects, unprimed the current ones.
+ *     sphere flags of the two records differ: the pixel is invalid
+ *     triangle: w = (1.0f - u) - v;  Q = (p0' w + p1' u) + p2' v per component (also with GEOMETRY_CURRENT, where p' = p)
+ *     sphere:   P = o + d t;  Q = c' + (P - c) (r' / r)
+ *   With the previous camera (o', tl', H', V'):
+ *     e = Q - o';  a = tl' - o';  hv = cross(H', V');  D = dot(a, hv);  n0 = dot(e, hv);  s = n0 / D
+ *     n1 = dot(a, cross(e, V'));  n2 = dot(a, cross(H', e))
+ *     motion = ((n1 / n0) (float)width, (-(n2 / n0)) (float)height);  prev_depth = sqrt(dot(e, e))
+ *   motion is the previous position in continuous pixel coordinates, the centre of pixel (i, j) being (i + 0.5, j + 0.5);
+ *   coordinates outside the frame are valid output.  A pixel is INVALID when it is a miss, its record types differ, s > 0 is
+ *   not true, or motion.x, motion.y or prev_depth is not finite; it gets motion = (0, 0) and prev_depth = 0, and
+ *   prev_depth == 0 is the only flag a consumer reads.  Not covered: what is seen in a mirror moves with the mirror's surface. */
+enum { PT_MOTION_GEOMETRY_CURRENT = 0, PT_MOTION_GEOMETRY_PREVIOUS = 1 };
+typedef struct pt_motion_params {
+    float   prev_cam_origin[3], prev_cam_top_left[3], prev_cam_horizontal[3], prev_cam_vertical[3];
+    int32_t geometry;             /* PT_MOTION_GEOMETRY_* */
+} pt_motion_params;               /* 52 bytes */
+typedef struct pt_guide_buffers { /* any pointer may be NULL; on_device != 0: all are device pointers on the scene's GPU */
+    float*   albedo;              /* pt_render_aov's four */
+    float*   normal;
+    float*   depth;
+    int32_t* prim;
+    float*   motion;              /* [rows, W, 2] */
+    float*   prev_depth;          /* [rows, W]    */
+} pt_guide_buffers;
+int pt_render_guides(pt_scene* scene, const pt_render_params* p, const pt_motion_params* m, const pt_guide_buffers* out,
+                     int on_device);
+
+/* Carries a colour history along those motion vectors: an exponential average whose length grows by one per frame up to
+ * max_history where the reprojected history agrees with this frame in depth and normal, and restarts elsewhere. */
+typedef struct pt_temporal_params {
+    int32_t width, height;        /* whole frames only                                                      */
+    int32_t max_history;          /* 0 -> 32; else 1..65536                                                 */
+    float   sigma_z;              /* 0 -> 0.1; else > 0, finite: relative depth tolerance                   */
+    float   normal_min;           /* used as given, in [-1, 1]; tools use 0.9                               */
+    float   scale;                /* 0 -> 1; else > 0, finite: color is multiplied by it first              */
+} pt_temporal_params;             /* 24 bytes */
+
+/* color, normal, hist_color, hist_normal, out_color [H, W, 3]; motion [H, W, 2]; prev_depth, hist_depth, hist_len, out_len [H, W].
+ * on_device != 0: device pointers, enqueued on hip_stream (NULL = default stream) without a host sync, as pt_denoise is;
+ * on_device == 0: host pointers, blocking (staged through memory of the handle).  The library keeps no state: after a call,
+ * (out_color, normal, depth, out_len) of this frame are the next call's hist_*, and the caller ping-pongs them.  out_color may
+ * be color.  out_color == hist_color or out_len == hist_len: PT_ERR_INVALID_ARG, because neighbours are gathered.  All four
+ * hist_* NULL = no history, every pixel takes the fallback (some but not all NULL: PT_ERR_INVALID_ARG).  A parameter out of
+ * range, a NULL parameter struct: PT_ERR_INVALID_ARG, pt_last_error() names the field.
+ *   The rule per pixel p = (i, j), in fp32, in the order written, no contraction, with c = color[p] * scale.
+ *   Fallback: out = c, out_len = 1.
+ *   1. prev_depth[p] == 0: fallback.
+ *   2. x = motion.x - 0.5f, y = motion.y - 0.5f.
+ *   3. Unless x >= -1 && x < W && y >= -1 && y < H: fallback.
+ *   4. x0 = floorf(x), y0 = floorf(y), fx = x - x0, fy = y - y0.
+ *   5. Taps in the order (dy, dx) = (0,0), (0,1), (1,0), (1,1): q = ((int)x0 + dx, (int)y0 + dy),
+ *      b = (dx ? fx : 1.0f - fx) * (dy ? fy : 1.0f - fy).
+ *   6. A tap is skipped when q is outside the frame (no address is formed for it), hist_len[q] > 0 is not true,
+ *      hist_depth[q] == 0, fabsf(hist_depth[q] - prev_depth[p]) <= sigma_z * prev_depth[p] is not true, or
+ *      dot(normal[p], hist_normal[q]) >= normal_min is not true (dot left to right).
+ *   7. A kept tap: sum += hist_color[q] * b per channel, lsum += hist_len[q] * b, wsum += b.
+ *   8. wsum > 0: r = 1.0f / wsum, h = sum * r, n = min(lsum * r + 1.0f, (float)max_history),
+ *      out = h + (c - h) * (1.0f / n), out_len = n.  Otherwise fallback.
+ *   Normals are compared in WORLD space: an object that rotates fast loses its history although its surface points are
+ *   followed correctly.  Non-finite input propagates; what it does is unspecified. */
+int pt_temporal_accumulate(pt_scene* scene, const pt_temporal_params* t, const float* color, const float* normal,
+                           const float* motion, const float* prev_depth, const float* hist_color, const float* hist_normal,
+                           const float* hist_depth, const float* hist_len, float* out_color, float* out_len, int on_device,
+                           void* hip_stream);
+/* The same per-pixel source (csrc/pt_temporal.h) compiled for the HOST: needs no GPU and no scene. */
+int pt_temporal_accumulate_host(const pt_temporal_params* t, const float* color, const float* normal, const float* motion,
+                                const float* prev_depth, const float* hist_color, const float* hist_normal,
+                                const float* hist_depth, const float* hist_len, float* out_color, float* out_len);
+
 int pt_get_counters(pt_scene* scene, pt_counters* out);   /* synchronises the scene's last stream */
 
 /* HIP-event times of the last render calls on the scene, oldest first: kernel_ms[k] / resolve_ms[k] of up to max_frames calls,
@@ -401,7 +485,7 @@ int pt_bvh_build_sweep_device(const pt_scene_desc* desc, pt_bvh_node* out_nodes,
  * "fast_tree" (an internal tree exists), "fast_tree_on" (the next render uses it), "fast_tree_is_callers" (it is the caller's own
  * topology in internal form: the sweep tree did not win the probe), "fast_tree_depth",
  * "fast_tree_cost_permille" (probe-ray node visits, internal / caller's x 1000; 0 = none built), "stack_entries" (per lane),
- * "redo_segments" (with "stats": segments of the last frame traced on the caller's tree), "debug_reruns" (same for pt_debug_intersect),
+ * "prev_geometry", "redo_segments" (with "stats": segments of the last frame traced on the caller's tree), "debug_reruns" (same for pt_debug_intersect),
  * "kernel" / "block_threads" (what the last render ran on), "trace_variant" (the template arguments of the trace kernel that call
  * launched last — for pt_render_adaptive the LIST kernel of its last round; 0 = none launched — packed into one value:
  *     bits  0-3  family: 1 trace_kernel, 2 trace_kernel_v2, 3 trace_kernel_q      bit  10  NEE

@@ -23,6 +23,7 @@
 #include "pt_scene_prep.h"
 #include "pt_scene_refit.h"
 #include "pt_denoise.h"
+#include "pt_temporal.h"
 #include "pt_kernels.h"
 #include "pt_kernel_q.h"
 
@@ -173,6 +174,11 @@ struct pt_scene {
     // (the record buffers then trade places with prims / normals); one refit plan per tree, made on the first geometry update
     DevBuf<DPrim> st_prims;
     DevBuf<DNormals> st_normals;
+    // pt_render_guides: the primitive records that were live before the last successful geometry update.  Allocated on the
+    // first geometry update; the three record buffers then rotate (staging -> current -> previous -> staging), so that an
+    // update that fails in staging destroys neither set and none is ever copied.
+    DevBuf<DPrim> prev_prims;
+    bool have_prev = false;
     DevBuf<float> st_boxes;
     DevBuf<unsigned int> st_status;
     ptf::Plan refit_plan[2];
@@ -195,6 +201,7 @@ struct pt_scene {
     // comes in host memory (colour, albedo, normal, depth: 10 floats per pixel; the result goes back through its first 3)
     DevBuf<float4> dn_guide, dn_x[2];
     DevBuf<float> dn_host;
+    DevBuf<float> tp_host;           // pt_temporal_accumulate: staging of a call that comes in host memory (21 floats per pixel)
     // What a frame's trace kernel writes lives in a frame slot; render call k uses slot k % frames_in_flight.  With more than one
     // slot a single-pass frame runs on the slot's own stream: the trace kernel at once (it reads the immutable scene and writes
     // the slot only), the resolve — the one step that touches the caller's buffer — once the caller's stream has reached the
@@ -1487,7 +1494,9 @@ int update_scene(pt_scene* S, const pt_scene_desc* d, int flags) {
         pt_scene_desc dg = *d;                                // material ids are checked against the handle's table
         dg.num_materials = S->dev.num_materials;
         int has_sphere = 0;
-        if ((rc = S->st_prims.ensure((size_t)N)) || (rc = S->st_normals.ensure((size_t)N)) || (rc = S->st_status.ensure(1))) return rc;
+        if ((rc = S->st_prims.ensure((size_t)N)) || (rc = S->prev_prims.ensure((size_t)N)) || (rc = S->st_normals.ensure((size_t)N)) ||
+            (rc = S->st_status.ensure(1)))
+            return rc;
         if ((rc = ptp::prims_device(&dg, S->st_prims.p, S->st_normals.p, &has_sphere))) return rc;
         us_records = us_since(t_stage); t_stage = clk::now();
         const int n_trees = N > 1 ? (S->have_fast ? 2 : 1) : 0;   // one shape: a dummy node, the root is never box-tested
@@ -1518,7 +1527,9 @@ int update_scene(pt_scene* S, const pt_scene_desc* d, int flags) {
         }
         if (whole && n_trees) HIP_TRY(hipMemcpy(&bad, S->st_status.p, sizeof bad, hipMemcpyDeviceToHost));
         if (bad) return fail(PT_ERR_UNSUPPORTED, "pt_scene_update: a new coordinate, radius or leaf box is not finite");
-        std::swap(S->prims.p, S->st_prims.p); std::swap(S->prims.n, S->st_prims.n);
+        std::swap(S->prev_prims.p, S->st_prims.p); std::swap(S->prev_prims.n, S->st_prims.n);   // the new records, for a moment
+        std::swap(S->prims.p, S->prev_prims.p); std::swap(S->prims.n, S->prev_prims.n);         // current -> previous, new -> current
+        S->have_prev = true;
         std::swap(S->normals.p, S->st_normals.p); std::swap(S->normals.n, S->st_normals.n);
         S->dev.prims = S->prims.p; S->dev.normals = S->normals.p;
         S->tri_only = !has_sphere;
@@ -1538,6 +1549,100 @@ int update_scene(pt_scene* S, const pt_scene_desc* d, int flags) {
     select_tree(S, 0);
     S->updates++;
     S->update_us[0] = us_since(t_all); S->update_us[1] = us_records; S->update_us[2] = us_refit; S->update_us[3] = us_plan;
+    return PT_OK;
+}
+
+// pt_render_aov (m == nullptr) and pt_render_guides: one aov_kernel launch on the default stream, blocking.
+int guide_pass(pt_scene* S, const pt_render_params* p, const pt_motion_params* m, const pt_guide_buffers& out, int on_device) {
+    float *albedo = out.albedo, *normal = out.normal, *depth = out.depth;
+    int32_t* prim = out.prim;
+    float *motion = m ? out.motion : nullptr, *prev_depth = m ? out.prev_depth : nullptr;
+    if (p->width <= 0 || p->height <= 0) return fail(PT_ERR_INVALID_ARG, "width and height must be positive");
+    const int traversal = p->traversal == PT_TRAVERSAL_DEFAULT ? PT_TRAVERSAL_EXACT : p->traversal;
+    if (traversal != PT_TRAVERSAL_EXACT && traversal != PT_TRAVERSAL_PRUNED) return fail(PT_ERR_INVALID_ARG, "unknown traversal mode");
+    RowSel rows;
+    int rc = select_rows(p, &rows);
+    if (rc) return rc;
+    const uint64_t npix = (uint64_t)rows.count * (uint64_t)p->width;
+    if (npix > (1ull << 30)) return fail(PT_ERR_INVALID_ARG, "more than 2^30 pixels per call");
+    if (npix == 0 || (!albedo && !normal && !depth && !prim && !motion && !prev_depth)) return PT_OK;
+    DeviceGuard guard;
+    { int grc = guard.enter(S->device); if (grc) return grc; }
+    // host outputs are staged in buffers of this call
+    DevBuf<float> d_albedo, d_normal, d_depth, d_motion, d_prev_depth;
+    DevBuf<int32_t> d_prim;
+    float *o_albedo = albedo, *o_normal = normal, *o_depth = depth;
+    int32_t* o_prim = prim;
+    if (!on_device) {
+        if ((albedo && (rc = d_albedo.ensure(npix * 3))) || (normal && (rc = d_normal.ensure(npix * 3))) ||
+            (depth && (rc = d_depth.ensure(npix))) || (prim && (rc = d_prim.ensure(npix))) ||
+            (motion && (rc = d_motion.ensure(npix * 2))) || (prev_depth && (rc = d_prev_depth.ensure(npix))))
+            return rc;
+        o_albedo = albedo ? d_albedo.p : nullptr; o_normal = normal ? d_normal.p : nullptr;
+        o_depth = depth ? d_depth.p : nullptr; o_prim = prim ? d_prim.p : nullptr;
+    }
+    MotionDev mo{};
+    if (m) {
+        std::memcpy(mo.cam.origin, m->prev_cam_origin, sizeof mo.cam.origin);
+        std::memcpy(mo.cam.top_left, m->prev_cam_top_left, sizeof mo.cam.top_left);
+        std::memcpy(mo.cam.horizontal, m->prev_cam_horizontal, sizeof mo.cam.horizontal);
+        std::memcpy(mo.cam.vertical, m->prev_cam_vertical, sizeof mo.cam.vertical);
+        // a handle that was never updated has previous = current
+        mo.prev_prims = m->geometry == PT_MOTION_GEOMETRY_PREVIOUS && S->have_prev ? S->prev_prims.p : S->prims.p;
+        mo.motion = on_device ? motion : (motion ? d_motion.p : nullptr);
+        mo.prev_depth = on_device ? prev_depth : (prev_depth ? d_prev_depth.p : nullptr);
+    }
+    // the tree a render traverses (pt_debug_intersect's choice): the internal one with ties settled in the caller's visit order
+    // and reference-order reruns where scene creation kept one and "fast_tree" is on, else the caller's
+    const bool fast = S->have_fast && S->opt_fast_tree;
+    select_tree(S, fast ? 1 : 0, fast);
+    const int cap = fast && S->dev.redo_cap > S->dev.stack_cap ? S->dev.redo_cap : S->dev.stack_cap;
+    const uint32_t lds = (uint32_t)(kBlock / 64) * (uint32_t)cap * 64u * 4u;
+    RenderDev rd{};
+    std::memcpy(rd.cam_origin, p->cam_origin, sizeof rd.cam_origin);
+    std::memcpy(rd.cam_top_left, p->cam_top_left, sizeof rd.cam_top_left);
+    std::memcpy(rd.cam_horizontal, p->cam_horizontal, sizeof rd.cam_horizontal);
+    std::memcpy(rd.cam_vertical, p->cam_vertical, sizeof rd.cam_vertical);
+    rd.width = p->width; rd.height = p->height;
+    rd.row_begin = rows.begin; rd.row_step = rows.step; rd.num_rows = rows.count;
+    rd.npix = (uint32_t)npix;
+    rd.div_width = make_fastdiv((uint32_t)p->width);
+    const dim3 grid((unsigned)((npix + kBlock - 1) / kBlock));
+    if (m && traversal == PT_TRAVERSAL_PRUNED)
+        hipLaunchKernelGGL((aov_kernel<true, true>), grid, dim3(kBlock), lds, nullptr, S->dev, rd, o_albedo, o_normal, o_depth, o_prim, mo);
+    else if (m)
+        hipLaunchKernelGGL((aov_kernel<false, true>), grid, dim3(kBlock), lds, nullptr, S->dev, rd, o_albedo, o_normal, o_depth, o_prim, mo);
+    else if (traversal == PT_TRAVERSAL_PRUNED)
+        hipLaunchKernelGGL(aov_kernel<true>, grid, dim3(kBlock), lds, nullptr, S->dev, rd, o_albedo, o_normal, o_depth, o_prim);
+    else
+        hipLaunchKernelGGL(aov_kernel<false>, grid, dim3(kBlock), lds, nullptr, S->dev, rd, o_albedo, o_normal, o_depth, o_prim);
+    HIP_TRY(hipGetLastError());
+    if (on_device) {
+        HIP_TRY(hipStreamSynchronize(nullptr));
+        return PT_OK;
+    }
+    if (albedo) HIP_TRY(hipMemcpy(albedo, d_albedo.p, npix * 3 * sizeof(float), hipMemcpyDeviceToHost));
+    if (normal) HIP_TRY(hipMemcpy(normal, d_normal.p, npix * 3 * sizeof(float), hipMemcpyDeviceToHost));
+    if (depth) HIP_TRY(hipMemcpy(depth, d_depth.p, npix * sizeof(float), hipMemcpyDeviceToHost));
+    if (prim) HIP_TRY(hipMemcpy(prim, d_prim.p, npix * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (motion) HIP_TRY(hipMemcpy(motion, d_motion.p, npix * 2 * sizeof(float), hipMemcpyDeviceToHost));
+    if (prev_depth) HIP_TRY(hipMemcpy(prev_depth, d_prev_depth.p, npix * sizeof(float), hipMemcpyDeviceToHost));
+    return PT_OK;
+}
+
+// Arguments of pt_temporal_accumulate and its host twin: nulls, the two forbidden aliases, the parameter ranges.
+int temporal_args(const pt_temporal_params* t, const float* color, const float* normal, const float* motion, const float* prev_depth,
+                  const float* hist_color, const float* hist_normal, const float* hist_depth, const float* hist_len,
+                  const float* out_color, const float* out_len, ptt::Resolved* r) {
+    if (!t) return fail(PT_ERR_INVALID_ARG, "pt_temporal_accumulate: null pt_temporal_params");
+    if (!color || !normal || !motion || !prev_depth || !out_color || !out_len)
+        return fail(PT_ERR_INVALID_ARG, "pt_temporal_accumulate: null color, normal, motion, prev_depth, out_color or out_len");
+    const int n_hist = (hist_color != nullptr) + (hist_normal != nullptr) + (hist_depth != nullptr) + (hist_len != nullptr);
+    if (n_hist != 0 && n_hist != 4)
+        return fail(PT_ERR_INVALID_ARG, "pt_temporal_accumulate: hist_color, hist_normal, hist_depth, hist_len must be given together or all be null");
+    if (n_hist && out_color == hist_color) return fail(PT_ERR_INVALID_ARG, "pt_temporal_accumulate: out_color must not be hist_color (neighbours are gathered)");
+    if (n_hist && out_len == hist_len) return fail(PT_ERR_INVALID_ARG, "pt_temporal_accumulate: out_len must not be hist_len (neighbours are gathered)");
+    if (const char* bad = ptt::resolve(t, r)) return fail(PT_ERR_INVALID_ARG, std::string("pt_temporal_params.") + bad + " out of range");
     return PT_OK;
 }
 
@@ -1579,8 +1684,8 @@ int pt_scene_destroy(pt_scene* S) {
     S->lights.release(); S->accum.release(); S->fb_tmp.release();
     S->ad_sum.release(); S->ad_mom.release(); S->ad_list[0].release(); S->ad_list[1].release(); S->ad_count.release();
     S->ad_spp_tmp.release(); S->ad_err_tmp.release();
-    S->dn_guide.release(); S->dn_x[0].release(); S->dn_x[1].release(); S->dn_host.release();
-    S->st_prims.release(); S->st_normals.release(); S->st_boxes.release(); S->st_status.release();
+    S->dn_guide.release(); S->dn_x[0].release(); S->dn_x[1].release(); S->dn_host.release(); S->tp_host.release();
+    S->st_prims.release(); S->prev_prims.release(); S->st_normals.release(); S->st_boxes.release(); S->st_status.release();
     for (auto& pl : S->refit_plan) ptf::plan_release(&pl);
     S->drop_events();
     delete S;
@@ -1722,58 +1827,68 @@ int pt_render_adaptive(pt_scene* S, const pt_render_params* p, const pt_adaptive
 
 int pt_render_aov(pt_scene* S, const pt_render_params* p, float* albedo, float* normal, float* depth, int32_t* prim, int on_device) {
     if (!S || !p) return fail(PT_ERR_INVALID_ARG, "null argument");
-    if (p->width <= 0 || p->height <= 0) return fail(PT_ERR_INVALID_ARG, "width and height must be positive");
-    const int traversal = p->traversal == PT_TRAVERSAL_DEFAULT ? PT_TRAVERSAL_EXACT : p->traversal;
-    if (traversal != PT_TRAVERSAL_EXACT && traversal != PT_TRAVERSAL_PRUNED) return fail(PT_ERR_INVALID_ARG, "unknown traversal mode");
-    RowSel rows;
-    int rc = select_rows(p, &rows);
+    const pt_guide_buffers out{albedo, normal, depth, prim, nullptr, nullptr};
+    return guide_pass(S, p, nullptr, out, on_device);
+}
+
+int pt_render_guides(pt_scene* S, const pt_render_params* p, const pt_motion_params* m, const pt_guide_buffers* out, int on_device) {
+    if (!S) return fail(PT_ERR_INVALID_ARG, "pt_render_guides: null scene");
+    if (!p) return fail(PT_ERR_INVALID_ARG, "pt_render_guides: null p");
+    if (!m) return fail(PT_ERR_INVALID_ARG, "pt_render_guides: null m");
+    if (!out) return fail(PT_ERR_INVALID_ARG, "pt_render_guides: null out");
+    if (m->geometry != PT_MOTION_GEOMETRY_CURRENT && m->geometry != PT_MOTION_GEOMETRY_PREVIOUS)
+        return fail(PT_ERR_INVALID_ARG, "pt_motion_params.geometry must be PT_MOTION_GEOMETRY_CURRENT or PT_MOTION_GEOMETRY_PREVIOUS");
+    return guide_pass(S, p, m, *out, on_device);
+}
+
+int pt_temporal_accumulate(pt_scene* S, const pt_temporal_params* t, const float* color, const float* normal, const float* motion,
+                           const float* prev_depth, const float* hist_color, const float* hist_normal, const float* hist_depth,
+                           const float* hist_len, float* out_color, float* out_len, int on_device, void* hip_stream) {
+    if (!S) return fail(PT_ERR_INVALID_ARG, "pt_temporal_accumulate: null scene");
+    ptt::Resolved r;
+    int rc = temporal_args(t, color, normal, motion, prev_depth, hist_color, hist_normal, hist_depth, hist_len, out_color, out_len, &r);
     if (rc) return rc;
-    const uint64_t npix = (uint64_t)rows.count * (uint64_t)p->width;
-    if (npix > (1ull << 30)) return fail(PT_ERR_INVALID_ARG, "more than 2^30 pixels per call");
-    if (npix == 0 || (!albedo && !normal && !depth && !prim)) return PT_OK;
     DeviceGuard guard;
     { int grc = guard.enter(S->device); if (grc) return grc; }
-    // host outputs are staged in buffers of this call
-    DevBuf<float> d_albedo, d_normal, d_depth;
-    DevBuf<int32_t> d_prim;
-    float *o_albedo = albedo, *o_normal = normal, *o_depth = depth;
-    int32_t* o_prim = prim;
-    if (!on_device) {
-        if ((albedo && (rc = d_albedo.ensure(npix * 3))) || (normal && (rc = d_normal.ensure(npix * 3))) ||
-            (depth && (rc = d_depth.ensure(npix))) || (prim && (rc = d_prim.ensure(npix))))
-            return rc;
-        o_albedo = albedo ? d_albedo.p : nullptr; o_normal = normal ? d_normal.p : nullptr;
-        o_depth = depth ? d_depth.p : nullptr; o_prim = prim ? d_prim.p : nullptr;
-    }
-    // the tree a render traverses (pt_debug_intersect's choice): the internal one with ties settled in the caller's visit order
-    // and reference-order reruns where scene creation kept one and "fast_tree" is on, else the caller's
-    const bool fast = S->have_fast && S->opt_fast_tree;
-    select_tree(S, fast ? 1 : 0, fast);
-    const int cap = fast && S->dev.redo_cap > S->dev.stack_cap ? S->dev.redo_cap : S->dev.stack_cap;
-    const uint32_t lds = (uint32_t)(kBlock / 64) * (uint32_t)cap * 64u * 4u;
-    RenderDev rd{};
-    std::memcpy(rd.cam_origin, p->cam_origin, sizeof rd.cam_origin);
-    std::memcpy(rd.cam_top_left, p->cam_top_left, sizeof rd.cam_top_left);
-    std::memcpy(rd.cam_horizontal, p->cam_horizontal, sizeof rd.cam_horizontal);
-    std::memcpy(rd.cam_vertical, p->cam_vertical, sizeof rd.cam_vertical);
-    rd.width = p->width; rd.height = p->height;
-    rd.row_begin = rows.begin; rd.row_step = rows.step; rd.num_rows = rows.count;
-    rd.npix = (uint32_t)npix;
-    rd.div_width = make_fastdiv((uint32_t)p->width);
-    const dim3 grid((unsigned)((npix + kBlock - 1) / kBlock));
-    if (traversal == PT_TRAVERSAL_PRUNED)
-        hipLaunchKernelGGL(aov_kernel<true>, grid, dim3(kBlock), lds, nullptr, S->dev, rd, o_albedo, o_normal, o_depth, o_prim);
-    else
-        hipLaunchKernelGGL(aov_kernel<false>, grid, dim3(kBlock), lds, nullptr, S->dev, rd, o_albedo, o_normal, o_depth, o_prim);
-    HIP_TRY(hipGetLastError());
     if (on_device) {
-        HIP_TRY(hipStreamSynchronize(nullptr));
+        const hipError_t e = (hipError_t)ptt::run_device(r, color, normal, motion, prev_depth, hist_color, hist_normal, hist_depth,
+                                                         hist_len, out_color, out_len, hip_stream);
+        if (e != hipSuccess) return fail(PT_ERR_DEVICE, std::string("pt_temporal_accumulate: ") + hipGetErrorString(e));
         return PT_OK;
     }
-    if (albedo) HIP_TRY(hipMemcpy(albedo, d_albedo.p, npix * 3 * sizeof(float), hipMemcpyDeviceToHost));
-    if (normal) HIP_TRY(hipMemcpy(normal, d_normal.p, npix * 3 * sizeof(float), hipMemcpyDeviceToHost));
-    if (depth) HIP_TRY(hipMemcpy(depth, d_depth.p, npix * sizeof(float), hipMemcpyDeviceToHost));
-    if (prim) HIP_TRY(hipMemcpy(prim, d_prim.p, npix * sizeof(int32_t), hipMemcpyDeviceToHost));
+    // host pointers: one staging buffer of this handle; per pixel 3 + 3 + 2 + 1 inputs, 3 + 3 + 1 + 1 of history, 3 + 1 outputs
+    const size_t npix = (size_t)r.width * (size_t)r.height;
+    if ((rc = S->tp_host.ensure(npix * 21))) return rc;
+    float* h = S->tp_host.p;
+    float* d_color = h; float* d_normal = h + npix * 3; float* d_motion = h + npix * 6; float* d_pz = h + npix * 8;
+    float* d_hc = h + npix * 9; float* d_hn = h + npix * 12; float* d_hz = h + npix * 15; float* d_hl = h + npix * 16;
+    float* d_oc = h + npix * 17; float* d_ol = h + npix * 20;
+    HIP_TRY(hipMemcpy(d_color, color, npix * 3 * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_normal, normal, npix * 3 * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_motion, motion, npix * 2 * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_pz, prev_depth, npix * sizeof(float), hipMemcpyHostToDevice));
+    if (hist_color) {
+        HIP_TRY(hipMemcpy(d_hc, hist_color, npix * 3 * sizeof(float), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_hn, hist_normal, npix * 3 * sizeof(float), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_hz, hist_depth, npix * sizeof(float), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_hl, hist_len, npix * sizeof(float), hipMemcpyHostToDevice));
+    } else {
+        d_hc = d_hn = d_hz = d_hl = nullptr;
+    }
+    const hipError_t e = (hipError_t)ptt::run_device(r, d_color, d_normal, d_motion, d_pz, d_hc, d_hn, d_hz, d_hl, d_oc, d_ol, nullptr);
+    if (e != hipSuccess) return fail(PT_ERR_DEVICE, std::string("pt_temporal_accumulate: ") + hipGetErrorString(e));
+    HIP_TRY(hipMemcpy(out_color, d_oc, npix * 3 * sizeof(float), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out_len, d_ol, npix * sizeof(float), hipMemcpyDeviceToHost));
+    return PT_OK;
+}
+
+int pt_temporal_accumulate_host(const pt_temporal_params* t, const float* color, const float* normal, const float* motion,
+                                const float* prev_depth, const float* hist_color, const float* hist_normal, const float* hist_depth,
+                                const float* hist_len, float* out_color, float* out_len) {
+    ptt::Resolved r;
+    int rc = temporal_args(t, color, normal, motion, prev_depth, hist_color, hist_normal, hist_depth, hist_len, out_color, out_len, &r);
+    if (rc) return rc;
+    ptt::run_host(r, color, normal, motion, prev_depth, hist_color, hist_normal, hist_depth, hist_len, out_color, out_len);
     return PT_OK;
 }
 
@@ -1924,6 +2039,7 @@ int pt_scene_get_info(pt_scene* S, const char* key, int64_t* value) {
     else if (k == "device") *value = S->device;
     else if (k == "sweep_on_device") *value = S->sweep_on_device;         // the internal tree was built on the GPU (pt_sweep_build.hip)
     else if (k.rfind("create_us", 0) == 0 && k.size() == 10 && k[9] >= '0' && k[9] <= '6') *value = S->create_us[k[9] - '0'];
+    else if (k == "prev_geometry") *value = S->have_prev ? 1 : 0;         // records from before the last geometry update are kept (pt_render_guides)
     else if (k == "updates") *value = S->updates;                         // successful pt_scene_update calls so far
     else if (k.rfind("update_us", 0) == 0 && k.size() == 10 && k[9] >= '0' && k[9] <= '3') *value = S->update_us[k[9] - '0'];
     else if (k == "kernel") *value = S->info_kernel;                      // the kernel the last render ran on (1, 2 or 3)

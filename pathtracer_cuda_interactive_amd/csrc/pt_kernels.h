@@ -13,6 +13,7 @@
 
 #include "pt_layout.h"
 #include "pt_math.h"
+#include "pt_temporal.h"
 #include "pt_trace.h"
 
 namespace ptk {
@@ -745,10 +746,22 @@ __global__ __launch_bounds__(kBlock) void intersect_kernel(SceneDev scn, const f
 //   prim    shape id, -1 on a miss                 depth   t, 0 on a miss
 //   normal  make_surface's shading normal turned towards the camera as shade_and_bounce turns it; 0 on a miss
 //   albedo  the material's reflectance, (1,1,1) for a mirror; 0 on a miss and where a render adds emission at this hit
-template <bool PRUNE>
+//
+// MOTION (pt_render_guides): from the same hit, where the surface point was in the previous frame — (prim, u, v) names the same
+// point of a triangle in the previous primitive records, a sphere carries its point along by its centre and radius — projected
+// into the previous camera (pt_temporal.h: project_previous).  mo.prev_prims = the current records or the ones that were live
+// before the last geometry update.  motion = (0, 0) and prev_depth = 0 on a miss and wherever the rule calls the pixel invalid.
+struct MotionDev {
+    ptt::PrevCam cam;
+    const DPrim* prev_prims;
+    float* motion;                  // [rows, W, 2] or null
+    float* prev_depth;              // [rows, W] or null
+};
+
+template <bool PRUNE, bool MOTION = false>
 __global__ __launch_bounds__(kBlock) void aov_kernel(SceneDev scn, RenderDev rp, float* __restrict__ albedo,
                                                      float* __restrict__ normal, float* __restrict__ depth,
-                                                     int32_t* __restrict__ prim) {
+                                                     int32_t* __restrict__ prim, MotionDev mo = MotionDev{}) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     ptd::SceneView sv;
     sv.nodes = scn.nodes; sv.prims = scn.prims; sv.normals = scn.normals;
@@ -801,6 +814,28 @@ __global__ __launch_bounds__(kBlock) void aov_kernel(SceneDev scn, RenderDev rp,
     if (depth) depth[k] = t;
     if (normal) { normal[3 * (size_t)k] = n.x; normal[3 * (size_t)k + 1] = n.y; normal[3 * (size_t)k + 2] = n.z; }
     if (albedo) { albedo[3 * (size_t)k] = a.x; albedo[3 * (size_t)k + 1] = a.y; albedo[3 * (size_t)k + 2] = a.z; }
+    if (MOTION) {
+        float mx = 0.0f, my = 0.0f, pz = 0.0f;
+        if (h.prim >= 0) {
+            const float4 c0 = ptd::ld4(sv.prims + h.prim, 0), c2 = ptd::ld4(sv.prims + h.prim, 2);
+            const float4 q0 = ptd::ld4(mo.prev_prims + h.prim, 0), q1 = ptd::ld4(mo.prev_prims + h.prim, 1),
+                         q2 = ptd::ld4(mo.prev_prims + h.prim, 2);
+            const bool sphere = __builtin_bit_cast(int32_t, c2.y) < 0, sphere_prev = __builtin_bit_cast(int32_t, q2.y) < 0;
+            if (sphere == sphere_prev) {
+                ptm::V3 Q;
+                if (sphere) {
+                    const ptm::V3 P = r.org + r.dir * h.t;
+                    Q = ptm::mk(q0.x, q0.y, q0.z) + (P - ptm::mk(c0.x, c0.y, c0.z)) * (q0.w / c0.w);
+                } else {
+                    const float w = (1.0f - h.u) - h.v;
+                    Q = (ptm::mk(q0.x, q0.y, q0.z) * w + ptm::mk(q0.w, q1.x, q1.y) * h.u) + ptm::mk(q1.z, q1.w, q2.x) * h.v;
+                }
+                (void)ptt::project_previous(Q, mo.cam, rp.width, rp.height, mx, my, pz);
+            }
+        }
+        if (mo.motion) { mo.motion[2 * (size_t)k] = mx; mo.motion[2 * (size_t)k + 1] = my; }
+        if (mo.prev_depth) mo.prev_depth[k] = pz;
+    }
 }
 
 // Inner-node visits of a fixed set of probe rays through the tree `scn` points at (pt_api.hip: validate_and_build chooses

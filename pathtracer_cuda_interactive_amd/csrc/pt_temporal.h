@@ -1,0 +1,133 @@
+// pt_temporal.h — the per-pixel rules of pt_render_guides' motion part and of pt_temporal_accumulate (include/pt_api.h,
+// DESIGN.md §19), written once for the device (aov_kernel<., true> in pt_kernels.h, pt_temporal.hip) and for the host twin
+// pt_temporal_accumulate_host.
+//
+// Every operation is an IEEE fp32 + - * / sqrt in the order written (no contraction: the build forbids it), so the device, the
+// host twin and a numpy restatement give the same bits.
+#pragma once
+
+#include <stdint.h>
+
+#include "../../include/pt_api.h"
+#include "pt_math.h"
+
+namespace ptt {
+
+PT_HD bool finite32(float v) { return __builtin_fabsf(v) <= 3.402823466e+38f; }   // false for inf and NaN
+
+// The previous camera of pt_motion_params, by value in the kernel's arguments.
+struct PrevCam {
+    float origin[3], top_left[3], horizontal[3], vertical[3];
+};
+
+// Projection of the previous position Q of a pixel's surface point into the previous camera: continuous pixel coordinates
+// (the centre of pixel (i, j) is (i + 0.5, j + 0.5)) and the distance from the previous camera.  False — and zeros — where
+// Q is not in front of that camera or a result is not finite.
+PT_HD bool project_previous(ptm::V3 Q, const PrevCam& c, int width, int height, float& mx, float& my, float& prev_depth) {
+    const ptm::V3 o = ptm::mk(c.origin[0], c.origin[1], c.origin[2]);
+    const ptm::V3 tl = ptm::mk(c.top_left[0], c.top_left[1], c.top_left[2]);
+    const ptm::V3 hz = ptm::mk(c.horizontal[0], c.horizontal[1], c.horizontal[2]);
+    const ptm::V3 vt = ptm::mk(c.vertical[0], c.vertical[1], c.vertical[2]);
+    const ptm::V3 e = Q - o;
+    const ptm::V3 a = tl - o;
+    const ptm::V3 hv = ptm::cross(hz, vt);
+    const float D = ptm::dot(a, hv);
+    const float n0 = ptm::dot(e, hv);
+    const float s = n0 / D;
+    const float n1 = ptm::dot(a, ptm::cross(e, vt));
+    const float n2 = ptm::dot(a, ptm::cross(hz, e));
+    const float x = (n1 / n0) * (float)width;
+    const float y = (-(n2 / n0)) * (float)height;
+    const float z = ptm::sqrt_exact(ptm::dot(e, e));
+    const bool ok = s > 0.0f && finite32(x) && finite32(y) && finite32(z);
+    mx = ok ? x : 0.0f;
+    my = ok ? y : 0.0f;
+    prev_depth = ok ? z : 0.0f;
+    return ok;
+}
+
+// pt_temporal_params with the defaults resolved
+struct Resolved {
+    int32_t width, height;
+    float max_history;               // (float)max_history: exact, at most 65536
+    float sigma_z, normal_min, scale;
+};
+
+// nullptr, or the name of the first field that is out of range
+inline const char* resolve(const pt_temporal_params* t, Resolved* r) {
+    auto pos_finite = [](float v) { return v > 0.0f && v <= 3.402823466e+38f; };
+    if (t->width <= 0 || t->height <= 0) return "width / height";
+    if ((int64_t)t->width * (int64_t)t->height > (1ll << 30)) return "width * height (more than 2^30 pixels)";
+    if (t->max_history < 0 || t->max_history > 65536) return "max_history";
+    if (t->sigma_z != 0.0f && !pos_finite(t->sigma_z)) return "sigma_z";
+    if (!(t->normal_min >= -1.0f && t->normal_min <= 1.0f)) return "normal_min";
+    if (t->scale != 0.0f && !pos_finite(t->scale)) return "scale";
+    r->width = t->width; r->height = t->height;
+    r->max_history = (float)(t->max_history ? t->max_history : 32);
+    r->sigma_z = t->sigma_z != 0.0f ? t->sigma_z : 0.1f;
+    r->normal_min = t->normal_min;
+    r->scale = t->scale != 0.0f ? t->scale : 1.0f;
+    return nullptr;
+}
+
+// One pixel of pt_temporal_accumulate.  hist_color == nullptr: no history.  The four tap addresses are formed only after the
+// clip to the frame.  out_color may be `color`: a pixel reads only its own colour.
+PT_HD void accumulate_pixel(const Resolved& r, int px, int py, const float* __restrict__ normal, const float* __restrict__ motion,
+                            const float* __restrict__ prev_depth, const float* __restrict__ hist_color,
+                            const float* __restrict__ hist_normal, const float* __restrict__ hist_depth,
+                            const float* __restrict__ hist_len, const float* color, float* out_color,
+                            float* __restrict__ out_len) {
+    const size_t p = (size_t)py * (size_t)r.width + (size_t)px;
+    const float cr = color[3 * p] * r.scale, cg = color[3 * p + 1] * r.scale, cb = color[3 * p + 2] * r.scale;
+    float o_r = cr, o_g = cg, o_b = cb, o_len = 1.0f;            // the fallback
+    const float zp = prev_depth[p];
+    if (hist_color && zp != 0.0f) {
+        const float x = motion[2 * p] - 0.5f, y = motion[2 * p + 1] - 0.5f;
+        if (x >= -1.0f && x < (float)r.width && y >= -1.0f && y < (float)r.height) {
+            const float x0 = __builtin_floorf(x), y0 = __builtin_floorf(y);
+            const float fx = x - x0, fy = y - y0;
+            const int ix = (int)x0, iy = (int)y0;
+            const float nx = normal[3 * p], ny = normal[3 * p + 1], nz = normal[3 * p + 2];
+            const float tol = r.sigma_z * zp;
+            float sr = 0.0f, sg = 0.0f, sb = 0.0f, lsum = 0.0f, wsum = 0.0f;
+#pragma unroll
+            for (int dy = 0; dy < 2; dy++) {
+#pragma unroll
+                for (int dx = 0; dx < 2; dx++) {
+                    const int qx = ix + dx, qy = iy + dy;
+                    if (qx < 0 || qx >= r.width || qy < 0 || qy >= r.height) continue;
+                    const float b = (dx ? fx : 1.0f - fx) * (dy ? fy : 1.0f - fy);
+                    const size_t q = (size_t)qy * (size_t)r.width + (size_t)qx;
+                    const float hl = hist_len[q], hz = hist_depth[q];
+                    if (!(hl > 0.0f) || hz == 0.0f) continue;
+                    if (!(__builtin_fabsf(hz - zp) <= tol)) continue;
+                    if (!(nx * hist_normal[3 * q] + ny * hist_normal[3 * q + 1] + nz * hist_normal[3 * q + 2] >= r.normal_min)) continue;
+                    sr = sr + hist_color[3 * q] * b; sg = sg + hist_color[3 * q + 1] * b; sb = sb + hist_color[3 * q + 2] * b;
+                    lsum = lsum + hl * b;
+                    wsum = wsum + b;
+                }
+            }
+            if (wsum > 0.0f) {
+                const float inv = 1.0f / wsum;
+                const float hr = sr * inv, hg = sg * inv, hb = sb * inv;
+                const float n = ptm::fmin2(lsum * inv + 1.0f, r.max_history);
+                const float a = 1.0f / n;
+                o_r = hr + (cr - hr) * a; o_g = hg + (cg - hg) * a; o_b = hb + (cb - hb) * a;
+                o_len = n;
+            }
+        }
+    }
+    out_color[3 * p] = o_r; out_color[3 * p + 1] = o_g; out_color[3 * p + 2] = o_b;
+    out_len[p] = o_len;
+}
+
+// Device side (pt_temporal.hip): one kernel on `stream`, no host sync.  Returns a hipError_t.
+int run_device(const Resolved& r, const float* color, const float* normal, const float* motion, const float* prev_depth,
+               const float* hist_color, const float* hist_normal, const float* hist_depth, const float* hist_len,
+               float* out_color, float* out_len, void* hip_stream);
+// Host twin: the same function over the frame.
+void run_host(const Resolved& r, const float* color, const float* normal, const float* motion, const float* prev_depth,
+              const float* hist_color, const float* hist_normal, const float* hist_depth, const float* hist_len,
+              float* out_color, float* out_len);
+
+}  // namespace ptt

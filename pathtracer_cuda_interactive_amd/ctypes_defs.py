@@ -95,6 +95,27 @@ class PtDenoiseParams(C.Structure):
                 ("sigma_z", C.c_float), ("sigma_c", C.c_float), ("scale", C.c_float), ("albedo_floor", C.c_float)]
 
 
+PT_MOTION_GEOMETRY_CURRENT, PT_MOTION_GEOMETRY_PREVIOUS = 0, 1                # pt_motion_params.geometry
+
+
+class PtMotionParams(C.Structure):
+    """pt_motion_params (pt_api.h): the previous frame's camera and which record set holds its geometry (pt_render_guides)."""
+    _fields_ = [("prev_cam_origin", c_float3), ("prev_cam_top_left", c_float3), ("prev_cam_horizontal", c_float3),
+                ("prev_cam_vertical", c_float3), ("geometry", C.c_int32)]
+
+
+class PtGuideBuffers(C.Structure):
+    """pt_guide_buffers (pt_api.h): the six outputs of pt_render_guides, any of them NULL."""
+    _fields_ = [("albedo", C.c_void_p), ("normal", C.c_void_p), ("depth", C.c_void_p), ("prim", C.c_void_p),
+                ("motion", C.c_void_p), ("prev_depth", C.c_void_p)]
+
+
+class PtTemporalParams(C.Structure):
+    """pt_temporal_params (pt_api.h): history length cap and the depth / normal tests of pt_temporal_accumulate."""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("max_history", C.c_int32), ("sigma_z", C.c_float),
+                ("normal_min", C.c_float), ("scale", C.c_float)]
+
+
 class PtCamera(C.Structure):
     _fields_ = [("lookfrom", c_float3), ("lookat", c_float3), ("up", c_float3), ("vfov", C.c_float),
                 ("width", C.c_int32), ("height", C.c_int32), ("spp", C.c_int32)]

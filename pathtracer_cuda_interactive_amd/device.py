@@ -9,9 +9,10 @@ import os
 import numpy as np
 
 from . import _build
-from .ctypes_defs import (PT_OK, PT_SHAPE_SPHERE, PT_TRAVERSAL_DEFAULT, PT_UPDATE_GEOMETRY, PT_UPDATE_SHADING, PtAdaptiveParams,
-                          PtBvhNode, PtCounters, PtDenoiseParams, PtError, PtLight, PtMaterial, PtMesh, PtRenderParams, PtSceneDesc,
-                          PtShape)
+from .ctypes_defs import (PT_MOTION_GEOMETRY_CURRENT, PT_MOTION_GEOMETRY_PREVIOUS, PT_OK, PT_SHAPE_SPHERE, PT_TRAVERSAL_DEFAULT,
+                          PT_UPDATE_GEOMETRY, PT_UPDATE_SHADING, PtAdaptiveParams, PtBvhNode, PtCounters, PtDenoiseParams, PtError,
+                          PtGuideBuffers, PtLight, PtMaterial, PtMesh, PtMotionParams, PtRenderParams, PtSceneDesc, PtShape,
+                          PtTemporalParams)
 from .host import NODE_DTYPE  # noqa: F401  (one definition; callers also read it from here)
 
 _lib = None
@@ -21,6 +22,7 @@ EXPORTS = [
     "pt_render_accumulate", "pt_get_counters", "pt_scene_set_option", "pt_scene_get_info", "pt_debug_math",
     "pt_debug_intersect", "pt_debug_math_host", "pt_bvh_build_device", "pt_bvh_build_sweep", "pt_get_frame_times", "pt_bvh_build_sweep_device",
     "pt_debug_exact_math", "pt_render_adaptive", "pt_render_aov", "pt_denoise", "pt_denoise_host", "pt_scene_update",
+    "pt_render_guides", "pt_temporal_accumulate", "pt_temporal_accumulate_host",
 ]
 
 
@@ -46,6 +48,9 @@ def lib():
         L.pt_render_aov.argtypes = [vp, C.POINTER(PtRenderParams), vp, vp, vp, vp, C.c_int]
         L.pt_denoise.argtypes = [vp, C.POINTER(PtDenoiseParams), vp, vp, vp, vp, vp, C.c_int, vp]
         L.pt_denoise_host.argtypes = [C.POINTER(PtDenoiseParams), vp, vp, vp, vp, vp]
+        L.pt_render_guides.argtypes = [vp, C.POINTER(PtRenderParams), C.POINTER(PtMotionParams), C.POINTER(PtGuideBuffers), C.c_int]
+        L.pt_temporal_accumulate.argtypes = [vp, C.POINTER(PtTemporalParams)] + [vp] * 10 + [C.c_int, vp]
+        L.pt_temporal_accumulate_host.argtypes = [C.POINTER(PtTemporalParams)] + [vp] * 10
         L.pt_get_counters.argtypes = [vp, C.POINTER(PtCounters)]
         L.pt_get_frame_times.argtypes = [vp, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int)]
         L.pt_scene_set_option.argtypes = [vp, C.c_char_p, C.c_int64]
@@ -193,6 +198,53 @@ class DeviceScene:
         _check(lib().pt_denoise(self._h, C.byref(d), C.c_void_p(color_ptr), C.c_void_p(albedo_ptr), C.c_void_p(normal_ptr),
                                 C.c_void_p(depth_ptr), C.c_void_p(out_ptr), 1, C.c_void_p(stream or 0)))
 
+    def render_guides(self, params, prev_camera, previous_geometry=False, traversal=None, albedo=True, normal=True, depth=True,
+                      prim=True, motion=True, prev_depth=True):
+        """pt_render_guides: render_aov's buffers plus "motion" [rows, W, 2] and "prev_depth" [rows, W] float32 (those asked
+        for), as a dict of host arrays.  prev_camera: the previous frame's PtRenderParams (its camera is read) or a
+        PtMotionParams; previous_geometry: the surface points are followed into the records from before the last update."""
+        p = params.copy()
+        if traversal is not None:
+            p.traversal = traversal
+        rows, W = p.num_rows(), p.width
+        shapes = {"albedo": ((rows, W, 3), np.float32), "normal": ((rows, W, 3), np.float32), "depth": ((rows, W), np.float32),
+                  "prim": ((rows, W), np.int32), "motion": ((rows, W, 2), np.float32), "prev_depth": ((rows, W), np.float32)}
+        want = {"albedo": albedo, "normal": normal, "depth": depth, "prim": prim, "motion": motion, "prev_depth": prev_depth}
+        out = {k: np.empty(*shapes[k]) for k in shapes if want[k]}
+        g = PtGuideBuffers(*(out[k].ctypes.data if k in out else None for k in shapes))
+        m = motion_params(prev_camera, previous_geometry)
+        _check(lib().pt_render_guides(self._h, C.byref(p), C.byref(m), C.byref(g), 0))
+        return out
+
+    def render_guides_into(self, params, prev_camera, previous_geometry=False, albedo_ptr=0, normal_ptr=0, depth_ptr=0, prim_ptr=0,
+                           motion_ptr=0, prev_depth_ptr=0, traversal=None):
+        """pt_render_guides into device memory (a pointer of 0 skips that buffer).  Blocking, on the default stream."""
+        p = params.copy()
+        if traversal is not None:
+            p.traversal = traversal
+        g = PtGuideBuffers(*(ptr or None for ptr in (albedo_ptr, normal_ptr, depth_ptr, prim_ptr, motion_ptr, prev_depth_ptr)))
+        m = motion_params(prev_camera, previous_geometry)
+        _check(lib().pt_render_guides(self._h, C.byref(p), C.byref(m), C.byref(g), 1))
+
+    def temporal_accumulate(self, color, normal, motion, prev_depth, history=None, **kw):
+        """pt_temporal_accumulate on host arrays: (out_color [H, W, 3], out_len [H, W]) as new arrays.  history: None or
+        (hist_color, hist_normal, hist_depth, hist_len) of the previous frame.  Keywords: the fields of pt_temporal_params."""
+        args, t = _temporal_args(color, normal, motion, prev_depth, history, kw)
+        out_color, out_len = np.empty_like(args[0]), np.empty_like(args[3])
+        ptrs = [a.ctypes.data_as(C.c_void_p) if a is not None else None for a in args + [out_color, out_len]]
+        _check(lib().pt_temporal_accumulate(self._h, C.byref(t), *ptrs, 0, None))
+        return out_color, out_len
+
+    def temporal_accumulate_into(self, width, height, color_ptr, normal_ptr, motion_ptr, prev_depth_ptr, hist_ptrs, out_color_ptr,
+                                 out_len_ptr, stream=None, **kw):
+        """pt_temporal_accumulate on device memory, enqueued on a HIP stream without a host sync.  hist_ptrs: None or the four
+        pointers (hist_color, hist_normal, hist_depth, hist_len); out_color_ptr may be color_ptr."""
+        t = temporal_params(width, height, **kw)
+        hist = [C.c_void_p(q) for q in hist_ptrs] if hist_ptrs else [None] * 4
+        _check(lib().pt_temporal_accumulate(self._h, C.byref(t), C.c_void_p(color_ptr), C.c_void_p(normal_ptr), C.c_void_p(motion_ptr),
+                                            C.c_void_p(prev_depth_ptr), *hist, C.c_void_p(out_color_ptr), C.c_void_p(out_len_ptr), 1,
+                                            C.c_void_p(stream or 0)))
+
     def accumulate_into(self, params, dev_ptr, stream=None):
         _check(lib().pt_render_accumulate(self._h, C.byref(params), C.c_void_p(dev_ptr), C.c_void_p(stream or 0)))
 
@@ -243,6 +295,48 @@ def denoise_host(color, albedo, normal, depth, out=None, **kw):
         raise ValueError("denoise_host: out must be a contiguous [H, W, 3] float32 array")
     _check(lib().pt_denoise_host(C.byref(d), *(a.ctypes.data_as(C.c_void_p) for a in (color, albedo, normal, depth, out))))
     return out
+
+
+def motion_params(prev_camera, previous_geometry=False):
+    """pt_motion_params from the previous frame's PtRenderParams (or a PtMotionParams, whose camera is taken over)."""
+    m = PtMotionParams()
+    for f in ("origin", "top_left", "horizontal", "vertical"):
+        src = getattr(prev_camera, "prev_cam_" + f) if isinstance(prev_camera, PtMotionParams) else getattr(prev_camera, "cam_" + f)
+        getattr(m, "prev_cam_" + f)[:] = src[:]
+    m.geometry = PT_MOTION_GEOMETRY_PREVIOUS if previous_geometry else PT_MOTION_GEOMETRY_CURRENT
+    return m
+
+
+def temporal_params(width, height, max_history=0, sigma_z=0.0, normal_min=0.9, scale=0.0):
+    """pt_temporal_params; 0 = the library's default (32 frames, sigma_z 0.1, scale 1); normal_min is used as given."""
+    return PtTemporalParams(int(width), int(height), int(max_history), float(sigma_z), float(normal_min), float(scale))
+
+
+def _temporal_args(color, normal, motion, prev_depth, history, kw):
+    color, normal, motion, prev_depth = (np.ascontiguousarray(a, dtype=np.float32) for a in (color, normal, motion, prev_depth))
+    H, W = prev_depth.shape
+    if not (color.shape == normal.shape == (H, W, 3) and motion.shape == (H, W, 2)):
+        raise ValueError("temporal_accumulate: color, normal must be [H, W, 3], motion [H, W, 2] and prev_depth [H, W]")
+    hist = [None] * 4
+    if history is not None:
+        hist = [np.ascontiguousarray(a, dtype=np.float32) for a in history]
+        if [a.shape for a in hist] != [(H, W, 3), (H, W, 3), (H, W), (H, W)]:
+            raise ValueError("temporal_accumulate: history must be (color [H, W, 3], normal [H, W, 3], depth [H, W], len [H, W])")
+    return [color, normal, motion, prev_depth] + hist, temporal_params(W, H, **kw)
+
+
+def temporal_accumulate_host(color, normal, motion, prev_depth, history=None, out_color=None, **kw):
+    """pt_temporal_accumulate_host: the rule of pt_temporal_accumulate run by the host half of the library (no GPU needed).
+    Returns (out_color, out_len); out_color: an [H, W, 3] float32 array to write (it may be `color` itself), default a new one."""
+    args, t = _temporal_args(color, normal, motion, prev_depth, history, kw)
+    if out_color is None:
+        out_color = np.empty_like(args[0])
+    if out_color.dtype != np.float32 or out_color.shape != args[0].shape or not out_color.flags.c_contiguous:
+        raise ValueError("temporal_accumulate_host: out_color must be a contiguous [H, W, 3] float32 array")
+    out_len = np.empty_like(args[3])
+    ptrs = [a.ctypes.data_as(C.c_void_p) if a is not None else None for a in args + [out_color, out_len]]
+    _check(lib().pt_temporal_accumulate_host(C.byref(t), *ptrs))
+    return out_color, out_len
 
 
 def debug_math(op, x, y=None, host=False):
@@ -334,6 +428,32 @@ def edited_desc(desc, meshes=None, spheres=None, materials=None, lights=None, ba
         d2.background[:] = [float(x) for x in background]
     d2._keep = keep
     return d2
+
+
+def wobbled_desc(desc, step, meshes=None, amp=0.01):
+    """A copy of `desc` (edited_desc) whose meshes — all of them, or those listed — are displaced by a smooth per-vertex wobble,
+    amp * extent * sin(k . p + phase(step)) per axis, with the vertex normals computed anew: an animation to drive
+    DeviceScene.update with (tools/animate.py).  step 0 is not the rest pose; the rest pose is `desc` itself."""
+    from . import host
+    from .standins import mesh_arrays
+    edits = {}
+    for m in (range(desc.num_meshes) if meshes is None else meshes):
+        P, I, _ = mesh_arrays(desc, m)
+        size = max(float((P.max(axis=0) - P.min(axis=0)).max()), 1e-6)
+        ph = 0.37 * step
+        off = np.stack([np.sin(5.0 / size * P[:, 1] + ph), np.cos(4.0 / size * P[:, 2] + ph), np.sin(6.0 / size * P[:, 0] - ph)], axis=1)
+        Q = (P + np.float32(amp * size) * off.astype(np.float32)).astype(np.float32)
+        edits[m] = (Q, host.compute_normals(Q, I))
+    return edited_desc(desc, meshes=edits)
+
+
+def translated_params(params, delta):
+    """A copy of the render parameters with the camera moved by `delta` (origin and image plane alike), in fp32."""
+    q = params.copy()
+    for name in ("cam_origin", "cam_top_left"):
+        v = np.array(list(getattr(params, name)), dtype=np.float32) + np.asarray(delta, dtype=np.float32)
+        getattr(q, name)[:] = [float(x) for x in v]
+    return q
 
 
 PT_BVH_DEVICE_LBVH, PT_BVH_DEVICE_SAH = 0, 1

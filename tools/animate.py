@@ -1,0 +1,189 @@
+"""N frames of a .pts scene under a moving camera and, optionally, wobbling meshes, cleaned in image space.
+
+  python tools/animate.py SCENE.pts [--frames 8] [--size 640x480] [--spp 2] [--translate DX,DY,DZ | --orbit DEG] [--wobble]
+                          [--denoise] [--reference-spp N] [--out PREFIX] [--time]
+
+Per frame: pt_render at --spp, pt_render_guides against the previous frame's camera (and, with --wobble, the previous
+geometry: every mesh gets device.wobbled_desc's per-vertex wobble through DeviceScene.update), pt_temporal_accumulate, and with
+--denoise pt_denoise on the accumulated colour.  Writes PREFIX_NNN_noisy.ppm / _accumulated.ppm / _denoised.ppm, prints the
+HIP-event time of every stage per frame and their medians, and with --reference-spp the RMSE of each stage's image against a
+pt_render of that many samples on the same geometry.  --translate is in units of the median first-hit distance of frame 0 per
+frame (default 0.02,0.008,-0.013); --orbit turns the camera about its look-at point by that many degrees per frame instead.
+--time: after the animation, each stage again on the last frame's inputs, warm, in windows of at least 0.5 s, with
+pt_render_aov and one pt_denoise iteration as yardsticks and the bytes pt_temporal_accumulate must move."""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+from pathtracer_cuda_interactive_amd import PT_BVH_SORT_REFERENCE, HostScene, host  # noqa: E402
+from pathtracer_cuda_interactive_amd import device as dev  # noqa: E402
+
+HBM_BYTES_PER_S = 6.29e12          # measured float4 copy rate of the MI355X
+TEMPORAL = dict(max_history=0, sigma_z=0.0, normal_min=0.9)      # the library's defaults; normal_min has none
+
+
+def timed(fn, window_s=0.5):
+    """Mean device time of fn() in ms: warm, then batches between two events until the window is filled."""
+    for _ in range(3):
+        fn()
+    torch.cuda.synchronize()
+    total_ms, n, batch = 0.0, 0, 8
+    while total_ms < window_s * 1e3:
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(batch):
+            fn()
+        e1.record()
+        e1.synchronize()
+        total_ms += e0.elapsed_time(e1)
+        n += batch
+        batch = min(batch * 2, 4096)
+    return total_ms / n
+
+
+def once(fn):
+    """Device time of one fn() in ms between two events on the current stream."""
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    fn()
+    e1.record()
+    e1.synchronize()
+    return e0.elapsed_time(e1)
+
+
+def orbited_params(hs, w, h, spp, degrees):
+    """Render parameters of the scene's camera turned about its look-at point, around its up vector."""
+    cam = hs.camera
+    at, up = np.array(cam.lookat[:], np.float64), np.array(cam.up[:], np.float64)
+    up /= np.linalg.norm(up)
+    v = np.array(cam.lookfrom[:], np.float64) - at
+    a = np.radians(degrees)
+    v = v * np.cos(a) + np.cross(up, v) * np.sin(a) + up * (up @ v) * (1 - np.cos(a))
+    p = hs.render_params(w, h, spp)
+    cam.lookfrom[:] = [float(x) for x in at + v]
+    rd = host.camera_ray_data(cam, w, h)
+    for name, row in zip(("cam_origin", "cam_top_left", "cam_horizontal", "cam_vertical"), rd):
+        getattr(p, name)[:] = [float(x) for x in row]
+    return p
+
+
+def rmse(a, b):
+    return float(np.sqrt(np.mean((a.astype(np.float64) - b.astype(np.float64)) ** 2)))
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("scene")
+    ap.add_argument("--frames", type=int, default=8)
+    ap.add_argument("--size", default="640x480")
+    ap.add_argument("--spp", type=int, default=2)
+    ap.add_argument("--translate", default="0.02,0.008,-0.013")
+    ap.add_argument("--orbit", type=float, default=0.0)
+    ap.add_argument("--wobble", action="store_true")
+    ap.add_argument("--denoise", action="store_true")
+    ap.add_argument("--reference-spp", type=int, default=0)
+    ap.add_argument("--out", default="")
+    ap.add_argument("--time", action="store_true")
+    a = ap.parse_args()
+    w, h = (int(v) for v in a.size.split("x"))
+    hs = HostScene.load(a.scene)
+    d0 = hs.finalize(PT_BVH_SORT_REFERENCE)
+    ds = dev.DeviceScene(d0)
+    ref = dev.DeviceScene(d0) if a.reference_spp else None
+    stream = torch.cuda.current_stream().cuda_stream
+    f3 = lambda: torch.empty((h, w, 3), device="cuda")           # noqa: E731
+    f1 = lambda: torch.empty((h, w), device="cuda")              # noqa: E731
+    color, albedo, denoised = f3(), f3(), f3()
+    motion, prev_depth = torch.empty((h, w, 2), device="cuda"), f1()
+    # what a frame leaves for the next one, ping-ponged: accumulated colour, normal, depth, history length
+    sets = [dict(out=f3(), normal=f3(), depth=f1(), length=f1()) for _ in range(2)]
+    p0 = hs.render_params(w, h, a.spp)
+    ds.render_aov_into(p0, 0, 0, sets[0]["depth"].data_ptr(), 0)
+    z = sets[0]["depth"]
+    step = np.array([float(v) for v in a.translate.split(",")]) * float(z[z > 0].median()) if (z > 0).any() else np.zeros(3)
+    stages = ["render", "guides", "accumulate"] + (["denoise"] if a.denoise else [])
+    times = {s: [] for s in stages}
+    errors = {s: [] for s in ("noisy", "accumulated", "denoised")}
+    p_prev = None
+    for k in range(a.frames):
+        p = orbited_params(hs, w, h, a.spp, a.orbit * k) if a.orbit else dev.translated_params(p0, step * k)
+        p.seed = 1984 + k
+        cur, old = sets[k & 1], sets[(k + 1) & 1]
+        update_ms = 0.0
+        if a.wobble and k:
+            ds.update(dev.wobbled_desc(d0, k))
+            update_ms = ds.info("update_us0") / 1e3
+        times["render"].append(once(lambda: ds.render_into(p, color.data_ptr(), stream)))
+        times["guides"].append(once(lambda: ds.render_guides_into(
+            p, p_prev or p, previous_geometry=True, albedo_ptr=albedo.data_ptr(), normal_ptr=cur["normal"].data_ptr(),
+            depth_ptr=cur["depth"].data_ptr(), motion_ptr=motion.data_ptr(), prev_depth_ptr=prev_depth.data_ptr())))
+        hist = [old[n].data_ptr() for n in ("out", "normal", "depth", "length")] if k else None
+        times["accumulate"].append(once(lambda: ds.temporal_accumulate_into(
+            w, h, color.data_ptr(), cur["normal"].data_ptr(), motion.data_ptr(), prev_depth.data_ptr(), hist,
+            cur["out"].data_ptr(), cur["length"].data_ptr(), stream, **TEMPORAL)))
+        if a.denoise:
+            times["denoise"].append(once(lambda: ds.denoise_into(w, h, cur["out"].data_ptr(), albedo.data_ptr(), cur["normal"].data_ptr(),
+                                                                 cur["depth"].data_ptr(), denoised.data_ptr(), stream)))
+        torch.cuda.synchronize()
+        images = {"noisy": color, "accumulated": cur["out"]}
+        if a.denoise:
+            images["denoised"] = denoised
+        line = f"frame {k:3d}: " + "  ".join(f"{s} {times[s][-1]:7.3f} ms" for s in stages)
+        if a.wobble and k:
+            line += f"  (update {update_ms:.3f} ms)"
+        valid = prev_depth > 0
+        line += f"  history: {float((cur['length'][valid] > 1).float().mean()) if valid.any() else 0.0:.3f} of the valid pixels, " \
+                f"mean length {float(cur['length'].mean()):.2f}"
+        if ref is not None:
+            if a.wobble and k:
+                ref.update(dev.wobbled_desc(d0, k))
+            q = p.copy()
+            q.spp, q.seed = a.reference_spp, 7
+            truth = ref.render(q)
+            for name, img in images.items():
+                errors[name].append(rmse(img.cpu().numpy(), truth))
+            line += "  RMSE " + "  ".join(f"{name} {errors[name][-1]:.5f}" for name in images)
+        print(line, flush=True)
+        if a.out:
+            for name, img in images.items():
+                host.write_image(f"{a.out}_{k:03d}_{name}.ppm", img.cpu().numpy())
+        p_prev = p
+    summary = {"scene": os.path.basename(a.scene), "size": a.size, "spp": a.spp, "frames": a.frames,
+               "median_ms": {s: float(np.median(times[s][1:] or times[s])) for s in stages}}
+    if ref is not None:
+        summary["rmse_last_frame"] = {n: e[-1] for n, e in errors.items() if e}
+    if a.time:
+        cur, old = sets[(a.frames - 1) & 1], sets[a.frames & 1]
+        hist = [old[n].data_ptr() for n in ("out", "normal", "depth", "length")]
+        scratch = f3()
+        t = {}
+        t["pt_render"] = timed(lambda: ds.render_into(p, color.data_ptr(), stream))
+        t["pt_render_aov (4 buffers)"] = timed(lambda: ds.render_aov_into(p, albedo.data_ptr(), scratch.data_ptr(), prev_depth.data_ptr(), 0))
+        t["pt_render_guides (4 buffers + motion)"] = timed(lambda: ds.render_guides_into(
+            p, p_prev, previous_geometry=True, albedo_ptr=albedo.data_ptr(), normal_ptr=scratch.data_ptr(), depth_ptr=cur["depth"].data_ptr(),
+            motion_ptr=motion.data_ptr(), prev_depth_ptr=prev_depth.data_ptr()))
+        t["pt_temporal_accumulate"] = timed(lambda: ds.temporal_accumulate_into(
+            w, h, color.data_ptr(), cur["normal"].data_ptr(), motion.data_ptr(), prev_depth.data_ptr(), hist, scratch.data_ptr(),
+            cur["length"].data_ptr(), stream, **TEMPORAL))
+        t["pt_denoise, 1 iteration"] = timed(lambda: ds.denoise_into(w, h, color.data_ptr(), albedo.data_ptr(), cur["normal"].data_ptr(),
+                                                                     cur["depth"].data_ptr(), scratch.data_ptr(), stream, iterations=1))
+        # per pixel: colour, normal, motion, prev_depth in (36 B), one history pixel's colour, normal, depth, length in where
+        # neighbouring lanes share their taps (32 B), colour and length out (16 B)
+        moved = w * h * 84
+        summary["timed_ms"] = t
+        summary["accumulate_bytes"] = moved
+        summary["accumulate_hbm_bound_us"] = moved / HBM_BYTES_PER_S * 1e6
+    print(json.dumps(summary))
+    ds.close()
+    if ref is not None:
+        ref.close()
+
+
+if __name__ == "__main__":
+    main()

@@ -492,7 +492,8 @@ int pt_bvh_build_sweep_device(const pt_scene_desc* desc, pt_bvh_node* out_nodes,
  *     bits  4-5  RES (family 1: LDS_SCENE)                                      bit  11  LIST
  *     bit   6    PRUNE       bit 7  STATS       bits 8-9  SPEC                    bit  12  POSTPONE
  *     bits 16-23 THRESH      bits 24-39 INNER, 16-bit two's complement          bits 40-43 MINW
- *   a field the family's template does not have is 0), "frames_in_flight", "sweep_on_device" (the internal tree was built on the GPU),
+ *   a field the family's template does not have is 0), "path_bank" (1 = that kernel handed out path starts from a per-wave
+ * register bank filled 64 at a time: trace_kernel_v2 on LDS-resident scenes of triangles with diffuse materials), "frames_in_flight", "sweep_on_device" (the internal tree was built on the GPU),
  * "create_us0".."create_us6" (wall microseconds of pt_scene_create: total, primitive records, caller's tree checked and re-laid,
  * internal tree built, ... re-laid, uploads + probe, tie tables). */
 int pt_scene_set_option(pt_scene* scene, const char* key, int64_t value);

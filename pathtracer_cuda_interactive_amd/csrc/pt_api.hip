@@ -259,7 +259,7 @@ struct pt_scene {
     // wall time of pt_scene_create's stages, microseconds: [0] total [1] primitive records [2] caller's tree checked and re-laid
     // [3] internal tree built [4] ... re-laid [5] uploads + probe [6] tie tables; built_on_device: the sweep ran on the GPU
     int64_t create_us[7] = {0, 0, 0, 0, 0, 0, 0}, sweep_on_device = 0;
-    int64_t info_grid = 0, info_lds_bytes = 0, info_lds_scene = 0, info_passes = 0, info_occupancy = 0, info_blocks_per_cu = 0, info_debug_reruns = 0, fast_cost_permille = 0, info_kernel = 0, info_trace_variant = 0;
+    int64_t info_grid = 0, info_lds_bytes = 0, info_lds_scene = 0, info_passes = 0, info_occupancy = 0, info_blocks_per_cu = 0, info_debug_reruns = 0, fast_cost_permille = 0, info_kernel = 0, info_trace_variant = 0, info_path_bank = 0;
     struct PassEvents { hipEvent_t t0, t1, r0, r1; };            // trace begin, trace end (on the trace kernel's stream); resolve begin, end (caller's)
     // HIP events of the last `opt_timing_frames` render calls (a ring; default 1): a caller that enqueues frame after frame
     // without a host sync in between — bench.py's timed loop — reads every frame's kernel time afterwards (pt_get_frame_times)
@@ -875,6 +875,7 @@ constexpr int64_t trace_variant(int family, int res, bool prune, bool stats, int
 struct TracePick {
     TraceFn fn;
     int64_t variant;
+    int bank = 0;        // info "path_bank": the kernel hands out path starts from a register bank (pt_kernels.h: path_bank_on)
 };
 template <bool LDS_SCENE, bool PRUNE, bool STATS, bool LIST = false>
 TracePick v1k() {
@@ -884,7 +885,7 @@ template <int RES, bool PRUNE, bool STATS, int THRESH, int INNER, int MINW, int 
 TracePick v2k() {
     static_assert(INNER >= -32768 && INNER <= 32767 && THRESH >= 0 && THRESH < 256 && MINW >= 0 && MINW < 16, "trace_variant fields");
     return {trace_kernel_v2<RES, PRUNE, STATS, THRESH, INNER, MINW, SPEC, NEE, LIST>,
-            trace_variant(2, RES, PRUNE, STATS, SPEC, NEE, LIST, false, THRESH, INNER, MINW)};
+            trace_variant(2, RES, PRUNE, STATS, SPEC, NEE, LIST, false, THRESH, INNER, MINW), path_bank_on(RES, SPEC, NEE, LIST, THRESH, INNER)};
 }
 
 TracePick pick_kernel_v1(bool lds, bool prune, bool stats) {
@@ -1190,6 +1191,7 @@ int launch_render(pt_scene* S, const pt_render_params* p, float* out_dev, int mo
     const size_t pass_base = frec.passes;               // passes of earlier adaptive rounds of this frame
     if (rows.count == 0) {           // nothing to trace: the frame's counters read zero
         S->info_trace_variant = 0;
+        S->info_path_bank = 0;
         if (slot.used && slot.free_stream != stream) HIP_TRY(hipStreamWaitEvent(stream, slot.free_ev, 0));
         HIP_TRY(hipMemsetAsync(slot.ctl.p, 0, (kWorkWords + kTimelineBase) * sizeof(unsigned long long), stream));
         HIP_TRY(hipEventRecord(slot.free_ev, stream));
@@ -1248,6 +1250,7 @@ int launch_render(pt_scene* S, const pt_render_params* p, float* out_dev, int mo
     TraceFnQ fnq = nullptr;
     TraceFn fn = nullptr;
     int64_t variant = 0;
+    int path_bank = 0;
     if (use_q) {
         qp = make_plan_q(S, lp, which, res);
         if (lp.total > S->lds_per_block_max) return fail(PT_ERR_DEVICE, "LDS plan exceeds the per-block limit");
@@ -1257,7 +1260,7 @@ int launch_render(pt_scene* S, const pt_render_params* p, float* out_dev, int mo
         const TracePick pk = listed ? pick_kernel_list(S, res, traversal == PT_TRAVERSAL_PRUNED, S->opt_stats != 0, which == 1, nee)
                            : nee ? pick_kernel_nee(res, S->opt_stats != 0, (S->tri_only && S->diffuse_only && S->opt_specialize) ? 2 : 0)
                                  : pick_kernel(S, res, traversal == PT_TRAVERSAL_PRUNED, S->opt_stats != 0, which == 1);
-        fn = pk.fn; variant = pk.variant;
+        fn = pk.fn; variant = pk.variant; path_bank = pk.bank;
         if (!fn) return fail(PT_ERR_INVALID_ARG, "no kernel variant compiled for these v2_thresh / v2_inner options");
     }
     const void* fn_any = use_q ? reinterpret_cast<const void*>(fnq) : reinterpret_cast<const void*>(fn);
@@ -1285,6 +1288,7 @@ int launch_render(pt_scene* S, const pt_render_params* p, float* out_dev, int mo
     if (own_stream && S->opt_blocks_per_cu <= 0) bpc = std::max(1, in_flight >= 3 ? bpc / 2 : bpc - 1);
     S->info_kernel = use_q ? 3 : S->opt_kernel == 1 ? 1 : 2;
     S->info_trace_variant = variant;
+    S->info_path_bank = path_bank;
     S->info_occupancy = occ;
     S->info_blocks_per_cu = bpc;
     S->info_lds_bytes = lp.total;
@@ -2044,6 +2048,7 @@ int pt_scene_get_info(pt_scene* S, const char* key, int64_t* value) {
     else if (k.rfind("update_us", 0) == 0 && k.size() == 10 && k[9] >= '0' && k[9] <= '3') *value = S->update_us[k[9] - '0'];
     else if (k == "kernel") *value = S->info_kernel;                      // the kernel the last render ran on (1, 2 or 3)
     else if (k == "trace_variant") *value = S->info_trace_variant;        // ... and its template arguments (include/pt_api.h)
+    else if (k == "path_bank") *value = S->info_path_bank;                // ... which handed out path starts from a register bank (1) or not
     else if (k == "block_threads") *value = S->info_kernel == 3 ? kQBlock : kBlock;
     else if (k == "frames_in_flight") *value = S->opt_frames_in_flight;
     else if (k.rfind("qdiag", 0) == 0 && k.size() >= 6 && k.size() <= 7 && k.find_first_not_of("0123456789", 5) == std::string::npos &&

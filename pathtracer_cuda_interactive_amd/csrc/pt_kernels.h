@@ -13,6 +13,7 @@
 
 #include "pt_layout.h"
 #include "pt_math.h"
+#include "pt_path_bank.h"
 #include "pt_temporal.h"
 #include "pt_trace.h"
 
@@ -91,10 +92,18 @@ struct PathStart {
     uint32_t sample_index;   // slot in the sample-major scratch buffer
 };
 
-// main.cu:32-44 for region-local work item `item` of `region`: (sample, pixel) -> PCG stream, jitter, primary ray.
+// What a work item stands for: pixel, PCG stream and slot in the scratch buffer.  Pure integer arithmetic on the item number
+// and launch constants, shared by start_path and by the hand-out of the path bank (trace_kernel_v2).
+struct PathIndex {
+    int col, j;              // image column and row
+    int32_t img_width;
+    uint64_t stream;         // PCG stream of the (pixel, sample)
+    uint32_t sample_index;   // slot in the sample-major scratch buffer
+};
+
 // LIST: an adaptive round after the first (RenderDev::list), a compile-time variant so that plain frames keep their code.
 template <bool LIST = false>
-__device__ __forceinline__ PathStart start_path(const RenderDev& rp, uint32_t region, uint32_t item) {
+__device__ __forceinline__ PathIndex path_index(const RenderDev& rp, uint32_t region, uint32_t item) {
     const uint32_t npix_r = region_rows(rp, region) * (uint32_t)rp.width;
     uint32_t s_local, rr;
     int i;
@@ -123,16 +132,70 @@ __device__ __forceinline__ PathStart start_path(const RenderDev& rp, uint32_t re
     const int32_t img_width = LIST ? rp.img_width : rp.width;
     const int j = rp.row_begin + (int)img_row * rp.row_step;
     const uint64_t pixel_index = (uint64_t)j * (uint64_t)img_width + (uint64_t)col;
-    const uint64_t stream = pixel_index * (uint64_t)rp.stream_stride + (uint64_t)(rp.sample_base + (int)s_local);
+    PathIndex px;
+    px.col = col;
+    px.j = j;
+    px.img_width = img_width;
+    px.stream = pixel_index * (uint64_t)rp.stream_stride + (uint64_t)(rp.sample_base + (int)s_local);
+    px.sample_index = s_local * rp.npix + local_row * (uint32_t)rp.width + (uint32_t)i;
+    return px;
+}
+
+// main.cu:32-44 for region-local work item `item` of `region`: (sample, pixel) -> PCG stream, jitter, primary ray.
+template <bool LIST = false>
+__device__ __forceinline__ PathStart start_path(const RenderDev& rp, uint32_t region, uint32_t item) {
+    const PathIndex px = path_index<LIST>(rp, region, item);
     PathStart ps;
-    ps.rng = ptm::pcg_init(stream, rp.seed);
+    ps.rng = ptm::pcg_init(px.stream, rp.seed);
     const float ru = ptm::pcg_float(ps.rng);
-    const float u = ((float)col + ru) / (float)img_width;
+    const float u = ((float)px.col + ru) / (float)px.img_width;
     const float rv = ptm::pcg_float(ps.rng);
-    const float v = ((float)j + rv) / (float)rp.height;
+    const float v = ((float)px.j + rv) / (float)rp.height;
     ps.ray = ptd::primary_ray(rp, u, v);
-    ps.sample_index = s_local * rp.npix + local_row * (uint32_t)rp.width + (uint32_t)i;
+    ps.sample_index = px.sample_index;
     return ps;
+}
+
+// The launch constants read again from the kernel-argument segment, where the runtime put them.  The bank's generation step
+// uses this copy: it runs once per 64 paths, and what only it needs of RenderDev (three camera vectors, height, seed, ...)
+// then no longer occupies scalar registers across the whole trace loop, where they overflowed into lanes of a VGPR and were
+// read back inside the traversal burst.  The empty asm keeps the loads from being hoisted out of the loop again.
+// Both forms of the copy load the same bytes.  WORDS exists for the register allocator alone: which form ends without
+// a stack slot differs between the STATS builds (word by word) and the others (block copy); see the ScratchSize of the
+// instantiations in the assembly metadata before changing it.
+struct TraceKernelArgs {             // the parameter list of the trace kernels, for offsetof
+    SceneDev scn; RenderDev rp; LdsPlan lp; float4* samples; uint32_t* work_counter; unsigned long long* counters;
+};
+template <bool WORDS>
+__device__ __forceinline__ RenderDev reload_render_args() {
+    typedef const __attribute__((address_space(4))) unsigned char* KernargPtr;
+    KernargPtr p = (KernargPtr)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(p));
+    if (WORDS) {
+        struct Words { uint32_t w[sizeof(RenderDev) / 4]; };
+        typedef const __attribute__((address_space(4))) uint32_t* WordPtr;
+        WordPtr q = (WordPtr)(p + offsetof(TraceKernelArgs, rp));
+        Words v;
+#pragma unroll
+        for (uint32_t i = 0; i < sizeof(RenderDev) / 4; i++) v.w[i] = q[i];
+        return __builtin_bit_cast(RenderDev, v);
+    }
+    RenderDev r;
+    __builtin_memcpy(&r, (const void*)(p + offsetof(TraceKernelArgs, rp)), sizeof(RenderDev));
+    return r;
+}
+
+// Path bank (pt_path_bank.h): trace_kernel_v2 instantiations on LDS-resident scenes of triangles with diffuse materials
+// generate path starts 64 at a time at full wave width and hand them out in the scheduler phase.  -DPT_PATH_BANK=0 builds
+// every kernel with the per-phase start_path (A/B library).
+#ifndef PT_PATH_BANK
+#define PT_PATH_BANK 1
+#endif
+// Only the default schedule of LDS-resident scenes (THRESH 40, burst 162: pt_api.hip, pick_kernel_v2) takes the bank: every
+// such instantiation keeps ScratchSize 0 at its register cap with the five bank registers, while some of the other burst
+// shapes, compiled in for tuning runs, would start to spill; those keep the per-phase start_path.
+constexpr bool path_bank_on(int res, int spec, bool nee, bool list, int thresh, int inner) {
+    return PT_PATH_BANK && (res == 1 || res == 2) && spec == 2 && !nee && !list && thresh == 40 && inner == 162;
 }
 
 __device__ __forceinline__ void stage_to_lds(void* dst, const void* src, uint32_t bytes) {
@@ -349,6 +412,13 @@ __global__ __launch_bounds__(kBlock, (kBlock > 256 ? 1 : MINW)) void trace_kerne
 
     WorkFeed feed;
     feed_init(feed, rp);
+    // path bank: slot `lane` of the wave's bank = direction of the primary ray and PCG state after the two jitter draws of
+    // work item bank_item(feed.cur, lane); everything else of a path start follows from the item number (path_index)
+    constexpr bool BANK = path_bank_on(RES, SPEC, NEE, LIST, THRESH, INNER);
+    PathBank bank;
+    bank_init(bank);
+    float bank_dx = 0.0f, bank_dy = 0.0f, bank_dz = 0.0f;
+    uint32_t bank_lo = 0, bank_hi = 0;
     bool alive = false;
     ptd::Ray ray;
     ray.org = ptm::mk(0, 0, 0); ray.dir = ptm::mk(0, 0, 1); ray.tnear = 0; ray.tfar = 0;
@@ -390,7 +460,10 @@ __global__ __launch_bounds__(kBlock, (kBlock > 256 ? 1 : MINW)) void trace_kerne
         const bool idle = tv.cur == DONE && (!POSTPONE || pend == DONE);
         const unsigned long long idle_mask = __ballot(idle);
         if (STATS) dg_iter++;
-        const bool work_left = !(feed.exhausted && feed.cur >= feed.end);        // wave-uniform
+        // wave-uniform.  With a path bank every item the wave reserved is in [feed.cur, feed.end) or in the bank, and only this
+        // wave hands out what its bank holds: work is left while either holds an item, so the loop cannot end (n_pend == 0
+        // below) with path starts still banked
+        const bool work_left = BANK ? bank_work_left(bank, feed.exhausted, feed.cur, feed.end) : !(feed.exhausted && feed.cur >= feed.end);
         if (STATS && !work_left && tl_dry == 0) tl_dry = wall_clock64();
         const int n_pend = __popcll(__ballot(idle && (alive || work_left)));
         // drain (no work left to refill with): fewer than THRESH lanes may be alive at all.  Scenes in global memory serve
@@ -441,7 +514,51 @@ __global__ __launch_bounds__(kBlock, (kBlock > 256 ? 1 : MINW)) void trace_kerne
             }
             // (2) refill dead lanes (main.cu:32-44)
             const unsigned long long need = __ballot(idle && !alive);
-            if (need) {
+            if (BANK) {
+                // Dead lanes take path starts out of the wave's bank; when it is empty the whole wave (the lanes that still
+                // traverse included: the bank registers are theirs too) generates the next 64.  At most two rounds: what is
+                // left of the bank, then a fresh one.  Lanes still without a path wait for the next phase, as they do below
+                // when a chunk ends.
+                unsigned long long want = need;
+#pragma nounroll
+                for (int round = 0; round < 2 && want; round++) {
+                    if (bank.left == 0) {
+                        feed_reserve(feed, rp, work_counter, lane);
+                        if (feed.cur >= feed.end) break;                 // every band exhausted
+                        bank_fill(bank, feed.cur, feed.end);
+                        // after a short fill (the tail of a band) the first slots hold the arithmetic of items that do not
+                        // exist (no memory is read for it): they are never handed out
+                        const RenderDev rg = reload_render_args<STATS>();
+                        const PathStart ps = start_path<LIST>(rg, feed.region, bank_item(feed.cur, (uint32_t)lane));
+                        bank_dx = ps.ray.dir.x; bank_dy = ps.ray.dir.y; bank_dz = ps.ray.dir.z;
+                        bank_lo = (uint32_t)ps.rng.state; bank_hi = (uint32_t)(ps.rng.state >> 32);
+                    }
+                    uint32_t first;
+                    const uint32_t k = bank_take(bank, (uint32_t)__popcll(want), first);
+                    const uint32_t rank = lane_rank(want);
+                    const bool take = idle && !alive && rank < k;
+                    const int src = take ? (int)(first + rank) : lane;
+                    // the permutes run with every lane active (a switched-off lane gives a permute nothing to read)
+                    const float dx = __shfl(bank_dx, src, 64), dy = __shfl(bank_dy, src, 64), dz = __shfl(bank_dz, src, 64);
+                    const uint32_t lo = __shfl(bank_lo, src, 64), hi = __shfl(bank_hi, src, 64);
+                    if (take) {
+                        const PathIndex px = path_index<LIST>(rp, feed.region, bank_item(feed.cur, first + rank));
+                        ray.org = ptm::mk(rp.cam_origin[0], rp.cam_origin[1], rp.cam_origin[2]);
+                        ray.dir = ptm::mk(dx, dy, dz);
+                        ray.tnear = 0.0f;
+                        ray.tfar = __builtin_inff();
+                        rng.state = (uint64_t)hi << 32 | lo;
+                        rng.inc = (px.stream << 1u) | 1u;
+                        my_w = px.sample_index;
+                        L = ptm::mk(0, 0, 0);
+                        T = ptm::mk(1, 1, 1);
+                        depth = 0;
+                        alive = true;
+                        n_paths++;
+                    }
+                    want = __ballot(idle && !alive);
+                }
+            } else if (need) {
                 feed_reserve(feed, rp, work_counter, lane);
                 const uint32_t avail = feed.end - feed.cur;
                 if (avail) {
@@ -488,7 +605,7 @@ __global__ __launch_bounds__(kBlock, (kBlock > 256 ? 1 : MINW)) void trace_kerne
                         if (n_in) { dg_in++; dg_in_lanes += (unsigned)n_in; dg_wait += (unsigned)__popcll(__ballot(tv.cur == DONE && pend == DONE)); }
                     }
                     if (tv.cur >= 0) {
-                        if (STATS) st.nodes++;
+                        if (STATS && !BANK) st.nodes++;
                         ptd::inner_step<PRUNE, RES == 2, STK, (RES == 3 ? 1 : 0)>(sv, ray.org, tv, stk);
                         if (tv.cur < 0 && tv.cur != DONE && pend == DONE) {       // a leaf: set it aside, take the next entry
                             pend = tv.cur;
@@ -504,7 +621,7 @@ __global__ __launch_bounds__(kBlock, (kBlock > 256 ? 1 : MINW)) void trace_kerne
                         if (n_lf) { dg_lf++; dg_lf_lanes += (unsigned)n_lf; dg_wait += (unsigned)__popcll(__ballot(tv.cur == DONE && pend == DONE)); }
                     }
                     if (pend != DONE) {
-                        if (STATS) st.leaves++;
+                        if (STATS && !BANK) st.leaves++;
                         ptd::leaf_test<TRI_ONLY>(sv, ray, tv, pend, fbk);
                         pend = DONE;
                         if (NEE && in_shadow && tv.best.prim >= 0) { tv.cur = DONE; tv.sp = 1; }      // occluded: done
@@ -530,11 +647,11 @@ __global__ __launch_bounds__(kBlock, (kBlock > 256 ? 1 : MINW)) void trace_kerne
                 }
                 if (n_in >= n_lf) {
                     if (at_inner) {
-                        if (STATS) st.nodes++;
+                        if (STATS && !BANK) st.nodes++;
                         ptd::inner_step<PRUNE, RES == 2, STK, (RES == 3 ? 1 : 0)>(sv, ray.org, tv, stk);
                     }
                 } else if (at_leaf) {
-                    if (STATS) st.leaves++;
+                    if (STATS && !BANK) st.leaves++;
                     ptd::leaf_step<STK, TRI_ONLY, NEE>(sv, ray, tv, stk, NEE && in_shadow, fbk);
                 }
             }
@@ -553,7 +670,7 @@ __global__ __launch_bounds__(kBlock, (kBlock > 256 ? 1 : MINW)) void trace_kerne
                         if (n_in) { dg_in++; dg_in_lanes += (unsigned)n_in; dg_wait += (unsigned)__popcll(__ballot(tv.cur == DONE)); }
                     }
                     if (tv.cur >= 0) {
-                        if (STATS) st.nodes++;
+                        if (STATS && !BANK) st.nodes++;
                         ptd::inner_step<PRUNE, RES == 2, STK, (RES == 3 ? 1 : 0)>(sv, ray.org, tv, stk);
                     }
                 }
@@ -564,12 +681,19 @@ __global__ __launch_bounds__(kBlock, (kBlock > 256 ? 1 : MINW)) void trace_kerne
                         if (n_lf) { dg_lf++; dg_lf_lanes += (unsigned)n_lf; dg_wait += (unsigned)__popcll(__ballot(tv.cur == DONE)); }
                     }
                     if (tv.cur < 0 && tv.cur != DONE) {
-                        if (STATS) st.leaves++;
+                        if (STATS && !BANK) st.leaves++;
                         ptd::leaf_step<STK, TRI_ONLY, NEE>(sv, ray, tv, stk, NEE && in_shadow, fbk);
                     }
                 }
             }
         }
+    }
+    if (BANK && STATS) {
+        // the lanes active in inner and leaf steps ARE the node visits and leaf tests (every burst shape adds to dg_in_lanes /
+        // dg_lf_lanes exactly the lanes that would count themselves); the bank kernels have no registers to spare for
+        // per-lane copies of the two sums.  (A wave's sums fit 32 bits like a lane's: a launch has at most 2^30 work items.)
+        st.nodes = lane == 0 ? (uint32_t)dg_in_lanes : 0u;
+        st.leaves = lane == 0 ? (uint32_t)dg_lf_lanes : 0u;
     }
     flush_counters<STATS>(counters, lane, n_paths, n_segs, st);
     const unsigned long long redo_sum = STATS ? wave_sum(n_redo) : 0ull;

@@ -403,6 +403,76 @@ int pt_temporal_accumulate_host(const pt_temporal_params* t, const float* color,
                                 const float* prev_depth, const float* hist_color, const float* hist_normal,
                                 const float* hist_depth, const float* hist_len, float* out_color, float* out_len);
 
+/* Temporal luminance moments and a variance-guided à-trous filter — an EXTENSION: off unless called, never part of a parity or
+ * roofline number, no other entry point's output changes by a bit.  DESIGN.md §20.
+ *   pt_temporal_accumulate_moments is pt_temporal_accumulate with the first and second moment of the pixel's luminance carried
+ *   along the same reprojection, in one launch; pt_denoise_variance is pt_denoise with a per-pixel, per-iteration luminance
+ *   tolerance derived from those moments and propagated through the iterations.  lum, dot, filterable, a', x_0, wn, wz and h are
+ *   pt_denoise's definitions above; fp32, operations in the order written, no contraction, IEEE division. */
+typedef struct pt_temporal_io {   /* on_device != 0: all are device pointers on the scene's GPU */
+    const float *color, *albedo, *normal, *motion, *prev_depth;                   /* this frame; albedo [H, W, 3] */
+    const float *hist_color, *hist_normal, *hist_depth, *hist_len, *hist_moments; /* all five NULL = no history; some but not
+                                                                                     all: PT_ERR_INVALID_ARG */
+    float *out_color, *out_len, *out_moments;                                     /* moments: [H, W, 2] */
+} pt_temporal_io;                 /* 104 bytes */
+
+/* Buffers, call forms, staging and errors as pt_temporal_accumulate; albedo_floor: 0 -> 0.01, else > 0 and finite.  A NULL t or
+ * io, a NULL pointer among this frame's five or the three outputs: PT_ERR_INVALID_ARG.  out_color may be color; out_color ==
+ * hist_color, out_len == hist_len or out_moments == hist_moments: PT_ERR_INVALID_ARG.  After a call, (out_color, normal, depth,
+ * out_len, out_moments) are the next call's hist_*.
+ *   The rule per pixel p.  out_color and out_len are pt_temporal_accumulate's bit for bit: steps 1-8, the taps, the skip tests
+ *   and b are the same.  With c = color[p] * scale:
+ *     l = lum(c.r / a'.r, c.g / a'.g, c.b / a'.b) if filterable(albedo[p]), lum(c) otherwise;  m_c = (l, l * l)
+ *   — the moments live in the demodulated space in which the spatial filter works.
+ *   Fallback: out_moments = m_c.
+ *   7. A kept tap, after lsum: msum += hist_moments[q] * b per component.
+ *   8. wsum > 0: mh = msum * r, out_moments = mh + (m_c - mh) * (1.0f / n) per component, with step 8's r and n. */
+int pt_temporal_accumulate_moments(pt_scene* scene, const pt_temporal_params* t, float albedo_floor, const pt_temporal_io* io,
+                                   int on_device, void* hip_stream);
+/* The same per-pixel source (csrc/pt_temporal.h) compiled for the HOST: needs no GPU and no scene. */
+int pt_temporal_accumulate_moments_host(const pt_temporal_params* t, float albedo_floor, const pt_temporal_io* io);
+
+typedef struct pt_vdenoise_params {
+    int32_t width, height;        /* full frame; the filter works on whole frames only                      */
+    int32_t iterations;           /* 0 -> 5; else 1..8; iteration k uses tap spacing 2^k                    */
+    int32_t normal_power_log2;    /* 0..10, used as given, as in pt_denoise_params                          */
+    float   sigma_z;              /* 0 -> 0.05; else > 0, finite                                            */
+    float   sigma_l;              /* 0 -> 4; else > 0, finite: luminance tolerance in standard deviations   */
+    float   scale, albedo_floor;  /* as in pt_denoise_params                                                */
+    int32_t min_history;          /* 0 -> 4; else 1..65536: a shorter history takes the spatial variance estimate */
+    float   var_floor;            /* 0 -> 1e-10; else > 0, finite: added to the tolerance, keeps it positive */
+} pt_vdenoise_params;             /* 40 bytes */
+
+/* color, albedo, normal [H, W, 3], depth, hist_len [H, W], moments [H, W, 2] -> out [H, W, 3], out_variance [H, W] (may be NULL);
+ * out may be color.  moments and hist_len are pt_temporal_accumulate_moments' out_moments and out_len of the same frame (color
+ * its out_color).  Call forms as pt_denoise: on_device != 0 enqueues 1 + iterations kernels on hip_stream without a host sync;
+ * on_device == 0 is blocking and staged (56 bytes per pixel).  The handle owns the scratch records: 48 bytes per pixel of its
+ * own, beside pt_denoise's, allocated on first use, freed with the scene.  A NULL pointer other than out_variance, a parameter
+ * out of range: PT_ERR_INVALID_ARG, pt_last_error() names the argument or field.
+ *   Prep.  x_0, a' and filterable as in pt_denoise.  A pixel that is not filterable has v = 0 at every stage, is copied through
+ *   and is never a tap.  kz = 1.0f / (sigma_z * sigma_z), sl2 = sigma_l * sigma_l.
+ *   Initial variance of a filterable p:  L = hist_len[p], m = moments[p], tv = max(0, m.y - m.x * m.x).
+ *     L >= (float)min_history: v_0 = tv.
+ *     Otherwise s1 = s2 = ws = 0; taps q = p + (dx, dy) in the order dy = -3..3 (outer), dx = -3..3 (inner), centre included;
+ *     a tap outside the frame (no address is formed for it) or not filterable is skipped; otherwise w = wn * wz (pt_denoise's
+ *     two guide weights from normal and depth, rd with 1.0f / max(z_p, 1e-20f)), s1 += moments[q].x * w, s2 += moments[q].y * w,
+ *     ws += w.  ws > 0: r = 1.0f / ws, M1 = s1 * r, M2 = s2 * r, v_0 = max(0, M2 - M1 * M1) * (4.0f / max(L, 1.0f)); else v_0 = tv.
+ *   Iteration k, spacing s = 1 << k, for a filterable p:
+ *     g: gsum = cwsum = 0; taps q = p + (dx, dy) at spacing 1, dy = -1..1 (outer), dx = -1..1 (inner), in the frame and
+ *     filterable only: cw = c3[dy + 1] * c3[dx + 1] with c3 = {1/4, 1/2, 1/4}, gsum += v_k[q] * cw, cwsum += cw;
+ *     g = gsum * (1.0f / cwsum);  den = sl2 * g + var_floor.
+ *     The 25 taps q = p + s (dx, dy) in pt_denoise's order and with its skips:  w = ((h[dy + 2] * h[dx + 2]) * wn) * wz;
+ *     dl = lum(x_k[p]) - lum(x_k[q]);  w = w * (den / (den + dl * dl));
+ *     sum += x_k[q] * w per channel, vsum += v_k[q] * (w * w), wsum += w.
+ *     r = 1.0f / wsum;  x_{k+1}[p] = sum * r;  v_{k+1}[p] = vsum * (r * r).
+ *   out = x_last * a' for filterable pixels, x_last otherwise; out_variance = v_last (of the demodulated luminance). */
+int pt_denoise_variance(pt_scene* scene, const pt_vdenoise_params* d, const float* color, const float* albedo,
+                        const float* normal, const float* depth, const float* moments, const float* hist_len, float* out,
+                        float* out_variance, int on_device, void* hip_stream);
+/* The same per-pixel source (csrc/pt_denoise.h) compiled for the HOST: needs no GPU and no scene. */
+int pt_denoise_variance_host(const pt_vdenoise_params* d, const float* color, const float* albedo, const float* normal,
+                             const float* depth, const float* moments, const float* hist_len, float* out, float* out_variance);
+
 int pt_get_counters(pt_scene* scene, pt_counters* out);   /* synchronises the scene's last stream */
 
 /* HIP-event times of the last render calls on the scene, oldest first: kernel_ms[k] / resolve_ms[k] of up to max_frames calls,

@@ -201,7 +201,12 @@ struct pt_scene {
     // comes in host memory (colour, albedo, normal, depth: 10 floats per pixel; the result goes back through its first 3)
     DevBuf<float4> dn_guide, dn_x[2];
     DevBuf<float> dn_host;
-    DevBuf<float> tp_host;           // pt_temporal_accumulate: staging of a call that comes in host memory (21 floats per pixel)
+    DevBuf<float> tp_host;           // pt_temporal_accumulate: staging of a call that comes in host memory (21 floats per pixel;
+                                     // 28 for pt_temporal_accumulate_moments)
+    // pt_denoise_variance: records of its own (a call may be in flight on another stream than pt_denoise's) and staging of a
+    // call that comes in host memory (14 floats per pixel)
+    DevBuf<float4> vd_guide, vd_x[2];
+    DevBuf<float> vd_host;
     // What a frame's trace kernel writes lives in a frame slot; render call k uses slot k % frames_in_flight.  With more than one
     // slot a single-pass frame runs on the slot's own stream: the trace kernel at once (it reads the immutable scene and writes
     // the slot only), the resolve — the one step that touches the caller's buffer — once the caller's stream has reached the
@@ -1650,6 +1655,38 @@ int temporal_args(const pt_temporal_params* t, const float* color, const float* 
     return PT_OK;
 }
 
+// Arguments of pt_temporal_accumulate_moments and its host twin.
+int temporal_moments_args(const pt_temporal_params* t, float albedo_floor, const pt_temporal_io* io, ptt::Resolved* r, float* floor_out) {
+    const char* fn = "pt_temporal_accumulate_moments: ";
+    if (!t) return fail(PT_ERR_INVALID_ARG, std::string(fn) + "null pt_temporal_params");
+    if (!io) return fail(PT_ERR_INVALID_ARG, std::string(fn) + "null pt_temporal_io");
+    if (!io->color || !io->albedo || !io->normal || !io->motion || !io->prev_depth || !io->out_color || !io->out_len || !io->out_moments)
+        return fail(PT_ERR_INVALID_ARG, std::string(fn) + "null color, albedo, normal, motion, prev_depth, out_color, out_len or out_moments");
+    const int n_hist = (io->hist_color != nullptr) + (io->hist_normal != nullptr) + (io->hist_depth != nullptr) +
+                       (io->hist_len != nullptr) + (io->hist_moments != nullptr);
+    if (n_hist != 0 && n_hist != 5)
+        return fail(PT_ERR_INVALID_ARG, std::string(fn) + "hist_color, hist_normal, hist_depth, hist_len, hist_moments must be given together or all be null");
+    if (n_hist && io->out_color == io->hist_color) return fail(PT_ERR_INVALID_ARG, std::string(fn) + "out_color must not be hist_color (neighbours are gathered)");
+    if (n_hist && io->out_len == io->hist_len) return fail(PT_ERR_INVALID_ARG, std::string(fn) + "out_len must not be hist_len (neighbours are gathered)");
+    if (n_hist && io->out_moments == io->hist_moments) return fail(PT_ERR_INVALID_ARG, std::string(fn) + "out_moments must not be hist_moments (neighbours are gathered)");
+    if (const char* bad = ptt::resolve(t, r)) return fail(PT_ERR_INVALID_ARG, std::string("pt_temporal_params.") + bad + " out of range");
+    if (albedo_floor != 0.0f && !(albedo_floor > 0.0f && albedo_floor <= 3.402823466e+38f))
+        return fail(PT_ERR_INVALID_ARG, std::string(fn) + "albedo_floor out of range");
+    *floor_out = albedo_floor != 0.0f ? albedo_floor : 0.01f;
+    return PT_OK;
+}
+
+// Arguments of pt_denoise_variance and its host twin.
+int vdenoise_args(const pt_vdenoise_params* d, const float* color, const float* albedo, const float* normal, const float* depth,
+                  const float* moments, const float* hist_len, const float* out, ptdn::VResolved* r) {
+    if (!d) return fail(PT_ERR_INVALID_ARG, "pt_denoise_variance: null pt_vdenoise_params");
+    if (!color || !albedo || !normal || !depth || !out) return fail(PT_ERR_INVALID_ARG, "pt_denoise_variance: null color, albedo, normal, depth or out");
+    if (!moments) return fail(PT_ERR_INVALID_ARG, "pt_denoise_variance: null moments");
+    if (!hist_len) return fail(PT_ERR_INVALID_ARG, "pt_denoise_variance: null hist_len");
+    if (const char* bad = ptdn::vresolve(d, r)) return fail(PT_ERR_INVALID_ARG, std::string("pt_vdenoise_params.") + bad + " out of range");
+    return PT_OK;
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------------------------------
@@ -1689,6 +1726,7 @@ int pt_scene_destroy(pt_scene* S) {
     S->ad_sum.release(); S->ad_mom.release(); S->ad_list[0].release(); S->ad_list[1].release(); S->ad_count.release();
     S->ad_spp_tmp.release(); S->ad_err_tmp.release();
     S->dn_guide.release(); S->dn_x[0].release(); S->dn_x[1].release(); S->dn_host.release(); S->tp_host.release();
+    S->vd_guide.release(); S->vd_x[0].release(); S->vd_x[1].release(); S->vd_host.release();
     S->st_prims.release(); S->prev_prims.release(); S->st_normals.release(); S->st_boxes.release(); S->st_status.release();
     for (auto& pl : S->refit_plan) ptf::plan_release(&pl);
     S->drop_events();
@@ -1893,6 +1931,110 @@ int pt_temporal_accumulate_host(const pt_temporal_params* t, const float* color,
     int rc = temporal_args(t, color, normal, motion, prev_depth, hist_color, hist_normal, hist_depth, hist_len, out_color, out_len, &r);
     if (rc) return rc;
     ptt::run_host(r, color, normal, motion, prev_depth, hist_color, hist_normal, hist_depth, hist_len, out_color, out_len);
+    return PT_OK;
+}
+
+int pt_temporal_accumulate_moments(pt_scene* S, const pt_temporal_params* t, float albedo_floor, const pt_temporal_io* io, int on_device,
+                                   void* hip_stream) {
+    if (!S) return fail(PT_ERR_INVALID_ARG, "pt_temporal_accumulate_moments: null scene");
+    ptt::Resolved r;
+    float floor_v;
+    int rc = temporal_moments_args(t, albedo_floor, io, &r, &floor_v);
+    if (rc) return rc;
+    DeviceGuard guard;
+    { int grc = guard.enter(S->device); if (grc) return grc; }
+    if (on_device) {
+        const hipError_t e = (hipError_t)ptt::run_device_moments(r, floor_v, *io, hip_stream);
+        if (e != hipSuccess) return fail(PT_ERR_DEVICE, std::string("pt_temporal_accumulate_moments: ") + hipGetErrorString(e));
+        return PT_OK;
+    }
+    // host pointers: the staging buffer of pt_temporal_accumulate; per pixel 3 + 3 + 3 + 2 + 1 inputs, 3 + 3 + 1 + 1 + 2 of
+    // history, 3 + 1 + 2 outputs
+    const size_t npix = (size_t)r.width * (size_t)r.height;
+    if ((rc = S->tp_host.ensure(npix * 28))) return rc;
+    float* h = S->tp_host.p;
+    float* d_color = h; float* d_albedo = h + npix * 3; float* d_normal = h + npix * 6; float* d_motion = h + npix * 9;
+    float* d_pz = h + npix * 11;
+    float* d_hc = h + npix * 12; float* d_hn = h + npix * 15; float* d_hz = h + npix * 18; float* d_hl = h + npix * 19;
+    float* d_hm = h + npix * 20;
+    float* d_oc = h + npix * 22; float* d_ol = h + npix * 25; float* d_om = h + npix * 26;
+    HIP_TRY(hipMemcpy(d_color, io->color, npix * 3 * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_albedo, io->albedo, npix * 3 * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_normal, io->normal, npix * 3 * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_motion, io->motion, npix * 2 * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_pz, io->prev_depth, npix * sizeof(float), hipMemcpyHostToDevice));
+    if (io->hist_color) {
+        HIP_TRY(hipMemcpy(d_hc, io->hist_color, npix * 3 * sizeof(float), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_hn, io->hist_normal, npix * 3 * sizeof(float), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_hz, io->hist_depth, npix * sizeof(float), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_hl, io->hist_len, npix * sizeof(float), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_hm, io->hist_moments, npix * 2 * sizeof(float), hipMemcpyHostToDevice));
+    } else {
+        d_hc = d_hn = d_hz = d_hl = d_hm = nullptr;
+    }
+    const pt_temporal_io dio = {d_color, d_albedo, d_normal, d_motion, d_pz, d_hc, d_hn, d_hz, d_hl, d_hm, d_oc, d_ol, d_om};
+    const hipError_t e = (hipError_t)ptt::run_device_moments(r, floor_v, dio, nullptr);
+    if (e != hipSuccess) return fail(PT_ERR_DEVICE, std::string("pt_temporal_accumulate_moments: ") + hipGetErrorString(e));
+    HIP_TRY(hipMemcpy(io->out_color, d_oc, npix * 3 * sizeof(float), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(io->out_len, d_ol, npix * sizeof(float), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(io->out_moments, d_om, npix * 2 * sizeof(float), hipMemcpyDeviceToHost));
+    return PT_OK;
+}
+
+int pt_temporal_accumulate_moments_host(const pt_temporal_params* t, float albedo_floor, const pt_temporal_io* io) {
+    ptt::Resolved r;
+    float floor_v;
+    int rc = temporal_moments_args(t, albedo_floor, io, &r, &floor_v);
+    if (rc) return rc;
+    ptt::run_host_moments(r, floor_v, *io);
+    return PT_OK;
+}
+
+int pt_denoise_variance(pt_scene* S, const pt_vdenoise_params* d, const float* color, const float* albedo, const float* normal,
+                        const float* depth, const float* moments, const float* hist_len, float* out, float* out_variance,
+                        int on_device, void* hip_stream) {
+    if (!S) return fail(PT_ERR_INVALID_ARG, "pt_denoise_variance: null scene");
+    ptdn::VResolved r;
+    int rc = vdenoise_args(d, color, albedo, normal, depth, moments, hist_len, out, &r);
+    if (rc) return rc;
+    DeviceGuard guard;
+    { int grc = guard.enter(S->device); if (grc) return grc; }
+    const size_t npix = (size_t)r.width * (size_t)r.height;
+    if ((rc = S->vd_guide.ensure(npix)) || (rc = S->vd_x[0].ensure(npix)) || (rc = S->vd_x[1].ensure(npix))) return rc;
+    if (on_device) {
+        const hipError_t e = (hipError_t)ptdn::run_device_variance(r, color, albedo, normal, depth, moments, hist_len, out, out_variance,
+                                                                   S->vd_guide.p, S->vd_x[0].p, S->vd_x[1].p, hip_stream);
+        if (e != hipSuccess) return fail(PT_ERR_DEVICE, std::string("pt_denoise_variance: ") + hipGetErrorString(e));
+        return PT_OK;
+    }
+    // host pointers: per pixel 3 + 3 + 3 + 1 + 2 + 1 inputs (the frame is written over the colour) and 1 of variance
+    if ((rc = S->vd_host.ensure(npix * 14))) return rc;
+    float* h = S->vd_host.p;
+    HIP_TRY(hipMemcpy(h, color, npix * 3 * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(h + npix * 3, albedo, npix * 3 * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(h + npix * 6, normal, npix * 3 * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(h + npix * 9, depth, npix * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(h + npix * 10, moments, npix * 2 * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(h + npix * 12, hist_len, npix * sizeof(float), hipMemcpyHostToDevice));
+    const hipError_t e = (hipError_t)ptdn::run_device_variance(r, h, h + npix * 3, h + npix * 6, h + npix * 9, h + npix * 10, h + npix * 12, h,
+                                                               out_variance ? h + npix * 13 : nullptr, S->vd_guide.p, S->vd_x[0].p,
+                                                               S->vd_x[1].p, nullptr);
+    if (e != hipSuccess) return fail(PT_ERR_DEVICE, std::string("pt_denoise_variance: ") + hipGetErrorString(e));
+    HIP_TRY(hipMemcpy(out, h, npix * 3 * sizeof(float), hipMemcpyDeviceToHost));
+    if (out_variance) HIP_TRY(hipMemcpy(out_variance, h + npix * 13, npix * sizeof(float), hipMemcpyDeviceToHost));
+    return PT_OK;
+}
+
+int pt_denoise_variance_host(const pt_vdenoise_params* d, const float* color, const float* albedo, const float* normal,
+                             const float* depth, const float* moments, const float* hist_len, float* out, float* out_variance) {
+    ptdn::VResolved r;
+    int rc = vdenoise_args(d, color, albedo, normal, depth, moments, hist_len, out, &r);
+    if (rc) return rc;
+    try {
+        ptdn::run_host_variance(r, color, albedo, normal, depth, moments, hist_len, out, out_variance);
+    } catch (const std::exception& e) {
+        return fail(PT_ERR_DEVICE, std::string("pt_denoise_variance_host: ") + e.what());
+    }
     return PT_OK;
 }
 

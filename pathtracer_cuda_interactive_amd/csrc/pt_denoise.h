@@ -134,6 +134,185 @@ PT_HD void dn_store(const Rec& x, const float* albedo, float albedo_floor, float
     }
 }
 
+// ---- pt_denoise_variance (include/pt_api.h) -----------------------------------------------------------------
+// The same two records per pixel; the colour record's fourth word carries the variance of the pixel's luminance instead of
+// the flag:
+//   colour (x.r, x.g, x.b, v)      v >= 0: filterable, the variance; v = -1: not filterable
+// so an iteration still reads two 16-B records per tap, and the 3 x 3 variance prefilter reads colour records only.
+
+// pt_vdenoise_params with the defaults resolved
+struct VResolved {
+    int32_t width, height, iterations, normal_power_log2;
+    float scale, albedo_floor;
+    float kz;                                // 1 / sigma_z^2
+    float sl2;                               // sigma_l * sigma_l
+    float min_history;                       // (float)min_history: exact, at most 65536
+    float var_floor;
+};
+
+// nullptr, or the name of the first field that is out of range
+inline const char* vresolve(const pt_vdenoise_params* d, VResolved* r) {
+    auto pos_finite = [](float v) { return v > 0.0f && v <= 3.402823466e+38f; };
+    if (d->width <= 0 || d->height <= 0) return "width / height";
+    if ((int64_t)d->width * (int64_t)d->height > (1ll << 30)) return "width * height (more than 2^30 pixels)";
+    if (d->iterations < 0 || d->iterations > 8) return "iterations";
+    if (d->normal_power_log2 < 0 || d->normal_power_log2 > 10) return "normal_power_log2";
+    if (d->sigma_z != 0.0f && !pos_finite(d->sigma_z)) return "sigma_z";
+    if (d->sigma_l != 0.0f && !pos_finite(d->sigma_l)) return "sigma_l";
+    if (d->scale != 0.0f && !pos_finite(d->scale)) return "scale";
+    if (d->albedo_floor != 0.0f && !pos_finite(d->albedo_floor)) return "albedo_floor";
+    if (d->min_history < 0 || d->min_history > 65536) return "min_history";
+    if (d->var_floor != 0.0f && !pos_finite(d->var_floor)) return "var_floor";
+    r->width = d->width; r->height = d->height;
+    r->iterations = d->iterations ? d->iterations : 5;
+    r->normal_power_log2 = d->normal_power_log2;
+    r->scale = d->scale != 0.0f ? d->scale : 1.0f;
+    r->albedo_floor = d->albedo_floor != 0.0f ? d->albedo_floor : 0.01f;
+    const float sz = d->sigma_z != 0.0f ? d->sigma_z : 0.05f;
+    r->kz = 1.0f / (sz * sz);
+    const float sl = d->sigma_l != 0.0f ? d->sigma_l : 4.0f;
+    r->sl2 = sl * sl;
+    r->min_history = (float)(d->min_history ? d->min_history : 4);
+    r->var_floor = d->var_floor != 0.0f ? d->var_floor : 1e-10f;
+    return nullptr;
+}
+
+// wn and wz of pt_denoise's rule: the two guide weights of a tap q seen from p
+PT_HD void vdn_guide_weights(float npx, float npy, float npz, float zp, float inv_zp, float nqx, float nqy, float nqz, float zq,
+                             int normal_power_log2, float kz, float& wn, float& wz) {
+    wn = ptm::fmax2(0.0f, npx * nqx + npy * nqy + npz * nqz);
+    for (int e = 0; e < normal_power_log2; e++) wn = wn * wn;
+    const float rd = (zp - zq) * inv_zp;
+    wz = 1.0f / (1.0f + (rd * rd) * kz);
+}
+
+// The guide record, x_0 and v_0 of pixel (px, py) from the caller's frames.  Only a pixel whose history is shorter than
+// min_history gathers: 7 x 7 taps at spacing 1 of the neighbours' albedo (filterable?), normal, depth and moments, each
+// clipped to the frame before its address is formed.
+PT_HD void vdn_prep(const VResolved& r, const float* __restrict__ color, const float* __restrict__ albedo,
+                    const float* __restrict__ normal, const float* __restrict__ depth, const float* __restrict__ moments,
+                    const float* __restrict__ hist_len, int px, int py, Rec& guide, Rec& x0) {
+    const size_t p = (size_t)py * (size_t)r.width + (size_t)px;
+    dn_prep(color + 3 * p, albedo + 3 * p, normal + 3 * p, depth[p], r.scale, r.albedo_floor, guide, x0);
+    if (x0.w == 0.0f) { x0.w = -1.0f; return; }
+    const float L = hist_len[p];
+    const float m1 = moments[2 * p], m2 = moments[2 * p + 1];
+    const float tv = ptm::fmax2(0.0f, m2 - m1 * m1);
+    float v = tv;
+    if (!(L >= r.min_history)) {
+        const float inv_zp = 1.0f / ptm::fmax2(guide.w, 1e-20f);
+        float s1 = 0.0f, s2 = 0.0f, ws = 0.0f;
+        for (int dy = -3; dy <= 3; dy++) {
+            const int qy = py + dy;
+            if (qy < 0 || qy >= r.height) continue;
+#pragma unroll
+            for (int dx = -3; dx <= 3; dx++) {
+                const int qx = px + dx;
+                if (qx < 0 || qx >= r.width) continue;
+                const size_t q = (size_t)qy * (size_t)r.width + (size_t)qx;
+                if (!filterable(albedo + 3 * q)) continue;
+                float wn, wz;
+                vdn_guide_weights(guide.x, guide.y, guide.z, guide.w, inv_zp, normal[3 * q], normal[3 * q + 1], normal[3 * q + 2],
+                                  depth[q], r.normal_power_log2, r.kz, wn, wz);
+                const float w = wn * wz;
+                s1 = s1 + moments[2 * q] * w; s2 = s2 + moments[2 * q + 1] * w;
+                ws = ws + w;
+            }
+        }
+        if (ws > 0.0f) {
+            const float inv = 1.0f / ws;
+            const float M1 = s1 * inv, M2 = s2 * inv;
+            v = ptm::fmax2(0.0f, M2 - M1 * M1) * (4.0f / ptm::fmax2(L, 1.0f));
+        }
+    }
+    x0.w = v;
+}
+
+// (x_{k+1}, v_{k+1}) of pixel (px, py) from the records of iteration k; spacing = 1 << k.  dn_filter's tap order and row-wise
+// loads; the luminance tolerance of a tap is the 3 x 3 average g of v_k around p (spacing 1, colour records only).
+template <class R>
+PT_HD Rec vdn_filter(const R* __restrict__ guide, const R* __restrict__ x, int px, int py, int width, int height, int spacing,
+                     int normal_power_log2, float kz, float sl2, float var_floor) {
+    const size_t p = (size_t)py * (size_t)width + (size_t)px;
+    const R xp = x[p];
+    if (xp.w < 0.0f) return Rec{xp.x, xp.y, xp.z, -1.0f};
+    const R gp = guide[p];
+    const float inv_zp = 1.0f / ptm::fmax2(gp.w, 1e-20f);
+    const float lp = lum(xp.x, xp.y, xp.z);
+    const float c3[3] = {1.0f / 4.0f, 1.0f / 2.0f, 1.0f / 4.0f};
+    float gsum = 0.0f, cwsum = 0.0f;
+#pragma unroll
+    for (int dy = -1; dy <= 1; dy++) {
+        const int qy = py + dy;
+        if (qy < 0 || qy >= height) continue;
+        float vr[3];                                             // -1 also for a tap outside the frame
+#pragma unroll
+        for (int dx = -1; dx <= 1; dx++) {
+            const int qx = px + dx;
+            const bool in = qx >= 0 && qx < width;
+            const float v = x[(size_t)qy * (size_t)width + (size_t)(in ? qx : px)].w;
+            vr[dx + 1] = in ? v : -1.0f;
+        }
+#pragma unroll
+        for (int dx = -1; dx <= 1; dx++) {
+            if (vr[dx + 1] < 0.0f) continue;
+            const float cw = c3[dy + 1] * c3[dx + 1];
+            gsum = gsum + vr[dx + 1] * cw;
+            cwsum = cwsum + cw;
+        }
+    }
+    const float g = gsum * (1.0f / cwsum);
+    const float den = sl2 * g + var_floor;
+    const float h[5] = {1.0f / 16.0f, 1.0f / 4.0f, 3.0f / 8.0f, 1.0f / 4.0f, 1.0f / 16.0f};
+    float sr = 0.0f, sg = 0.0f, sb = 0.0f, vsum = 0.0f, wsum = 0.0f;
+#pragma unroll
+    for (int dy = -2; dy <= 2; dy++) {
+        const int qy = py + spacing * dy;
+        if (qy < 0 || qy >= height) continue;
+        // as in dn_filter: the ten records of a tap row are loaded before any of them is used; a tap outside the frame reads
+        // the centre column's record of that row instead and is dropped below
+        R xr[5], gr[5];
+        bool in[5];
+#pragma unroll
+        for (int dx = -2; dx <= 2; dx++) {
+            const int qx = px + spacing * dx;
+            in[dx + 2] = qx >= 0 && qx < width;
+            const size_t q = (size_t)qy * (size_t)width + (size_t)(in[dx + 2] ? qx : px);
+            xr[dx + 2] = x[q];
+            gr[dx + 2] = guide[q];
+        }
+#pragma unroll
+        for (int dx = -2; dx <= 2; dx++) {
+            const R xq = xr[dx + 2], gq = gr[dx + 2];
+            if (!in[dx + 2] || xq.w < 0.0f) continue;
+            float wn, wz;
+            vdn_guide_weights(gp.x, gp.y, gp.z, gp.w, inv_zp, gq.x, gq.y, gq.z, gq.w, normal_power_log2, kz, wn, wz);
+            float w = ((h[dy + 2] * h[dx + 2]) * wn) * wz;
+            const float dl = lp - lum(xq.x, xq.y, xq.z);
+            w = w * (den / (den + dl * dl));
+            sr = sr + xq.x * w; sg = sg + xq.y * w; sb = sb + xq.z * w;
+            vsum = vsum + xq.w * (w * w);
+            wsum = wsum + w;
+        }
+    }
+    const float inv = 1.0f / wsum;
+    return Rec{sr * inv, sg * inv, sb * inv, vsum * (inv * inv)};
+}
+
+// out = x_last * a' for filterable pixels, x_last otherwise; the variance of a pixel that is not filterable is 0
+PT_HD void vdn_store(const Rec& x, const float* albedo, float albedo_floor, float* out, float* out_variance) {
+    dn_store(Rec{x.x, x.y, x.z, x.w < 0.0f ? 0.0f : 1.0f}, albedo, albedo_floor, out);
+    if (out_variance) *out_variance = x.w < 0.0f ? 0.0f : x.w;
+}
+
+// Device side (pt_denoise.hip): run_device's contract with the two extra inputs and the optional variance output.
+int run_device_variance(const VResolved& r, const float* color, const float* albedo, const float* normal, const float* depth,
+                        const float* moments, const float* hist_len, float* out, float* out_variance, void* guide, void* xa,
+                        void* xb, void* hip_stream);
+// Host twin: the same functions over the frame, pass by pass (so `out` may alias `color`).
+void run_host_variance(const VResolved& r, const float* color, const float* albedo, const float* normal, const float* depth,
+                       const float* moments, const float* hist_len, float* out, float* out_variance);
+
 // Device side (pt_denoise.hip).  guide / xa / xb: width * height records each, device memory owned by the caller (the scene
 // handle); color .. out: device pointers.  Enqueues 1 + iterations kernels on `stream`, no host sync.  Returns a hipError_t.
 int run_device(const Resolved& r, const float* color, const float* albedo, const float* normal, const float* depth, float* out,

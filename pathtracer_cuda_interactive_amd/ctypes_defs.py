@@ -116,6 +116,19 @@ class PtTemporalParams(C.Structure):
                 ("normal_min", C.c_float), ("scale", C.c_float)]
 
 
+class PtTemporalIo(C.Structure):
+    """pt_temporal_io (pt_api.h): the buffers of pt_temporal_accumulate_moments; host or device addresses, None = NULL."""
+    _fields_ = [(n, C.c_void_p) for n in ("color", "albedo", "normal", "motion", "prev_depth", "hist_color", "hist_normal",
+                                          "hist_depth", "hist_len", "hist_moments", "out_color", "out_len", "out_moments")]
+
+
+class PtVdenoiseParams(C.Structure):
+    """pt_vdenoise_params (pt_api.h): the variance-guided a-trous filter (pt_denoise_variance)."""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("iterations", C.c_int32), ("normal_power_log2", C.c_int32),
+                ("sigma_z", C.c_float), ("sigma_l", C.c_float), ("scale", C.c_float), ("albedo_floor", C.c_float),
+                ("min_history", C.c_int32), ("var_floor", C.c_float)]
+
+
 class PtCamera(C.Structure):
     _fields_ = [("lookfrom", c_float3), ("lookat", c_float3), ("up", c_float3), ("vfov", C.c_float),
                 ("width", C.c_int32), ("height", C.c_int32), ("spp", C.c_int32)]

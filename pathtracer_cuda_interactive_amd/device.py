@@ -12,7 +12,7 @@ from . import _build
 from .ctypes_defs import (PT_MOTION_GEOMETRY_CURRENT, PT_MOTION_GEOMETRY_PREVIOUS, PT_OK, PT_SHAPE_SPHERE, PT_TRAVERSAL_DEFAULT,
                           PT_UPDATE_GEOMETRY, PT_UPDATE_SHADING, PtAdaptiveParams, PtBvhNode, PtCounters, PtDenoiseParams, PtError,
                           PtGuideBuffers, PtLight, PtMaterial, PtMesh, PtMotionParams, PtRenderParams, PtSceneDesc, PtShape,
-                          PtTemporalParams)
+                          PtTemporalIo, PtTemporalParams, PtVdenoiseParams)
 from .host import NODE_DTYPE  # noqa: F401  (one definition; callers also read it from here)
 
 _lib = None
@@ -23,6 +23,7 @@ EXPORTS = [
     "pt_debug_intersect", "pt_debug_math_host", "pt_bvh_build_device", "pt_bvh_build_sweep", "pt_get_frame_times", "pt_bvh_build_sweep_device",
     "pt_debug_exact_math", "pt_render_adaptive", "pt_render_aov", "pt_denoise", "pt_denoise_host", "pt_scene_update",
     "pt_render_guides", "pt_temporal_accumulate", "pt_temporal_accumulate_host",
+    "pt_temporal_accumulate_moments", "pt_temporal_accumulate_moments_host", "pt_denoise_variance", "pt_denoise_variance_host",
 ]
 
 
@@ -51,6 +52,10 @@ def lib():
         L.pt_render_guides.argtypes = [vp, C.POINTER(PtRenderParams), C.POINTER(PtMotionParams), C.POINTER(PtGuideBuffers), C.c_int]
         L.pt_temporal_accumulate.argtypes = [vp, C.POINTER(PtTemporalParams)] + [vp] * 10 + [C.c_int, vp]
         L.pt_temporal_accumulate_host.argtypes = [C.POINTER(PtTemporalParams)] + [vp] * 10
+        L.pt_temporal_accumulate_moments.argtypes = [vp, C.POINTER(PtTemporalParams), C.c_float, C.POINTER(PtTemporalIo), C.c_int, vp]
+        L.pt_temporal_accumulate_moments_host.argtypes = [C.POINTER(PtTemporalParams), C.c_float, C.POINTER(PtTemporalIo)]
+        L.pt_denoise_variance.argtypes = [vp, C.POINTER(PtVdenoiseParams)] + [vp] * 8 + [C.c_int, vp]
+        L.pt_denoise_variance_host.argtypes = [C.POINTER(PtVdenoiseParams)] + [vp] * 8
         L.pt_get_counters.argtypes = [vp, C.POINTER(PtCounters)]
         L.pt_get_frame_times.argtypes = [vp, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int)]
         L.pt_scene_set_option.argtypes = [vp, C.c_char_p, C.c_int64]
@@ -245,6 +250,45 @@ class DeviceScene:
                                             C.c_void_p(prev_depth_ptr), *hist, C.c_void_p(out_color_ptr), C.c_void_p(out_len_ptr), 1,
                                             C.c_void_p(stream or 0)))
 
+    def temporal_accumulate_moments(self, color, albedo, normal, motion, prev_depth, history=None, albedo_floor=0.0, **kw):
+        """pt_temporal_accumulate_moments on host arrays: (out_color [H, W, 3], out_len [H, W], out_moments [H, W, 2]) as new
+        arrays.  history: None or (hist_color, hist_normal, hist_depth, hist_len, hist_moments) of the previous frame.
+        Keywords: the fields of pt_temporal_params."""
+        args, t = _temporal_moments_args(color, albedo, normal, motion, prev_depth, history, kw)
+        outs = [np.empty_like(args[0]), np.empty_like(args[4]), np.empty_like(args[3])]
+        io = PtTemporalIo(*(a.ctypes.data if a is not None else None for a in args + outs))
+        _check(lib().pt_temporal_accumulate_moments(self._h, C.byref(t), float(albedo_floor), C.byref(io), 0, None))
+        return tuple(outs)
+
+    def temporal_accumulate_moments_into(self, width, height, color_ptr, albedo_ptr, normal_ptr, motion_ptr, prev_depth_ptr, hist_ptrs,
+                                         out_color_ptr, out_len_ptr, out_moments_ptr, stream=None, albedo_floor=0.0, **kw):
+        """pt_temporal_accumulate_moments on device memory, enqueued on a HIP stream without a host sync.  hist_ptrs: None or the
+        five pointers (hist_color, hist_normal, hist_depth, hist_len, hist_moments); out_color_ptr may be color_ptr."""
+        t = temporal_params(width, height, **kw)
+        io = PtTemporalIo(color_ptr, albedo_ptr, normal_ptr, motion_ptr, prev_depth_ptr, *(hist_ptrs if hist_ptrs else [None] * 5),
+                          out_color_ptr, out_len_ptr, out_moments_ptr)
+        _check(lib().pt_temporal_accumulate_moments(self._h, C.byref(t), float(albedo_floor), C.byref(io), 1, C.c_void_p(stream or 0)))
+
+    def denoise_variance(self, color, albedo, normal, depth, moments, hist_len, variance=False, **kw):
+        """pt_denoise_variance on host arrays (moments [H, W, 2] and hist_len [H, W] from temporal_accumulate_moments): the
+        filtered frame as a new array, or (frame, variance [H, W]) with variance=True.  Keywords: the fields of
+        pt_vdenoise_params (vdenoise_params)."""
+        arrays, d = _vdenoise_args(color, albedo, normal, depth, moments, hist_len, kw)
+        out = np.empty_like(arrays[0])
+        var = np.empty_like(arrays[3]) if variance else None
+        ptrs = [a.ctypes.data_as(C.c_void_p) for a in arrays + [out]] + [var.ctypes.data_as(C.c_void_p) if variance else None]
+        _check(lib().pt_denoise_variance(self._h, C.byref(d), *ptrs, 0, None))
+        return (out, var) if variance else out
+
+    def denoise_variance_into(self, width, height, color_ptr, albedo_ptr, normal_ptr, depth_ptr, moments_ptr, hist_len_ptr, out_ptr,
+                              out_variance_ptr=0, stream=None, **kw):
+        """pt_denoise_variance on device memory, enqueued on a HIP stream without a host sync (out_ptr may be color_ptr;
+        out_variance_ptr 0 = not wanted)."""
+        d = vdenoise_params(width, height, **kw)
+        _check(lib().pt_denoise_variance(self._h, C.byref(d), *(C.c_void_p(q) for q in (color_ptr, albedo_ptr, normal_ptr, depth_ptr,
+                                                                                      moments_ptr, hist_len_ptr, out_ptr)),
+                                         C.c_void_p(out_variance_ptr or 0), 1, C.c_void_p(stream or 0)))
+
     def accumulate_into(self, params, dev_ptr, stream=None):
         _check(lib().pt_render_accumulate(self._h, C.byref(params), C.c_void_p(dev_ptr), C.c_void_p(stream or 0)))
 
@@ -337,6 +381,69 @@ def temporal_accumulate_host(color, normal, motion, prev_depth, history=None, ou
     ptrs = [a.ctypes.data_as(C.c_void_p) if a is not None else None for a in args + [out_color, out_len]]
     _check(lib().pt_temporal_accumulate_host(C.byref(t), *ptrs))
     return out_color, out_len
+
+
+def _temporal_moments_args(color, albedo, normal, motion, prev_depth, history, kw):
+    hist5 = [None] * 5
+    if history is not None:
+        if len(history) != 5:
+            raise ValueError("temporal_accumulate_moments: history must be (color, normal, depth, len, moments [H, W, 2])")
+        hist5 = list(history)
+    args, t = _temporal_args(color, normal, motion, prev_depth, None if history is None else hist5[:4], kw)
+    albedo = np.ascontiguousarray(albedo, dtype=np.float32)
+    if albedo.shape != args[0].shape:
+        raise ValueError("temporal_accumulate_moments: albedo must be [H, W, 3]")
+    if history is not None:
+        hist5[4] = np.ascontiguousarray(hist5[4], dtype=np.float32)
+        if hist5[4].shape != args[2].shape:
+            raise ValueError("temporal_accumulate_moments: the history's moments must be [H, W, 2]")
+    return [args[0], albedo] + args[1:8] + [hist5[4]], t
+
+
+def temporal_accumulate_moments_host(color, albedo, normal, motion, prev_depth, history=None, out_color=None, albedo_floor=0.0, **kw):
+    """pt_temporal_accumulate_moments_host: the rule of pt_temporal_accumulate_moments run by the host half of the library (no
+    GPU needed).  Returns (out_color, out_len, out_moments); out_color: an [H, W, 3] float32 array to write (it may be `color`
+    itself), default a new one."""
+    args, t = _temporal_moments_args(color, albedo, normal, motion, prev_depth, history, kw)
+    if out_color is None:
+        out_color = np.empty_like(args[0])
+    if out_color.dtype != np.float32 or out_color.shape != args[0].shape or not out_color.flags.c_contiguous:
+        raise ValueError("temporal_accumulate_moments_host: out_color must be a contiguous [H, W, 3] float32 array")
+    outs = [out_color, np.empty_like(args[4]), np.empty_like(args[3])]
+    io = PtTemporalIo(*(a.ctypes.data if a is not None else None for a in args + outs))
+    _check(lib().pt_temporal_accumulate_moments_host(C.byref(t), float(albedo_floor), C.byref(io)))
+    return tuple(outs)
+
+
+def vdenoise_params(width, height, iterations=0, normal_power_log2=7, sigma_z=0.0, sigma_l=0.0, scale=0.0, albedo_floor=0.0,
+                    min_history=0, var_floor=0.0):
+    """pt_vdenoise_params; 0 = the library's default (5 iterations, sigma_z 0.05, sigma_l 4, scale 1, albedo_floor 0.01,
+    min_history 4, var_floor 1e-10)."""
+    return PtVdenoiseParams(int(width), int(height), int(iterations), int(normal_power_log2), float(sigma_z), float(sigma_l),
+                            float(scale), float(albedo_floor), int(min_history), float(var_floor))
+
+
+def _vdenoise_args(color, albedo, normal, depth, moments, hist_len, kw):
+    color, albedo, normal, depth = _denoise_args(color, albedo, normal, depth, {})[:4]
+    moments, hist_len = (np.ascontiguousarray(a, dtype=np.float32) for a in (moments, hist_len))
+    H, W = depth.shape
+    if moments.shape != (H, W, 2) or hist_len.shape != (H, W):
+        raise ValueError("denoise_variance: moments must be [H, W, 2] and hist_len [H, W]")
+    return [color, albedo, normal, depth, moments, hist_len], vdenoise_params(W, H, **kw)
+
+
+def denoise_variance_host(color, albedo, normal, depth, moments, hist_len, out=None, variance=False, **kw):
+    """pt_denoise_variance_host: the filter of pt_denoise_variance run by the host half of the library (no GPU needed).  out: an
+    [H, W, 3] float32 array to write (it may be `color` itself); default a new one.  variance=True: (out, variance [H, W])."""
+    arrays, d = _vdenoise_args(color, albedo, normal, depth, moments, hist_len, kw)
+    if out is None:
+        out = np.empty_like(arrays[0])
+    if out.dtype != np.float32 or out.shape != arrays[0].shape or not out.flags.c_contiguous:
+        raise ValueError("denoise_variance_host: out must be a contiguous [H, W, 3] float32 array")
+    var = np.empty_like(arrays[3]) if variance else None
+    ptrs = [a.ctypes.data_as(C.c_void_p) for a in arrays + [out]] + [var.ctypes.data_as(C.c_void_p) if variance else None]
+    _check(lib().pt_denoise_variance_host(C.byref(d), *ptrs))
+    return (out, var) if variance else out
 
 
 def debug_math(op, x, y=None, host=False):

@@ -1,7 +1,7 @@
 """N frames of a .pts scene under a moving camera and, optionally, wobbling meshes, cleaned in image space.
 
   python tools/animate.py SCENE.pts [--frames 8] [--size 640x480] [--spp 2] [--translate DX,DY,DZ | --orbit DEG] [--wobble]
-                          [--denoise] [--reference-spp N] [--out PREFIX] [--time]
+                          [--denoise | --variance] [--reference-spp N] [--out PREFIX] [--time]
 
 Per frame: pt_render at --spp, pt_render_guides against the previous frame's camera (and, with --wobble, the previous
 geometry: every mesh gets device.wobbled_desc's per-vertex wobble through DeviceScene.update), pt_temporal_accumulate, and with
@@ -9,6 +9,8 @@ geometry: every mesh gets device.wobbled_desc's per-vertex wobble through Device
 HIP-event time of every stage per frame and their medians, and with --reference-spp the RMSE of each stage's image against a
 pt_render of that many samples on the same geometry.  --translate is in units of the median first-hit distance of frame 0 per
 frame (default 0.02,0.008,-0.013); --orbit turns the camera about its look-at point by that many degrees per frame instead.
+--variance: the temporal stage is pt_temporal_accumulate_moments and the spatial stage pt_denoise_variance on
+its colour, moments and history length (stages "accumulate_moments" and "denoise_variance", image _variance.ppm).
 --time: after the animation, each stage again on the last frame's inputs, warm, in windows of at least 0.5 s, with
 pt_render_aov and one pt_denoise iteration as yardsticks and the bytes pt_temporal_accumulate must move."""
 import argparse
@@ -87,6 +89,7 @@ def main():
     ap.add_argument("--orbit", type=float, default=0.0)
     ap.add_argument("--wobble", action="store_true")
     ap.add_argument("--denoise", action="store_true")
+    ap.add_argument("--variance", action="store_true")
     ap.add_argument("--reference-spp", type=int, default=0)
     ap.add_argument("--out", default="")
     ap.add_argument("--time", action="store_true")
@@ -103,13 +106,18 @@ def main():
     motion, prev_depth = torch.empty((h, w, 2), device="cuda"), f1()
     # what a frame leaves for the next one, ping-ponged: accumulated colour, normal, depth, history length
     sets = [dict(out=f3(), normal=f3(), depth=f1(), length=f1()) for _ in range(2)]
+    if a.variance:
+        for st in sets:
+            st["moments"] = torch.empty((h, w, 2), device="cuda")
     p0 = hs.render_params(w, h, a.spp)
     ds.render_aov_into(p0, 0, 0, sets[0]["depth"].data_ptr(), 0)
     z = sets[0]["depth"]
     step = np.array([float(v) for v in a.translate.split(",")]) * float(z[z > 0].median()) if (z > 0).any() else np.zeros(3)
     stages = ["render", "guides", "accumulate"] + (["denoise"] if a.denoise else [])
+    if a.variance:
+        stages = ["render", "guides", "accumulate_moments", "denoise_variance"]
     times = {s: [] for s in stages}
-    errors = {s: [] for s in ("noisy", "accumulated", "denoised")}
+    errors = {s: [] for s in ("noisy", "accumulated", "denoised", "variance")}
     p_prev = None
     for k in range(a.frames):
         p = orbited_params(hs, w, h, a.spp, a.orbit * k) if a.orbit else dev.translated_params(p0, step * k)
@@ -124,15 +132,26 @@ def main():
             p, p_prev or p, previous_geometry=True, albedo_ptr=albedo.data_ptr(), normal_ptr=cur["normal"].data_ptr(),
             depth_ptr=cur["depth"].data_ptr(), motion_ptr=motion.data_ptr(), prev_depth_ptr=prev_depth.data_ptr())))
         hist = [old[n].data_ptr() for n in ("out", "normal", "depth", "length")] if k else None
-        times["accumulate"].append(once(lambda: ds.temporal_accumulate_into(
-            w, h, color.data_ptr(), cur["normal"].data_ptr(), motion.data_ptr(), prev_depth.data_ptr(), hist,
-            cur["out"].data_ptr(), cur["length"].data_ptr(), stream, **TEMPORAL)))
-        if a.denoise:
+        if a.variance:
+            hist5 = hist + [old["moments"].data_ptr()] if k else None
+            times["accumulate_moments"].append(once(lambda: ds.temporal_accumulate_moments_into(
+                w, h, color.data_ptr(), albedo.data_ptr(), cur["normal"].data_ptr(), motion.data_ptr(), prev_depth.data_ptr(), hist5,
+                cur["out"].data_ptr(), cur["length"].data_ptr(), cur["moments"].data_ptr(), stream, **TEMPORAL)))
+            times["denoise_variance"].append(once(lambda: ds.denoise_variance_into(
+                w, h, cur["out"].data_ptr(), albedo.data_ptr(), cur["normal"].data_ptr(), cur["depth"].data_ptr(),
+                cur["moments"].data_ptr(), cur["length"].data_ptr(), denoised.data_ptr(), 0, stream)))
+        else:
+            times["accumulate"].append(once(lambda: ds.temporal_accumulate_into(
+                w, h, color.data_ptr(), cur["normal"].data_ptr(), motion.data_ptr(), prev_depth.data_ptr(), hist,
+                cur["out"].data_ptr(), cur["length"].data_ptr(), stream, **TEMPORAL)))
+        if a.denoise and not a.variance:
             times["denoise"].append(once(lambda: ds.denoise_into(w, h, cur["out"].data_ptr(), albedo.data_ptr(), cur["normal"].data_ptr(),
                                                                  cur["depth"].data_ptr(), denoised.data_ptr(), stream)))
         torch.cuda.synchronize()
         images = {"noisy": color, "accumulated": cur["out"]}
-        if a.denoise:
+        if a.variance:
+            images["variance"] = denoised
+        elif a.denoise:
             images["denoised"] = denoised
         line = f"frame {k:3d}: " + "  ".join(f"{s} {times[s][-1]:7.3f} ms" for s in stages)
         if a.wobble and k:
@@ -171,6 +190,17 @@ def main():
         t["pt_temporal_accumulate"] = timed(lambda: ds.temporal_accumulate_into(
             w, h, color.data_ptr(), cur["normal"].data_ptr(), motion.data_ptr(), prev_depth.data_ptr(), hist, scratch.data_ptr(),
             cur["length"].data_ptr(), stream, **TEMPORAL))
+        if a.variance:
+            hist5 = hist + [old["moments"].data_ptr()]
+            mom = torch.empty((h, w, 2), device="cuda")
+            t["pt_temporal_accumulate_moments"] = timed(lambda: ds.temporal_accumulate_moments_into(
+                w, h, color.data_ptr(), albedo.data_ptr(), cur["normal"].data_ptr(), motion.data_ptr(), prev_depth.data_ptr(), hist5,
+                scratch.data_ptr(), cur["length"].data_ptr(), mom.data_ptr(), stream, **TEMPORAL))
+            t["pt_denoise, 5 iterations"] = timed(lambda: ds.denoise_into(w, h, cur["out"].data_ptr(), albedo.data_ptr(), cur["normal"].data_ptr(),
+                                                                          cur["depth"].data_ptr(), scratch.data_ptr(), stream))
+            t["pt_denoise_variance, 5 iterations"] = timed(lambda: ds.denoise_variance_into(
+                w, h, cur["out"].data_ptr(), albedo.data_ptr(), cur["normal"].data_ptr(), cur["depth"].data_ptr(), cur["moments"].data_ptr(),
+                cur["length"].data_ptr(), scratch.data_ptr(), 0, stream))
         t["pt_denoise, 1 iteration"] = timed(lambda: ds.denoise_into(w, h, color.data_ptr(), albedo.data_ptr(), cur["normal"].data_ptr(),
                                                                      cur["depth"].data_ptr(), scratch.data_ptr(), stream, iterations=1))
         # per pixel: colour, normal, motion, prev_depth in (36 B), one history pixel's colour, normal, depth, length in where

@@ -198,13 +198,12 @@ struct pt_scene {
     DevBuf<float> ad_err_tmp;
     int64_t info_adaptive_rounds = 0;
     // pt_denoise: the guide record and the two ping-pong colour records per pixel (pt_denoise.h), and staging of a frame that
-    // comes in host memory (colour, albedo, normal, depth: 10 floats per pixel; the result goes back through its first 3)
+    // comes in host memory (run_staged: the planes of the call; the result goes back through the colour plane)
     DevBuf<float4> dn_guide, dn_x[2];
     DevBuf<float> dn_host;
-    DevBuf<float> tp_host;           // pt_temporal_accumulate: staging of a call that comes in host memory (21 floats per pixel;
-                                     // 28 for pt_temporal_accumulate_moments)
+    DevBuf<float> tp_host;           // pt_temporal_accumulate(_moments): staging of a call that comes in host memory
     // pt_denoise_variance: records of its own (a call may be in flight on another stream than pt_denoise's) and staging of a
-    // call that comes in host memory (14 floats per pixel)
+    // call that comes in host memory
     DevBuf<float4> vd_guide, vd_x[2];
     DevBuf<float> vd_host;
     // What a frame's trace kernel writes lives in a frame slot; render call k uses slot k % frames_in_flight.  With more than one
@@ -1639,51 +1638,143 @@ int guide_pass(pt_scene* S, const pt_render_params* p, const pt_motion_params* m
     return PT_OK;
 }
 
-// Arguments of pt_temporal_accumulate and its host twin: nulls, the two forbidden aliases, the parameter ranges.
-int temporal_args(const pt_temporal_params* t, const float* color, const float* normal, const float* motion, const float* prev_depth,
-                  const float* hist_color, const float* hist_normal, const float* hist_depth, const float* hist_len,
-                  const float* out_color, const float* out_len, ptt::Resolved* r) {
-    if (!t) return fail(PT_ERR_INVALID_ARG, "pt_temporal_accumulate: null pt_temporal_params");
-    if (!color || !normal || !motion || !prev_depth || !out_color || !out_len)
-        return fail(PT_ERR_INVALID_ARG, "pt_temporal_accumulate: null color, normal, motion, prev_depth, out_color or out_len");
-    const int n_hist = (hist_color != nullptr) + (hist_normal != nullptr) + (hist_depth != nullptr) + (hist_len != nullptr);
-    if (n_hist != 0 && n_hist != 4)
-        return fail(PT_ERR_INVALID_ARG, "pt_temporal_accumulate: hist_color, hist_normal, hist_depth, hist_len must be given together or all be null");
-    if (n_hist && out_color == hist_color) return fail(PT_ERR_INVALID_ARG, "pt_temporal_accumulate: out_color must not be hist_color (neighbours are gathered)");
-    if (n_hist && out_len == hist_len) return fail(PT_ERR_INVALID_ARG, "pt_temporal_accumulate: out_len must not be hist_len (neighbours are gathered)");
-    if (const char* bad = ptt::resolve(t, r)) return fail(PT_ERR_INVALID_ARG, std::string("pt_temporal_params.") + bad + " out of range");
-    return PT_OK;
-}
-
-// Arguments of pt_temporal_accumulate_moments and its host twin.
-int temporal_moments_args(const pt_temporal_params* t, float albedo_floor, const pt_temporal_io* io, ptt::Resolved* r, float* floor_out) {
-    const char* fn = "pt_temporal_accumulate_moments: ";
-    if (!t) return fail(PT_ERR_INVALID_ARG, std::string(fn) + "null pt_temporal_params");
-    if (!io) return fail(PT_ERR_INVALID_ARG, std::string(fn) + "null pt_temporal_io");
-    if (!io->color || !io->albedo || !io->normal || !io->motion || !io->prev_depth || !io->out_color || !io->out_len || !io->out_moments)
-        return fail(PT_ERR_INVALID_ARG, std::string(fn) + "null color, albedo, normal, motion, prev_depth, out_color, out_len or out_moments");
+// Arguments of pt_temporal_accumulate, pt_temporal_accumulate_moments and their host twins: nulls, the forbidden aliases, the
+// parameter ranges.  fn: the entry point's name for the message; moments: albedo and the moments planes are expected.
+int temporal_args(const char* fn, bool moments, const pt_temporal_params* t, float albedo_floor, const pt_temporal_io* io,
+                  ptt::Resolved* r, float* floor_out) {
+    const std::string pre = std::string(fn) + ": ";
+    if (!t) return fail(PT_ERR_INVALID_ARG, pre + "null pt_temporal_params");
+    if (!io) return fail(PT_ERR_INVALID_ARG, pre + "null pt_temporal_io");
+    if (!io->color || (moments && !io->albedo) || !io->normal || !io->motion || !io->prev_depth || !io->out_color || !io->out_len ||
+        (moments && !io->out_moments))
+        return fail(PT_ERR_INVALID_ARG, pre + (moments ? "null color, albedo, normal, motion, prev_depth, out_color, out_len or out_moments"
+                                                       : "null color, normal, motion, prev_depth, out_color or out_len"));
     const int n_hist = (io->hist_color != nullptr) + (io->hist_normal != nullptr) + (io->hist_depth != nullptr) +
-                       (io->hist_len != nullptr) + (io->hist_moments != nullptr);
-    if (n_hist != 0 && n_hist != 5)
-        return fail(PT_ERR_INVALID_ARG, std::string(fn) + "hist_color, hist_normal, hist_depth, hist_len, hist_moments must be given together or all be null");
-    if (n_hist && io->out_color == io->hist_color) return fail(PT_ERR_INVALID_ARG, std::string(fn) + "out_color must not be hist_color (neighbours are gathered)");
-    if (n_hist && io->out_len == io->hist_len) return fail(PT_ERR_INVALID_ARG, std::string(fn) + "out_len must not be hist_len (neighbours are gathered)");
-    if (n_hist && io->out_moments == io->hist_moments) return fail(PT_ERR_INVALID_ARG, std::string(fn) + "out_moments must not be hist_moments (neighbours are gathered)");
+                       (io->hist_len != nullptr) + (moments && io->hist_moments != nullptr);
+    if (n_hist != 0 && n_hist != (moments ? 5 : 4))
+        return fail(PT_ERR_INVALID_ARG, pre + "hist_color, hist_normal, hist_depth, hist_len" + (moments ? ", hist_moments" : "") +
+                                            " must be given together or all be null");
+    if (n_hist && io->out_color == io->hist_color) return fail(PT_ERR_INVALID_ARG, pre + "out_color must not be hist_color (neighbours are gathered)");
+    if (n_hist && io->out_len == io->hist_len) return fail(PT_ERR_INVALID_ARG, pre + "out_len must not be hist_len (neighbours are gathered)");
+    if (moments && n_hist && io->out_moments == io->hist_moments)
+        return fail(PT_ERR_INVALID_ARG, pre + "out_moments must not be hist_moments (neighbours are gathered)");
     if (const char* bad = ptt::resolve(t, r)) return fail(PT_ERR_INVALID_ARG, std::string("pt_temporal_params.") + bad + " out of range");
     if (albedo_floor != 0.0f && !(albedo_floor > 0.0f && albedo_floor <= 3.402823466e+38f))
-        return fail(PT_ERR_INVALID_ARG, std::string(fn) + "albedo_floor out of range");
+        return fail(PT_ERR_INVALID_ARG, pre + "albedo_floor out of range");
     *floor_out = albedo_floor != 0.0f ? albedo_floor : 0.01f;
     return PT_OK;
 }
 
+// pt_temporal_accumulate's eleven pointers as the pt_temporal_io of the shared rule; the moments' three stay null
+pt_temporal_io temporal_io(const float* color, const float* normal, const float* motion, const float* prev_depth,
+                           const float* hist_color, const float* hist_normal, const float* hist_depth, const float* hist_len,
+                           float* out_color, float* out_len) {
+    return {color, nullptr, normal, motion, prev_depth, hist_color, hist_normal, hist_depth, hist_len, nullptr, out_color, out_len, nullptr};
+}
+
 // Arguments of pt_denoise_variance and its host twin.
-int vdenoise_args(const pt_vdenoise_params* d, const float* color, const float* albedo, const float* normal, const float* depth,
-                  const float* moments, const float* hist_len, const float* out, ptdn::VResolved* r) {
+int vdenoise_args(const pt_vdenoise_params* d, const ptdn::Frames& f, ptdn::Resolved* r) {
     if (!d) return fail(PT_ERR_INVALID_ARG, "pt_denoise_variance: null pt_vdenoise_params");
-    if (!color || !albedo || !normal || !depth || !out) return fail(PT_ERR_INVALID_ARG, "pt_denoise_variance: null color, albedo, normal, depth or out");
-    if (!moments) return fail(PT_ERR_INVALID_ARG, "pt_denoise_variance: null moments");
-    if (!hist_len) return fail(PT_ERR_INVALID_ARG, "pt_denoise_variance: null hist_len");
+    if (!f.color || !f.albedo || !f.normal || !f.depth || !f.out) return fail(PT_ERR_INVALID_ARG, "pt_denoise_variance: null color, albedo, normal, depth or out");
+    if (!f.moments) return fail(PT_ERR_INVALID_ARG, "pt_denoise_variance: null moments");
+    if (!f.hist_len) return fail(PT_ERR_INVALID_ARG, "pt_denoise_variance: null hist_len");
     if (const char* bad = ptdn::vresolve(d, r)) return fail(PT_ERR_INVALID_ARG, std::string("pt_vdenoise_params.") + bad + " out of range");
+    return PT_OK;
+}
+
+// Arguments of pt_denoise and its host twin.
+int denoise_args(const pt_denoise_params* d, const ptdn::Frames& f, ptdn::Resolved* r) {
+    if (!d || !f.color || !f.albedo || !f.normal || !f.depth || !f.out) return fail(PT_ERR_INVALID_ARG, "null argument");
+    if (const char* bad = ptdn::resolve(d, r)) return fail(PT_ERR_INVALID_ARG, std::string("pt_denoise_params.") + bad + " out of range");
+    return PT_OK;
+}
+
+// One plane of an image-space call: the slots of the call's pointer struct that hold it and its floats per pixel.  `in`: the
+// kernels read it; `out`: they write it; both (pt_denoise's colour): the result goes over the input.  A plane may be absent:
+// the caller's pointers in its slots are null (a history, the variance output) and stay null.
+struct Plane {
+    const float** in;
+    float** out;
+    int floats;
+};
+
+// The tail of the four image-space entry points, after their arguments are checked and the scene's device is current: run
+// the kernels (`run(stream)`, a hipError_t) on the caller's pointers, or for a call that comes in host memory stage it through
+// `staging`: one buffer of the sum of the planes, the inputs copied in plane by plane, the slots pointed at the device planes
+// for `run` on the default stream, the outputs copied back.  A plane that a call does not have is 0 floats wide.
+template <size_t N, class Run>
+int run_staged(const char* fn, int on_device, void* hip_stream, DevBuf<float>& staging, size_t npix, const Plane (&planes)[N], Run run) {
+    auto launch = [&](void* stream) {
+        const hipError_t e = (hipError_t)run(stream);
+        return e != hipSuccess ? fail(PT_ERR_DEVICE, std::string(fn) + ": " + hipGetErrorString(e)) : PT_OK;
+    };
+    if (on_device) return launch(hip_stream);
+    size_t floats = 0;
+    for (const Plane& pl : planes) floats += (size_t)pl.floats;
+    int rc = staging.ensure(npix * floats);
+    if (rc) return rc;
+    float* host_out[N];
+    float* dev = staging.p;
+    for (size_t i = 0; i < N; i++) {
+        const Plane& pl = planes[i];
+        host_out[i] = pl.out ? *pl.out : nullptr;
+        if (pl.in && *pl.in) {
+            HIP_TRY(hipMemcpy(dev, *pl.in, npix * (size_t)pl.floats * sizeof(float), hipMemcpyHostToDevice));
+            *pl.in = dev;
+        }
+        if (host_out[i]) *pl.out = dev;
+        dev += npix * (size_t)pl.floats;
+    }
+    if ((rc = launch(nullptr))) return rc;
+    for (size_t i = 0; i < N; i++)
+        if (host_out[i]) HIP_TRY(hipMemcpy(host_out[i], *planes[i].out, npix * (size_t)planes[i].floats * sizeof(float), hipMemcpyDeviceToHost));
+    return PT_OK;
+}
+
+// pt_temporal_accumulate (moments = false) and pt_temporal_accumulate_moments
+int temporal_call(const char* fn, bool moments, pt_scene* S, const pt_temporal_params* t, float albedo_floor, const pt_temporal_io* io_in,
+                  int on_device, void* hip_stream) {
+    if (!S) return fail(PT_ERR_INVALID_ARG, std::string(fn) + ": null scene");
+    ptt::Resolved r;
+    float floor_v;
+    int rc = temporal_args(fn, moments, t, albedo_floor, io_in, &r, &floor_v);
+    if (rc) return rc;
+    DeviceGuard guard;
+    { int grc = guard.enter(S->device); if (grc) return grc; }
+    pt_temporal_io io = *io_in;
+    const Plane planes[] = {{&io.color, nullptr, 3}, {&io.albedo, nullptr, moments ? 3 : 0}, {&io.normal, nullptr, 3},
+                            {&io.motion, nullptr, 2}, {&io.prev_depth, nullptr, 1},
+                            {&io.hist_color, nullptr, 3}, {&io.hist_normal, nullptr, 3}, {&io.hist_depth, nullptr, 1},
+                            {&io.hist_len, nullptr, 1}, {&io.hist_moments, nullptr, moments ? 2 : 0},
+                            {nullptr, &io.out_color, 3}, {nullptr, &io.out_len, 1}, {nullptr, &io.out_moments, moments ? 2 : 0}};
+    return run_staged(fn, on_device, hip_stream, S->tp_host, (size_t)r.width * (size_t)r.height, planes,
+                      [&](void* stream) { return ptt::run_device(r, moments, floor_v, io, stream); });
+}
+
+// pt_denoise and pt_denoise_variance behind their argument checks: the record buffers, then the kernels.  The frame is
+// written over the colour plane of a staged call.
+int denoise_call(const char* fn, pt_scene* S, const ptdn::Resolved& r, ptdn::Frames f, DevBuf<float4>& guide, DevBuf<float4> (&x)[2],
+                 DevBuf<float>& staging, int on_device, void* hip_stream) {
+    DeviceGuard guard;
+    { int grc = guard.enter(S->device); if (grc) return grc; }
+    const size_t npix = (size_t)r.width * (size_t)r.height;
+    int rc;
+    if ((rc = guide.ensure(npix)) || (rc = x[0].ensure(npix)) || (rc = x[1].ensure(npix))) return rc;
+    const bool variance = r.mode == ptdn::Mode::Variance;
+    const Plane planes[] = {{&f.color, &f.out, 3}, {&f.albedo, nullptr, 3}, {&f.normal, nullptr, 3}, {&f.depth, nullptr, 1},
+                            {&f.moments, nullptr, variance ? 2 : 0}, {&f.hist_len, nullptr, variance ? 1 : 0},
+                            {nullptr, &f.out_variance, variance ? 1 : 0}};
+    return run_staged(fn, on_device, hip_stream, staging, npix, planes,
+                      [&](void* stream) { return ptdn::run_device(r, f, guide.p, x[0].p, x[1].p, stream); });
+}
+
+// the host twins of pt_denoise and pt_denoise_variance behind their argument checks
+int denoise_host_call(const char* fn, const ptdn::Resolved& r, const ptdn::Frames& f) {
+    try {
+        ptdn::run_host(r, f);
+    } catch (const std::exception& e) {
+        return fail(PT_ERR_DEVICE, std::string(fn) + ": " + e.what());
+    }
     return PT_OK;
 }
 
@@ -1886,107 +1977,33 @@ int pt_render_guides(pt_scene* S, const pt_render_params* p, const pt_motion_par
 int pt_temporal_accumulate(pt_scene* S, const pt_temporal_params* t, const float* color, const float* normal, const float* motion,
                            const float* prev_depth, const float* hist_color, const float* hist_normal, const float* hist_depth,
                            const float* hist_len, float* out_color, float* out_len, int on_device, void* hip_stream) {
-    if (!S) return fail(PT_ERR_INVALID_ARG, "pt_temporal_accumulate: null scene");
-    ptt::Resolved r;
-    int rc = temporal_args(t, color, normal, motion, prev_depth, hist_color, hist_normal, hist_depth, hist_len, out_color, out_len, &r);
-    if (rc) return rc;
-    DeviceGuard guard;
-    { int grc = guard.enter(S->device); if (grc) return grc; }
-    if (on_device) {
-        const hipError_t e = (hipError_t)ptt::run_device(r, color, normal, motion, prev_depth, hist_color, hist_normal, hist_depth,
-                                                         hist_len, out_color, out_len, hip_stream);
-        if (e != hipSuccess) return fail(PT_ERR_DEVICE, std::string("pt_temporal_accumulate: ") + hipGetErrorString(e));
-        return PT_OK;
-    }
-    // host pointers: one staging buffer of this handle; per pixel 3 + 3 + 2 + 1 inputs, 3 + 3 + 1 + 1 of history, 3 + 1 outputs
-    const size_t npix = (size_t)r.width * (size_t)r.height;
-    if ((rc = S->tp_host.ensure(npix * 21))) return rc;
-    float* h = S->tp_host.p;
-    float* d_color = h; float* d_normal = h + npix * 3; float* d_motion = h + npix * 6; float* d_pz = h + npix * 8;
-    float* d_hc = h + npix * 9; float* d_hn = h + npix * 12; float* d_hz = h + npix * 15; float* d_hl = h + npix * 16;
-    float* d_oc = h + npix * 17; float* d_ol = h + npix * 20;
-    HIP_TRY(hipMemcpy(d_color, color, npix * 3 * sizeof(float), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_normal, normal, npix * 3 * sizeof(float), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_motion, motion, npix * 2 * sizeof(float), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_pz, prev_depth, npix * sizeof(float), hipMemcpyHostToDevice));
-    if (hist_color) {
-        HIP_TRY(hipMemcpy(d_hc, hist_color, npix * 3 * sizeof(float), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d_hn, hist_normal, npix * 3 * sizeof(float), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d_hz, hist_depth, npix * sizeof(float), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d_hl, hist_len, npix * sizeof(float), hipMemcpyHostToDevice));
-    } else {
-        d_hc = d_hn = d_hz = d_hl = nullptr;
-    }
-    const hipError_t e = (hipError_t)ptt::run_device(r, d_color, d_normal, d_motion, d_pz, d_hc, d_hn, d_hz, d_hl, d_oc, d_ol, nullptr);
-    if (e != hipSuccess) return fail(PT_ERR_DEVICE, std::string("pt_temporal_accumulate: ") + hipGetErrorString(e));
-    HIP_TRY(hipMemcpy(out_color, d_oc, npix * 3 * sizeof(float), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(out_len, d_ol, npix * sizeof(float), hipMemcpyDeviceToHost));
-    return PT_OK;
+    const pt_temporal_io io = temporal_io(color, normal, motion, prev_depth, hist_color, hist_normal, hist_depth, hist_len, out_color, out_len);
+    return temporal_call("pt_temporal_accumulate", false, S, t, 0.0f, &io, on_device, hip_stream);
 }
 
 int pt_temporal_accumulate_host(const pt_temporal_params* t, const float* color, const float* normal, const float* motion,
                                 const float* prev_depth, const float* hist_color, const float* hist_normal, const float* hist_depth,
                                 const float* hist_len, float* out_color, float* out_len) {
+    const pt_temporal_io io = temporal_io(color, normal, motion, prev_depth, hist_color, hist_normal, hist_depth, hist_len, out_color, out_len);
     ptt::Resolved r;
-    int rc = temporal_args(t, color, normal, motion, prev_depth, hist_color, hist_normal, hist_depth, hist_len, out_color, out_len, &r);
+    float floor_v;
+    int rc = temporal_args("pt_temporal_accumulate", false, t, 0.0f, &io, &r, &floor_v);
     if (rc) return rc;
-    ptt::run_host(r, color, normal, motion, prev_depth, hist_color, hist_normal, hist_depth, hist_len, out_color, out_len);
+    ptt::run_host(r, false, floor_v, io);
     return PT_OK;
 }
 
 int pt_temporal_accumulate_moments(pt_scene* S, const pt_temporal_params* t, float albedo_floor, const pt_temporal_io* io, int on_device,
                                    void* hip_stream) {
-    if (!S) return fail(PT_ERR_INVALID_ARG, "pt_temporal_accumulate_moments: null scene");
-    ptt::Resolved r;
-    float floor_v;
-    int rc = temporal_moments_args(t, albedo_floor, io, &r, &floor_v);
-    if (rc) return rc;
-    DeviceGuard guard;
-    { int grc = guard.enter(S->device); if (grc) return grc; }
-    if (on_device) {
-        const hipError_t e = (hipError_t)ptt::run_device_moments(r, floor_v, *io, hip_stream);
-        if (e != hipSuccess) return fail(PT_ERR_DEVICE, std::string("pt_temporal_accumulate_moments: ") + hipGetErrorString(e));
-        return PT_OK;
-    }
-    // host pointers: the staging buffer of pt_temporal_accumulate; per pixel 3 + 3 + 3 + 2 + 1 inputs, 3 + 3 + 1 + 1 + 2 of
-    // history, 3 + 1 + 2 outputs
-    const size_t npix = (size_t)r.width * (size_t)r.height;
-    if ((rc = S->tp_host.ensure(npix * 28))) return rc;
-    float* h = S->tp_host.p;
-    float* d_color = h; float* d_albedo = h + npix * 3; float* d_normal = h + npix * 6; float* d_motion = h + npix * 9;
-    float* d_pz = h + npix * 11;
-    float* d_hc = h + npix * 12; float* d_hn = h + npix * 15; float* d_hz = h + npix * 18; float* d_hl = h + npix * 19;
-    float* d_hm = h + npix * 20;
-    float* d_oc = h + npix * 22; float* d_ol = h + npix * 25; float* d_om = h + npix * 26;
-    HIP_TRY(hipMemcpy(d_color, io->color, npix * 3 * sizeof(float), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_albedo, io->albedo, npix * 3 * sizeof(float), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_normal, io->normal, npix * 3 * sizeof(float), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_motion, io->motion, npix * 2 * sizeof(float), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_pz, io->prev_depth, npix * sizeof(float), hipMemcpyHostToDevice));
-    if (io->hist_color) {
-        HIP_TRY(hipMemcpy(d_hc, io->hist_color, npix * 3 * sizeof(float), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d_hn, io->hist_normal, npix * 3 * sizeof(float), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d_hz, io->hist_depth, npix * sizeof(float), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d_hl, io->hist_len, npix * sizeof(float), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d_hm, io->hist_moments, npix * 2 * sizeof(float), hipMemcpyHostToDevice));
-    } else {
-        d_hc = d_hn = d_hz = d_hl = d_hm = nullptr;
-    }
-    const pt_temporal_io dio = {d_color, d_albedo, d_normal, d_motion, d_pz, d_hc, d_hn, d_hz, d_hl, d_hm, d_oc, d_ol, d_om};
-    const hipError_t e = (hipError_t)ptt::run_device_moments(r, floor_v, dio, nullptr);
-    if (e != hipSuccess) return fail(PT_ERR_DEVICE, std::string("pt_temporal_accumulate_moments: ") + hipGetErrorString(e));
-    HIP_TRY(hipMemcpy(io->out_color, d_oc, npix * 3 * sizeof(float), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(io->out_len, d_ol, npix * sizeof(float), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(io->out_moments, d_om, npix * 2 * sizeof(float), hipMemcpyDeviceToHost));
-    return PT_OK;
+    return temporal_call("pt_temporal_accumulate_moments", true, S, t, albedo_floor, io, on_device, hip_stream);
 }
 
 int pt_temporal_accumulate_moments_host(const pt_temporal_params* t, float albedo_floor, const pt_temporal_io* io) {
     ptt::Resolved r;
     float floor_v;
-    int rc = temporal_moments_args(t, albedo_floor, io, &r, &floor_v);
+    int rc = temporal_args("pt_temporal_accumulate_moments", true, t, albedo_floor, io, &r, &floor_v);
     if (rc) return rc;
-    ptt::run_host_moments(r, floor_v, *io);
+    ptt::run_host(r, true, floor_v, *io);
     return PT_OK;
 }
 
@@ -1994,88 +2011,39 @@ int pt_denoise_variance(pt_scene* S, const pt_vdenoise_params* d, const float* c
                         const float* depth, const float* moments, const float* hist_len, float* out, float* out_variance,
                         int on_device, void* hip_stream) {
     if (!S) return fail(PT_ERR_INVALID_ARG, "pt_denoise_variance: null scene");
-    ptdn::VResolved r;
-    int rc = vdenoise_args(d, color, albedo, normal, depth, moments, hist_len, out, &r);
+    const ptdn::Frames f{color, albedo, normal, depth, moments, hist_len, out, out_variance};
+    ptdn::Resolved r;
+    int rc = vdenoise_args(d, f, &r);
     if (rc) return rc;
-    DeviceGuard guard;
-    { int grc = guard.enter(S->device); if (grc) return grc; }
-    const size_t npix = (size_t)r.width * (size_t)r.height;
-    if ((rc = S->vd_guide.ensure(npix)) || (rc = S->vd_x[0].ensure(npix)) || (rc = S->vd_x[1].ensure(npix))) return rc;
-    if (on_device) {
-        const hipError_t e = (hipError_t)ptdn::run_device_variance(r, color, albedo, normal, depth, moments, hist_len, out, out_variance,
-                                                                   S->vd_guide.p, S->vd_x[0].p, S->vd_x[1].p, hip_stream);
-        if (e != hipSuccess) return fail(PT_ERR_DEVICE, std::string("pt_denoise_variance: ") + hipGetErrorString(e));
-        return PT_OK;
-    }
-    // host pointers: per pixel 3 + 3 + 3 + 1 + 2 + 1 inputs (the frame is written over the colour) and 1 of variance
-    if ((rc = S->vd_host.ensure(npix * 14))) return rc;
-    float* h = S->vd_host.p;
-    HIP_TRY(hipMemcpy(h, color, npix * 3 * sizeof(float), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(h + npix * 3, albedo, npix * 3 * sizeof(float), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(h + npix * 6, normal, npix * 3 * sizeof(float), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(h + npix * 9, depth, npix * sizeof(float), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(h + npix * 10, moments, npix * 2 * sizeof(float), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(h + npix * 12, hist_len, npix * sizeof(float), hipMemcpyHostToDevice));
-    const hipError_t e = (hipError_t)ptdn::run_device_variance(r, h, h + npix * 3, h + npix * 6, h + npix * 9, h + npix * 10, h + npix * 12, h,
-                                                               out_variance ? h + npix * 13 : nullptr, S->vd_guide.p, S->vd_x[0].p,
-                                                               S->vd_x[1].p, nullptr);
-    if (e != hipSuccess) return fail(PT_ERR_DEVICE, std::string("pt_denoise_variance: ") + hipGetErrorString(e));
-    HIP_TRY(hipMemcpy(out, h, npix * 3 * sizeof(float), hipMemcpyDeviceToHost));
-    if (out_variance) HIP_TRY(hipMemcpy(out_variance, h + npix * 13, npix * sizeof(float), hipMemcpyDeviceToHost));
-    return PT_OK;
+    return denoise_call("pt_denoise_variance", S, r, f, S->vd_guide, S->vd_x, S->vd_host, on_device, hip_stream);
 }
 
 int pt_denoise_variance_host(const pt_vdenoise_params* d, const float* color, const float* albedo, const float* normal,
                              const float* depth, const float* moments, const float* hist_len, float* out, float* out_variance) {
-    ptdn::VResolved r;
-    int rc = vdenoise_args(d, color, albedo, normal, depth, moments, hist_len, out, &r);
+    const ptdn::Frames f{color, albedo, normal, depth, moments, hist_len, out, out_variance};
+    ptdn::Resolved r;
+    int rc = vdenoise_args(d, f, &r);
     if (rc) return rc;
-    try {
-        ptdn::run_host_variance(r, color, albedo, normal, depth, moments, hist_len, out, out_variance);
-    } catch (const std::exception& e) {
-        return fail(PT_ERR_DEVICE, std::string("pt_denoise_variance_host: ") + e.what());
-    }
-    return PT_OK;
+    return denoise_host_call("pt_denoise_variance_host", r, f);
 }
 
 int pt_denoise(pt_scene* S, const pt_denoise_params* d, const float* color, const float* albedo, const float* normal,
                const float* depth, float* out, int on_device, void* hip_stream) {
-    if (!S || !d || !color || !albedo || !normal || !depth || !out) return fail(PT_ERR_INVALID_ARG, "null argument");
+    if (!S) return fail(PT_ERR_INVALID_ARG, "null argument");
+    const ptdn::Frames f{color, albedo, normal, depth, nullptr, nullptr, out, nullptr};
     ptdn::Resolved r;
-    if (const char* bad = ptdn::resolve(d, &r)) return fail(PT_ERR_INVALID_ARG, std::string("pt_denoise_params.") + bad + " out of range");
-    DeviceGuard guard;
-    { int grc = guard.enter(S->device); if (grc) return grc; }
-    const size_t npix = (size_t)r.width * (size_t)r.height;
-    int rc;
-    if ((rc = S->dn_guide.ensure(npix)) || (rc = S->dn_x[0].ensure(npix)) || (rc = S->dn_x[1].ensure(npix))) return rc;
-    if (on_device) {
-        const hipError_t e = (hipError_t)ptdn::run_device(r, color, albedo, normal, depth, out, S->dn_guide.p, S->dn_x[0].p, S->dn_x[1].p, hip_stream);
-        if (e != hipSuccess) return fail(PT_ERR_DEVICE, std::string("pt_denoise: ") + hipGetErrorString(e));
-        return PT_OK;
-    }
-    if ((rc = S->dn_host.ensure(npix * 10))) return rc;
-    float* h = S->dn_host.p;
-    HIP_TRY(hipMemcpy(h, color, npix * 3 * sizeof(float), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(h + npix * 3, albedo, npix * 3 * sizeof(float), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(h + npix * 6, normal, npix * 3 * sizeof(float), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(h + npix * 9, depth, npix * sizeof(float), hipMemcpyHostToDevice));
-    const hipError_t e = (hipError_t)ptdn::run_device(r, h, h + npix * 3, h + npix * 6, h + npix * 9, h, S->dn_guide.p, S->dn_x[0].p, S->dn_x[1].p, nullptr);
-    if (e != hipSuccess) return fail(PT_ERR_DEVICE, std::string("pt_denoise: ") + hipGetErrorString(e));
-    HIP_TRY(hipMemcpy(out, h, npix * 3 * sizeof(float), hipMemcpyDeviceToHost));
-    return PT_OK;
+    int rc = denoise_args(d, f, &r);
+    if (rc) return rc;
+    return denoise_call("pt_denoise", S, r, f, S->dn_guide, S->dn_x, S->dn_host, on_device, hip_stream);
 }
 
 int pt_denoise_host(const pt_denoise_params* d, const float* color, const float* albedo, const float* normal, const float* depth,
                     float* out) {
-    if (!d || !color || !albedo || !normal || !depth || !out) return fail(PT_ERR_INVALID_ARG, "null argument");
+    const ptdn::Frames f{color, albedo, normal, depth, nullptr, nullptr, out, nullptr};
     ptdn::Resolved r;
-    if (const char* bad = ptdn::resolve(d, &r)) return fail(PT_ERR_INVALID_ARG, std::string("pt_denoise_params.") + bad + " out of range");
-    try {
-        ptdn::run_host(r, color, albedo, normal, depth, out);
-    } catch (const std::exception& e) {
-        return fail(PT_ERR_DEVICE, std::string("pt_denoise_host: ") + e.what());
-    }
-    return PT_OK;
+    int rc = denoise_args(d, f, &r);
+    if (rc) return rc;
+    return denoise_host_call("pt_denoise_host", r, f);
 }
 
 int pt_get_counters(pt_scene* S, pt_counters* out) {

@@ -1,7 +1,8 @@
 // pt_temporal.h — the per-pixel rules of pt_render_guides' motion part and of pt_temporal_accumulate (include/pt_api.h,
 // DESIGN.md §19), written once for the device (aov_kernel<., true> in pt_kernels.h, pt_temporal.hip) and for the host twin
-// pt_temporal_accumulate_host; and of pt_temporal_accumulate_moments, which carries two luminance moments on
-// the same taps.
+// pt_temporal_accumulate_host.  pt_temporal_accumulate_moments is the same function, accumulate_pixel, with
+// MOMENTS = true: it carries two luminance moments on the same taps.  The host twins' frame loop, run_host, is here too, so a
+// plain host compile of this header runs what pt_temporal_accumulate*_host run (tests/native/post_rules_check.cpp).
 //
 // Every operation is an IEEE fp32 + - * / sqrt in the order written (no contraction: the build forbids it), so the device, the
 // host twin and a numpy restatement give the same bits.
@@ -72,68 +73,23 @@ inline const char* resolve(const pt_temporal_params* t, Resolved* r) {
     return nullptr;
 }
 
-// One pixel of pt_temporal_accumulate.  hist_color == nullptr: no history.  The four tap addresses are formed only after the
-// clip to the frame.  out_color may be `color`: a pixel reads only its own colour.
-PT_HD void accumulate_pixel(const Resolved& r, int px, int py, const float* __restrict__ normal, const float* __restrict__ motion,
-                            const float* __restrict__ prev_depth, const float* __restrict__ hist_color,
-                            const float* __restrict__ hist_normal, const float* __restrict__ hist_depth,
-                            const float* __restrict__ hist_len, const float* color, float* out_color,
-                            float* __restrict__ out_len) {
-    const size_t p = (size_t)py * (size_t)r.width + (size_t)px;
-    const float cr = color[3 * p] * r.scale, cg = color[3 * p + 1] * r.scale, cb = color[3 * p + 2] * r.scale;
-    float o_r = cr, o_g = cg, o_b = cb, o_len = 1.0f;            // the fallback
-    const float zp = prev_depth[p];
-    if (hist_color && zp != 0.0f) {
-        const float x = motion[2 * p] - 0.5f, y = motion[2 * p + 1] - 0.5f;
-        if (x >= -1.0f && x < (float)r.width && y >= -1.0f && y < (float)r.height) {
-            const float x0 = __builtin_floorf(x), y0 = __builtin_floorf(y);
-            const float fx = x - x0, fy = y - y0;
-            const int ix = (int)x0, iy = (int)y0;
-            const float nx = normal[3 * p], ny = normal[3 * p + 1], nz = normal[3 * p + 2];
-            const float tol = r.sigma_z * zp;
-            float sr = 0.0f, sg = 0.0f, sb = 0.0f, lsum = 0.0f, wsum = 0.0f;
-#pragma unroll
-            for (int dy = 0; dy < 2; dy++) {
-#pragma unroll
-                for (int dx = 0; dx < 2; dx++) {
-                    const int qx = ix + dx, qy = iy + dy;
-                    if (qx < 0 || qx >= r.width || qy < 0 || qy >= r.height) continue;
-                    const float b = (dx ? fx : 1.0f - fx) * (dy ? fy : 1.0f - fy);
-                    const size_t q = (size_t)qy * (size_t)r.width + (size_t)qx;
-                    const float hl = hist_len[q], hz = hist_depth[q];
-                    if (!(hl > 0.0f) || hz == 0.0f) continue;
-                    if (!(__builtin_fabsf(hz - zp) <= tol)) continue;
-                    if (!(nx * hist_normal[3 * q] + ny * hist_normal[3 * q + 1] + nz * hist_normal[3 * q + 2] >= r.normal_min)) continue;
-                    sr = sr + hist_color[3 * q] * b; sg = sg + hist_color[3 * q + 1] * b; sb = sb + hist_color[3 * q + 2] * b;
-                    lsum = lsum + hl * b;
-                    wsum = wsum + b;
-                }
-            }
-            if (wsum > 0.0f) {
-                const float inv = 1.0f / wsum;
-                const float hr = sr * inv, hg = sg * inv, hb = sb * inv;
-                const float n = ptm::fmin2(lsum * inv + 1.0f, r.max_history);
-                const float a = 1.0f / n;
-                o_r = hr + (cr - hr) * a; o_g = hg + (cg - hg) * a; o_b = hb + (cb - hb) * a;
-                o_len = n;
-            }
-        }
-    }
-    out_color[3 * p] = o_r; out_color[3 * p + 1] = o_g; out_color[3 * p + 2] = o_b;
-    out_len[p] = o_len;
-}
-
-// One pixel of pt_temporal_accumulate_moments: accumulate_pixel's colour and length, operation for operation, and the first
-// two moments of the demodulated luminance carried on the same taps with the same weights.  io.hist_color == nullptr: no
-// history.  io.out_color may be io.color.
-PT_HD void accumulate_moments_pixel(const Resolved& r, float albedo_floor, int px, int py, const pt_temporal_io& io) {
+// One pixel of pt_temporal_accumulate (MOMENTS = false) and of pt_temporal_accumulate_moments (MOMENTS = true: the same
+// colour and length from the same instantiation of every line, and the first two moments of the demodulated luminance carried
+// on the same taps with the same weights).  io.hist_color == nullptr: no history.  The four tap addresses are formed only
+// after the clip to the frame.  io.out_color may be io.color: a pixel reads only its own colour.  MOMENTS = false never reads
+// io.albedo, io.hist_moments or io.out_moments (they are null there) nor albedo_floor.
+template <bool MOMENTS>
+PT_HD void accumulate_pixel(const Resolved& r, float albedo_floor, int px, int py, const pt_temporal_io& io) {
     const size_t p = (size_t)py * (size_t)r.width + (size_t)px;
     const float cr = io.color[3 * p] * r.scale, cg = io.color[3 * p + 1] * r.scale, cb = io.color[3 * p + 2] * r.scale;
-    const float* al = io.albedo + 3 * p;
-    const float l = ptdn::filterable(al) ? ptdn::lum(cr / ptm::fmax2(al[0], albedo_floor), cg / ptm::fmax2(al[1], albedo_floor),
-                                                     cb / ptm::fmax2(al[2], albedo_floor))
-                                         : ptdn::lum(cr, cg, cb);
-    const float m1 = l, m2 = l * l;
+    float m1 = 0.0f, m2 = 0.0f;
+    if constexpr (MOMENTS) {
+        const float* al = io.albedo + 3 * p;
+        const float l = ptdn::filterable(al) ? ptdn::lum(cr / ptm::fmax2(al[0], albedo_floor), cg / ptm::fmax2(al[1], albedo_floor),
+                                                         cb / ptm::fmax2(al[2], albedo_floor))
+                                             : ptdn::lum(cr, cg, cb);
+        m1 = l; m2 = l * l;
+    }
     float o_r = cr, o_g = cg, o_b = cb, o_len = 1.0f, o_m1 = m1, o_m2 = m2;            // the fallback
     const float zp = io.prev_depth[p];
     if (io.hist_color && zp != 0.0f) {
@@ -159,7 +115,7 @@ PT_HD void accumulate_moments_pixel(const Resolved& r, float albedo_floor, int p
                     if (!(nx * io.hist_normal[3 * q] + ny * io.hist_normal[3 * q + 1] + nz * io.hist_normal[3 * q + 2] >= r.normal_min)) continue;
                     sr = sr + io.hist_color[3 * q] * b; sg = sg + io.hist_color[3 * q + 1] * b; sb = sb + io.hist_color[3 * q + 2] * b;
                     lsum = lsum + hl * b;
-                    ms1 = ms1 + io.hist_moments[2 * q] * b; ms2 = ms2 + io.hist_moments[2 * q + 1] * b;
+                    if constexpr (MOMENTS) { ms1 = ms1 + io.hist_moments[2 * q] * b; ms2 = ms2 + io.hist_moments[2 * q + 1] * b; }
                     wsum = wsum + b;
                 }
             }
@@ -170,28 +126,28 @@ PT_HD void accumulate_moments_pixel(const Resolved& r, float albedo_floor, int p
                 const float a = 1.0f / n;
                 o_r = hr + (cr - hr) * a; o_g = hg + (cg - hg) * a; o_b = hb + (cb - hb) * a;
                 o_len = n;
-                const float h1 = ms1 * inv, h2 = ms2 * inv;
-                o_m1 = h1 + (m1 - h1) * a; o_m2 = h2 + (m2 - h2) * a;
+                if constexpr (MOMENTS) {
+                    const float h1 = ms1 * inv, h2 = ms2 * inv;
+                    o_m1 = h1 + (m1 - h1) * a; o_m2 = h2 + (m2 - h2) * a;
+                }
             }
         }
     }
     io.out_color[3 * p] = o_r; io.out_color[3 * p + 1] = o_g; io.out_color[3 * p + 2] = o_b;
     io.out_len[p] = o_len;
-    io.out_moments[2 * p] = o_m1; io.out_moments[2 * p + 1] = o_m2;
+    if constexpr (MOMENTS) { io.out_moments[2 * p] = o_m1; io.out_moments[2 * p + 1] = o_m2; }
 }
 
 // Device side (pt_temporal.hip): one kernel on `stream`, no host sync.  Returns a hipError_t.
-int run_device_moments(const Resolved& r, float albedo_floor, const pt_temporal_io& io, void* hip_stream);
-// Host twin: the same function over the frame.
-void run_host_moments(const Resolved& r, float albedo_floor, const pt_temporal_io& io);
+int run_device(const Resolved& r, bool moments, float albedo_floor, const pt_temporal_io& io, void* hip_stream);
 
-// Device side (pt_temporal.hip): one kernel on `stream`, no host sync.  Returns a hipError_t.
-int run_device(const Resolved& r, const float* color, const float* normal, const float* motion, const float* prev_depth,
-               const float* hist_color, const float* hist_normal, const float* hist_depth, const float* hist_len,
-               float* out_color, float* out_len, void* hip_stream);
 // Host twin: the same function over the frame.
-void run_host(const Resolved& r, const float* color, const float* normal, const float* motion, const float* prev_depth,
-              const float* hist_color, const float* hist_normal, const float* hist_depth, const float* hist_len,
-              float* out_color, float* out_len);
+inline void run_host(const Resolved& r, bool moments, float albedo_floor, const pt_temporal_io& io) {
+    for (int py = 0; py < r.height; py++)
+        for (int px = 0; px < r.width; px++) {
+            if (moments) accumulate_pixel<true>(r, albedo_floor, px, py, io);
+            else accumulate_pixel<false>(r, albedo_floor, px, py, io);
+        }
+}
 
 }  // namespace ptt

@@ -193,8 +193,7 @@ class DeviceScene:
         array.  Keywords: the fields of pt_denoise_params (denoise_params)."""
         color, albedo, normal, depth, d = _denoise_args(color, albedo, normal, depth, kw)
         out = np.empty_like(color)
-        _check(lib().pt_denoise(self._h, C.byref(d), *(a.ctypes.data_as(C.c_void_p) for a in (color, albedo, normal, depth, out)),
-                                0, None))
+        _check(lib().pt_denoise(self._h, C.byref(d), *_ptrs([color, albedo, normal, depth, out]), 0, None))
         return out
 
     def denoise_into(self, width, height, color_ptr, albedo_ptr, normal_ptr, depth_ptr, out_ptr, stream=None, **kw):
@@ -236,8 +235,7 @@ class DeviceScene:
         (hist_color, hist_normal, hist_depth, hist_len) of the previous frame.  Keywords: the fields of pt_temporal_params."""
         args, t = _temporal_args(color, normal, motion, prev_depth, history, kw)
         out_color, out_len = np.empty_like(args[0]), np.empty_like(args[3])
-        ptrs = [a.ctypes.data_as(C.c_void_p) if a is not None else None for a in args + [out_color, out_len]]
-        _check(lib().pt_temporal_accumulate(self._h, C.byref(t), *ptrs, 0, None))
+        _check(lib().pt_temporal_accumulate(self._h, C.byref(t), *_ptrs(args + [out_color, out_len]), 0, None))
         return out_color, out_len
 
     def temporal_accumulate_into(self, width, height, color_ptr, normal_ptr, motion_ptr, prev_depth_ptr, hist_ptrs, out_color_ptr,
@@ -256,7 +254,7 @@ class DeviceScene:
         Keywords: the fields of pt_temporal_params."""
         args, t = _temporal_moments_args(color, albedo, normal, motion, prev_depth, history, kw)
         outs = [np.empty_like(args[0]), np.empty_like(args[4]), np.empty_like(args[3])]
-        io = PtTemporalIo(*(a.ctypes.data if a is not None else None for a in args + outs))
+        io = PtTemporalIo(*_ptrs(args + outs))
         _check(lib().pt_temporal_accumulate_moments(self._h, C.byref(t), float(albedo_floor), C.byref(io), 0, None))
         return tuple(outs)
 
@@ -276,8 +274,7 @@ class DeviceScene:
         arrays, d = _vdenoise_args(color, albedo, normal, depth, moments, hist_len, kw)
         out = np.empty_like(arrays[0])
         var = np.empty_like(arrays[3]) if variance else None
-        ptrs = [a.ctypes.data_as(C.c_void_p) for a in arrays + [out]] + [var.ctypes.data_as(C.c_void_p) if variance else None]
-        _check(lib().pt_denoise_variance(self._h, C.byref(d), *ptrs, 0, None))
+        _check(lib().pt_denoise_variance(self._h, C.byref(d), *_ptrs(arrays + [out, var]), 0, None))
         return (out, var) if variance else out
 
     def denoise_variance_into(self, width, height, color_ptr, albedo_ptr, normal_ptr, depth_ptr, moments_ptr, hist_len_ptr, out_ptr,
@@ -314,6 +311,20 @@ class DeviceScene:
         return tuv, prim
 
 
+def _ptrs(arrays):
+    """The c_void_p of each array of a list; None stays None (a null pointer)."""
+    return [a.ctypes.data_as(C.c_void_p) if a is not None else None for a in arrays]
+
+
+def _out_like(out, like, what):
+    """`out` if given, else a new array like `like`; it must be a contiguous float32 array of `like`'s shape."""
+    if out is None:
+        return np.empty_like(like)
+    if out.dtype != np.float32 or out.shape != like.shape or not out.flags.c_contiguous:
+        raise ValueError(what + " must be a contiguous [H, W, 3] float32 array")
+    return out
+
+
 def denoise_params(width, height, iterations=0, normal_power_log2=7, sigma_z=0.0, sigma_c=0.0, scale=0.0, albedo_floor=0.0):
     """pt_denoise_params; 0 = the library's default (5 iterations, sigma_z 0.05, no colour term, scale 1, albedo_floor 0.01)."""
     return PtDenoiseParams(int(width), int(height), int(iterations), int(normal_power_log2), float(sigma_z), float(sigma_c),
@@ -333,11 +344,8 @@ def denoise_host(color, albedo, normal, depth, out=None, **kw):
     """pt_denoise_host: the filter of pt_denoise run by the host half of the library (no GPU needed).  out: an [H, W, 3]
     float32 array to write (it may be `color` itself); default a new one."""
     color, albedo, normal, depth, d = _denoise_args(color, albedo, normal, depth, kw)
-    if out is None:
-        out = np.empty_like(color)
-    if out.dtype != np.float32 or out.shape != color.shape or not out.flags.c_contiguous:
-        raise ValueError("denoise_host: out must be a contiguous [H, W, 3] float32 array")
-    _check(lib().pt_denoise_host(C.byref(d), *(a.ctypes.data_as(C.c_void_p) for a in (color, albedo, normal, depth, out))))
+    out = _out_like(out, color, "denoise_host: out")
+    _check(lib().pt_denoise_host(C.byref(d), *_ptrs([color, albedo, normal, depth, out])))
     return out
 
 
@@ -373,31 +381,26 @@ def temporal_accumulate_host(color, normal, motion, prev_depth, history=None, ou
     """pt_temporal_accumulate_host: the rule of pt_temporal_accumulate run by the host half of the library (no GPU needed).
     Returns (out_color, out_len); out_color: an [H, W, 3] float32 array to write (it may be `color` itself), default a new one."""
     args, t = _temporal_args(color, normal, motion, prev_depth, history, kw)
-    if out_color is None:
-        out_color = np.empty_like(args[0])
-    if out_color.dtype != np.float32 or out_color.shape != args[0].shape or not out_color.flags.c_contiguous:
-        raise ValueError("temporal_accumulate_host: out_color must be a contiguous [H, W, 3] float32 array")
+    out_color = _out_like(out_color, args[0], "temporal_accumulate_host: out_color")
     out_len = np.empty_like(args[3])
-    ptrs = [a.ctypes.data_as(C.c_void_p) if a is not None else None for a in args + [out_color, out_len]]
-    _check(lib().pt_temporal_accumulate_host(C.byref(t), *ptrs))
+    _check(lib().pt_temporal_accumulate_host(C.byref(t), *_ptrs(args + [out_color, out_len])))
     return out_color, out_len
 
 
 def _temporal_moments_args(color, albedo, normal, motion, prev_depth, history, kw):
-    hist5 = [None] * 5
-    if history is not None:
-        if len(history) != 5:
-            raise ValueError("temporal_accumulate_moments: history must be (color, normal, depth, len, moments [H, W, 2])")
-        hist5 = list(history)
-    args, t = _temporal_args(color, normal, motion, prev_depth, None if history is None else hist5[:4], kw)
+    if history is not None and len(history) != 5:
+        raise ValueError("temporal_accumulate_moments: history must be (color, normal, depth, len, moments [H, W, 2])")
+    (color, normal, motion, prev_depth, *hist), t = _temporal_args(color, normal, motion, prev_depth,
+                                                                   None if history is None else list(history)[:4], kw)
     albedo = np.ascontiguousarray(albedo, dtype=np.float32)
-    if albedo.shape != args[0].shape:
+    if albedo.shape != color.shape:
         raise ValueError("temporal_accumulate_moments: albedo must be [H, W, 3]")
+    hist_moments = None
     if history is not None:
-        hist5[4] = np.ascontiguousarray(hist5[4], dtype=np.float32)
-        if hist5[4].shape != args[2].shape:
+        hist_moments = np.ascontiguousarray(history[4], dtype=np.float32)
+        if hist_moments.shape != motion.shape:
             raise ValueError("temporal_accumulate_moments: the history's moments must be [H, W, 2]")
-    return [args[0], albedo] + args[1:8] + [hist5[4]], t
+    return [color, albedo, normal, motion, prev_depth, *hist, hist_moments], t
 
 
 def temporal_accumulate_moments_host(color, albedo, normal, motion, prev_depth, history=None, out_color=None, albedo_floor=0.0, **kw):
@@ -405,12 +408,9 @@ def temporal_accumulate_moments_host(color, albedo, normal, motion, prev_depth, 
     GPU needed).  Returns (out_color, out_len, out_moments); out_color: an [H, W, 3] float32 array to write (it may be `color`
     itself), default a new one."""
     args, t = _temporal_moments_args(color, albedo, normal, motion, prev_depth, history, kw)
-    if out_color is None:
-        out_color = np.empty_like(args[0])
-    if out_color.dtype != np.float32 or out_color.shape != args[0].shape or not out_color.flags.c_contiguous:
-        raise ValueError("temporal_accumulate_moments_host: out_color must be a contiguous [H, W, 3] float32 array")
+    out_color = _out_like(out_color, args[0], "temporal_accumulate_moments_host: out_color")
     outs = [out_color, np.empty_like(args[4]), np.empty_like(args[3])]
-    io = PtTemporalIo(*(a.ctypes.data if a is not None else None for a in args + outs))
+    io = PtTemporalIo(*_ptrs(args + outs))
     _check(lib().pt_temporal_accumulate_moments_host(C.byref(t), float(albedo_floor), C.byref(io)))
     return tuple(outs)
 
@@ -436,13 +436,9 @@ def denoise_variance_host(color, albedo, normal, depth, moments, hist_len, out=N
     """pt_denoise_variance_host: the filter of pt_denoise_variance run by the host half of the library (no GPU needed).  out: an
     [H, W, 3] float32 array to write (it may be `color` itself); default a new one.  variance=True: (out, variance [H, W])."""
     arrays, d = _vdenoise_args(color, albedo, normal, depth, moments, hist_len, kw)
-    if out is None:
-        out = np.empty_like(arrays[0])
-    if out.dtype != np.float32 or out.shape != arrays[0].shape or not out.flags.c_contiguous:
-        raise ValueError("denoise_variance_host: out must be a contiguous [H, W, 3] float32 array")
+    out = _out_like(out, arrays[0], "denoise_variance_host: out")
     var = np.empty_like(arrays[3]) if variance else None
-    ptrs = [a.ctypes.data_as(C.c_void_p) for a in arrays + [out]] + [var.ctypes.data_as(C.c_void_p) if variance else None]
-    _check(lib().pt_denoise_variance_host(C.byref(d), *ptrs))
+    _check(lib().pt_denoise_variance_host(C.byref(d), *_ptrs(arrays + [out, var])))
     return (out, var) if variance else out
 
 

@@ -124,6 +124,8 @@ def corner_cases():
     cases["1 iteration"] = synthetic(8, 24, 31) + ({"iterations": 1},)
     cases["8 iterations"] = synthetic(9, 40, 70) + ({"iterations": 8},)
     cases["8 iterations, colour term"] = synthetic(10, 19, 300, unfilterable=0.02) + ({"iterations": 8, "sigma_c": 1.0},)
+    cases["1x1 frame"] = synthetic(11, 1, 1, unfilterable=0) + ({"sigma_c": 0.5},)
+    cases["65x5 frame: one pixel past a 64x4 tile each way"] = synthetic(12, 5, 65) + ({"iterations": 8},)
     return cases
 
 

@@ -192,6 +192,10 @@ def corner_cases():
     cases["min_history 65536, sigma_l 0.5, var_floor 1e-3"] = synthetic_v(10, 24, 31) + \
         ({"min_history": 65536, "sigma_l": 0.5, "var_floor": 1e-3},)
     cases["sigma_z 0.2, sigma_l 16"] = synthetic_v(11, 33, 40) + ({"sigma_z": 0.2, "sigma_l": 16.0},)
+    c, a, n, z, m, L = synthetic_v(12, 1, 1, unfilterable=0)
+    cases["1x1 frame, history short"] = (c, a, n, z, m, np.ones_like(L), {})
+    cases["1x1 frame, history long"] = (c, a, n, z, m, np.full_like(L, 9), {})
+    cases["65x5 frame: one pixel past a 64x4 tile each way"] = synthetic_v(13, 5, 65) + ({"iterations": 8},)
     return cases
 
 

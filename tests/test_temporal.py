@@ -142,6 +142,12 @@ def corner_cases():
     cases["no history"] = (c, n, m, z, None, {"scale": 0.5})
     cases["history of length 0 everywhere"] = (c, n, m, z, (h[0], h[1], h[2], np.zeros_like(h[3])), {})
     cases["every pixel invalid"] = (c, n, m, np.zeros_like(z), h, {})
+    c, n, m, z, h = synthetic(10, 1, 1)
+    z[:] = 2.0
+    for name, mv in (("the tap kept", (0.5, 0.5)), ("the window half outside", (0.25, 1.25))):
+        motion = np.broadcast_to(np.array(mv, dtype=F), m.shape).copy()
+        cases["1x1 frame, " + name] = (c, n, motion, z, (h[0], n.copy(), z.copy(), np.full_like(h[3], 3)), {})
+    cases["65x5: one pixel past a 64x4 tile each way"] = synthetic(11, 5, 65) + ({},)
     return cases
 
 

@@ -490,7 +490,12 @@ int pt_get_frame_times(pt_scene* scene, int max_frames, double* kernel_ms, doubl
  * *out_depth (optional) the depth with leaves counting 1 (computeMaxDepth, bvh.cu:56-65); *out_build_ms (optional)
  * the device time from primitive boxes to finished nodes (uploads and the copy back to the host excluded).
  * Such trees visit fewer nodes per ray than the reference's; closest hits — and so images — are the same except where
- * two primitives tie on t (the first one VISITED wins, scene.h:270).  Parity and roofline numbers use the reference tree. */
+ * two primitives tie on t (the first one VISITED wins, scene.h:270).  Parity and roofline numbers use the reference tree.
+ * Depth: PT_BVH_DEVICE_SAH caps its tree at min(48, max(8, ceil(log2 N) + 5)) levels, always within the reference's 64-entry
+ * stack (scene.h:251).  PT_BVH_DEVICE_LBVH has no cap: the hierarchy of 63-bit codes plus a run of equal codes can be deeper
+ * than 64 levels for adversarial input (centroids a factor of two apart on every level).  The call still returns PT_OK, the
+ * complete tree and its true depth in *out_depth; pt_scene_create accepts a caller's tree of up to 64 levels and rejects a
+ * deeper one with PT_ERR_BAD_SCENE in host code, before anything is launched — check *out_depth, or build with PT_BVH_DEVICE_SAH. */
 enum { PT_BVH_DEVICE_LBVH = 0, PT_BVH_DEVICE_SAH = 1 };
 int pt_bvh_build_device(const pt_scene_desc* desc, int method, pt_bvh_node* out_nodes, int32_t* out_root,
                         int32_t* out_depth, double* out_build_ms);

@@ -208,7 +208,10 @@ int pt_scene_destroy(pt_scene* scene);
  *   pt_scene_get_info: "updates" = successful updates so far; "update_us0".."update_us3" = wall microseconds of the last one:
  *   total, records including uploads, refit of both trees with their octant tables (host time up to its last enqueue: what the
  *   level launches of a large tree still have to execute ends inside the closing synchronise and is in the total alone), the
- *   one-time plan build (0 after the first).  That first update costs more than a pt_scene_create. */
+ *   one-time plan build (0 after the first).  That first update costs more than a pt_scene_create.
+ *   "refit_shape0" / "refit_shape1" = how geometry updates refit the caller's tree / the internal one: 0 no plan (no such tree,
+ *   a one-shape scene, or no geometry update yet), 1 one launch for the whole tree, 2 a scatter, a launch per wide level and
+ *   the single-workgroup launch for the narrow top, 3 a scatter and that single-workgroup launch alone. */
 enum { PT_UPDATE_GEOMETRY = 1, PT_UPDATE_SHADING = 2 };
 int pt_scene_update(pt_scene* scene, const pt_scene_desc* desc, int flags);
 

@@ -2156,6 +2156,12 @@ int pt_scene_get_info(pt_scene* S, const char* key, int64_t* value) {
     else if (k == "prev_geometry") *value = S->have_prev ? 1 : 0;         // records from before the last geometry update are kept (pt_render_guides)
     else if (k == "updates") *value = S->updates;                         // successful pt_scene_update calls so far
     else if (k.rfind("update_us", 0) == 0 && k.size() == 10 && k[9] >= '0' && k[9] <= '3') *value = S->update_us[k[9] - '0'];
+    else if (k == "refit_shape0" || k == "refit_shape1") {
+        // how a geometry update refits tree 0 (the caller's) / 1 (the internal one): 0 no plan (no such tree, a one-shape scene, or
+        // no geometry update yet), 1 one launch, 2 scatter + a launch per wide level + the narrow top, 3 scatter + the narrow top alone
+        const ptf::Plan& pl = S->refit_plan[k[11] - '0'];
+        *value = !pl.built ? 0 : pl.whole_tree ? 1 : pl.narrow_top < pl.levels - 1 ? 2 : 3;
+    }
     else if (k == "kernel") *value = S->info_kernel;                      // the kernel the last render ran on (1, 2 or 3)
     else if (k == "trace_variant") *value = S->info_trace_variant;        // ... and its template arguments (include/pt_api.h)
     else if (k == "path_bank") *value = S->info_path_bank;                // ... which handed out path starts from a register bank (1) or not

@@ -480,21 +480,48 @@ def build_bvh_sweep(desc, on_device=False):
     return d2, {"root": root.value, "depth": depth.value, "build_ms": ms.value, "nodes": nodes}
 
 
-def edited_desc(desc, meshes=None, spheres=None, materials=None, lights=None, background=None):
+def edited_desc(desc, meshes=None, spheres=None, materials=None, lights=None, background=None, shapes=None, mesh_list=None):
     """A copy of `desc` with some of its arrays replaced, for DeviceScene.update and host.refit_bvh.
       meshes      {mesh_index: (positions [V, 3], normals [V, 3] or None = keep the mesh's normals)}
       spheres     {shape_id: (center, radius)}
       materials   a sequence of PtMaterial, as many as desc has       lights   the same with PtLight
       background  (r, g, b)
-    Topology (indices, shape list, node pool) is shared with `desc`; the copy keeps the new arrays, and `desc`, alive."""
+      shapes      a sequence of PtShape that replaces the whole shape list; as many as desc has (ValueError otherwise)
+      mesh_list   a sequence of (positions [V, 3], indices [F, 3], normals [V, 3], material_id, area_light_id) that replaces the
+                  whole mesh table; its length may differ from desc's, and may be 0
+    Every argument defaults to "unchanged".  `meshes` edits the table `mesh_list` gives (or desc's), `spheres` the list `shapes`
+    gives (or desc's).  The node pool is desc's — topology is what an update keeps — and whatever is not replaced is shared
+    with `desc`; the copy keeps the new arrays, and `desc`, alive."""
     d2 = PtSceneDesc()
     C.memmove(C.byref(d2), C.byref(desc), C.sizeof(PtSceneDesc))
     keep = [desc]
+    if mesh_list is not None:
+        mesh_list = list(mesh_list)
+        arr = (PtMesh * max(len(mesh_list), 1))()
+        for m, (pos, idx, nrm, material_id, area_light_id) in enumerate(mesh_list):
+            P = np.ascontiguousarray(pos, dtype=np.float32).reshape(-1, 3)
+            I = np.ascontiguousarray(idx, dtype=np.int32).reshape(-1, 3)
+            Nn = np.ascontiguousarray(nrm, dtype=np.float32).reshape(-1, 3)
+            if Nn.shape != P.shape:
+                raise ValueError("normals must match positions")
+            arr[m] = PtMesh(int(material_id), int(area_light_id), P.shape[0], I.shape[0], _fp(P),
+                            I.ctypes.data_as(C.POINTER(C.c_int32)), _fp(Nn))
+            keep += [P, I, Nn]
+        d2.meshes = arr if mesh_list else None
+        d2.num_meshes = len(mesh_list)
+        keep.append(arr)
+    if shapes is not None:
+        shapes = list(shapes)
+        if len(shapes) != desc.num_shapes:
+            raise ValueError(f"shapes: the count must stay {desc.num_shapes}")
+        arr = (PtShape * desc.num_shapes)(*shapes)
+        d2.shapes = arr
+        keep.append(arr)
     if meshes:
-        arr = (PtMesh * desc.num_meshes)()
-        C.memmove(arr, desc.meshes, C.sizeof(arr))
+        arr = (PtMesh * d2.num_meshes)()
+        C.memmove(arr, d2.meshes, C.sizeof(arr))
         for m, (pos, nrm) in meshes.items():
-            if not 0 <= m < desc.num_meshes:
+            if not 0 <= m < d2.num_meshes:
                 raise ValueError(f"mesh index {m} out of range")
             P = np.ascontiguousarray(pos, dtype=np.float32).reshape(-1, 3)
             if P.shape[0] != arr[m].num_vertices:
@@ -511,7 +538,7 @@ def edited_desc(desc, meshes=None, spheres=None, materials=None, lights=None, ba
         keep.append(arr)
     if spheres:
         arr = (PtShape * desc.num_shapes)()
-        C.memmove(arr, desc.shapes, C.sizeof(arr))
+        C.memmove(arr, d2.shapes, C.sizeof(arr))
         for i, (center, radius) in spheres.items():
             if not 0 <= i < desc.num_shapes or arr[i].type != PT_SHAPE_SPHERE:
                 raise ValueError(f"shape {i} is not a sphere")

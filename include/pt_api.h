@@ -476,6 +476,64 @@ int pt_denoise_variance(pt_scene* scene, const pt_vdenoise_params* d, const floa
 int pt_denoise_variance_host(const pt_vdenoise_params* d, const float* color, const float* albedo, const float* normal,
                              const float* depth, const float* moments, const float* hist_len, float* out, float* out_variance);
 
+/* Temporal gradients: a history that follows light and material changes — an EXTENSION: off unless called, never part of a
+ * parity or roofline number, no other entry point's output changes by a bit.  DESIGN.md §21.
+ *   pt_temporal_accumulate* reject history on depth and normal only, so after pt_scene_update(PT_UPDATE_SHADING) the old lighting
+ *   stays in the image for up to max_history frames.  A pixel's samples depend only on (pixel index, seed, sample_offset,
+ *   stream_stride), so pt_render with the PREVIOUS frame's parameters and a row selection, on the CURRENT scene, re-traces a
+ *   sparse set of the previous frame's samples with the same random numbers: where nothing that the paths of a pixel touch has
+ *   changed the result is the previous frame's, bit for bit.  pt_temporal_gradient turns the difference into a map lambda in
+ *   [0, 1] per tile of stride x stride pixels; pt_temporal_accumulate_adaptive drops that share of a pixel's history.
+ *   fp32, operations in the order written, no contraction, IEEE division. */
+typedef struct pt_gradient_params {
+    int32_t width, height;   /* full frame */
+    int32_t stride;          /* 0 -> 3; else 1..16: strata of stride x stride pixels, one sampled row each */
+    int32_t iterations;      /* 0 -> 3; else 1..8 */
+    float   gain;            /* 0 -> 2; else > 0, finite */
+    float   norm_floor;      /* 0 -> 1e-6; else > 0, finite */
+} pt_gradient_params;        /* 24 bytes */
+
+/* Grid.  With s = stride: r0 = s / 2, TW = (W + s - 1) / s, TH = (H - r0 + s - 1) / s; tile (ty, tx) holds the pixels of rows
+ * s ty .. s ty + s - 1 and columns s tx .. s tx + s - 1 that are in the frame, and its sampled row is r0 + s ty.  H <= r0:
+ * PT_ERR_INVALID_ARG.
+ * prev_color [H, W, 3]: the previous frame's own noisy pt_render output (not an accumulated one).  resampled [TH, W, 3]: what
+ * pt_render / pt_render_async writes for the previous frame's parameters with row_begin = r0, row_end = H, row_stride = s on
+ * the current scene.  lambda_out [TH, TW].  on_device != 0: device pointers, 1 + iterations kernels are enqueued on hip_stream
+ * without a host sync; on_device == 0: host pointers, blocking, staged through memory of the handle.  The handle owns two
+ * ping-pong buffers of 32 bytes per tile, allocated on first use, grown when a larger frame arrives, freed with the scene.
+ * A NULL pointer, a parameter out of range: PT_ERR_INVALID_ARG, pt_last_error() names the argument or field.
+ *   Reduce, tile (ty, tx): y = r0 + s ty; a = b = 0 per channel; for x = s tx .. min(W, s tx + s) - 1 in increasing order
+ *     a_c += prev_color[y, x, c], b_c += resampled[ty, x, c];  d_c = b_c - a_c, m_c = a_c < b_c ? b_c : a_c;
+ *     x_0 = (d_r, d_g, d_b, m_r, m_g, m_b).
+ *   Filter, k = 0 .. iterations - 1, spacing 1 << k on the tile grid, unguided, with pt_denoise's h = {1/16, 1/4, 3/8, 1/4, 1/16}:
+ *     sum = 0 (six components), wsum = 0; taps q = t + (dx, dy) << k, dy = -2..2 (outer), dx = -2..2 (inner); a tap outside the
+ *     grid is skipped and no address is formed for it; w = h[dy + 2] * h[dx + 2], sum += x_k[q] * w, wsum += w;
+ *     x_{k+1}[t] = sum * (1.0f / wsum).
+ *   Final, on x_iterations: r_c = fabsf(d_c) / max(m_c, norm_floor), r = max(max(r_r, r_g), r_b), lambda = min(gain * r, 1.0f).
+ *   Non-finite input propagates; what it does is unspecified.
+ *   A property callers may rely on: prev_color equal to resampled on every sampled row gives lambda == +0 (the bits) at every
+ *   tile — and pt_temporal_accumulate_adaptive then is pt_temporal_accumulate_moments. */
+int pt_temporal_gradient(pt_scene* scene, const pt_gradient_params* g, const float* prev_color, const float* resampled,
+                         float* lambda_out, int on_device, void* hip_stream);
+/* The same per-tile source (csrc/pt_gradient.h) compiled for the HOST: needs no GPU and no scene. */
+int pt_temporal_gradient_host(const pt_gradient_params* g, const float* prev_color, const float* resampled, float* lambda_out);
+
+/* pt_temporal_accumulate_moments with pt_temporal_gradient's map.  Buffers, call forms, aliases, staging and errors are
+ * pt_temporal_accumulate_moments'.  lambda [TH, TW] and stride (0 -> 3; else 1..16) are the map and the stride of the
+ * pt_temporal_gradient call for the same frame size; lambda == NULL, a stride out of range, H <= r0: PT_ERR_INVALID_ARG,
+ * pt_last_error() names lambda, stride or height.  With no history lambda is never read.
+ *   The rule per pixel p: steps 1-7 of pt_temporal_accumulate_moments unchanged.  In step 8 (wsum > 0), after n:
+ *     a0 = 1.0f / n;  jx = (int)floorf(motion.x) clamped to [0, W - 1], jy = (int)floorf(motion.y) clamped to [0, H - 1];
+ *     tx = jx / s, ty = min(jy / s, TH - 1);  l = lambda[ty * TW + tx];  L = l > 1.0f ? 1.0f : l  (min; a NaN stays a NaN).
+ *     L > 0:  a = a0 + L * (1.0f - a0);  out = h + (c - h) * a, out_moments = mh + (m_c - mh) * a, out_len = 1.0f / a.
+ *     Otherwise (L is 0, negative or NaN): every output of the pixel is pt_temporal_accumulate_moments', bit for bit.
+ *   L == 1 gives a == 1: out = h + (c - h), out_len = 1 — the history is dropped up to one rounding. */
+int pt_temporal_accumulate_adaptive(pt_scene* scene, const pt_temporal_params* t, float albedo_floor, const pt_temporal_io* io,
+                                    const float* lambda, int32_t stride, int on_device, void* hip_stream);
+/* The same per-pixel source (csrc/pt_temporal.h) compiled for the HOST: needs no GPU and no scene. */
+int pt_temporal_accumulate_adaptive_host(const pt_temporal_params* t, float albedo_floor, const pt_temporal_io* io,
+                                         const float* lambda, int32_t stride);
+
 int pt_get_counters(pt_scene* scene, pt_counters* out);   /* synchronises the scene's last stream */
 
 /* HIP-event times of the last render calls on the scene, oldest first: kernel_ms[k] / resolve_ms[k] of up to max_frames calls,

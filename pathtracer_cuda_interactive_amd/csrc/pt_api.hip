@@ -23,6 +23,7 @@
 #include "pt_scene_prep.h"
 #include "pt_scene_refit.h"
 #include "pt_denoise.h"
+#include "pt_gradient.h"
 #include "pt_temporal.h"
 #include "pt_kernels.h"
 #include "pt_kernel_q.h"
@@ -206,6 +207,10 @@ struct pt_scene {
     // call that comes in host memory
     DevBuf<float4> vd_guide, vd_x[2];
     DevBuf<float> vd_host;
+    // pt_temporal_gradient: the two ping-pong tile records (pt_gradient.h, two float4 per tile), allocated on first use and
+    // grown when a larger frame arrives, and staging of a call that comes in host memory
+    DevBuf<float4> gr_x[2];
+    DevBuf<float> gr_host;
     // What a frame's trace kernel writes lives in a frame slot; render call k uses slot k % frames_in_flight.  With more than one
     // slot a single-pass frame runs on the slot's own stream: the trace kernel at once (it reads the immutable scene and writes
     // the slot only), the resolve — the one step that touches the caller's buffer — once the caller's stream has reached the
@@ -1731,14 +1736,28 @@ int run_staged(const char* fn, int on_device, void* hip_stream, DevBuf<float>& s
     return PT_OK;
 }
 
-// pt_temporal_accumulate (moments = false) and pt_temporal_accumulate_moments
+// The lambda map of pt_temporal_accumulate_adaptive and its host twin, after temporal_args: the pointer, the stride, the tile grid.
+int adaptive_args(const char* fn, const ptt::Resolved& r, const float* lambda, int32_t stride, ptt::Lambda* lam) {
+    const std::string pre = std::string(fn) + ": ";
+    if (!lambda) return fail(PT_ERR_INVALID_ARG, pre + "null lambda");
+    if (stride < 0 || stride > 16) return fail(PT_ERR_INVALID_ARG, pre + "stride out of range");
+    int32_t r0;
+    *lam = ptt::Lambda{lambda, stride ? stride : 3, 0, 0};
+    if (!ptg::tile_grid(r.width, r.height, lam->stride, &r0, &lam->tw, &lam->th))
+        return fail(PT_ERR_INVALID_ARG, pre + "height: no sampled row (height <= stride / 2)");
+    return PT_OK;
+}
+
+// pt_temporal_accumulate (moments = false), pt_temporal_accumulate_moments and, with a lambda map, pt_temporal_accumulate_adaptive
 int temporal_call(const char* fn, bool moments, pt_scene* S, const pt_temporal_params* t, float albedo_floor, const pt_temporal_io* io_in,
-                  int on_device, void* hip_stream) {
+                  int on_device, void* hip_stream, bool adaptive = false, const float* lambda = nullptr, int32_t stride = 0) {
     if (!S) return fail(PT_ERR_INVALID_ARG, std::string(fn) + ": null scene");
     ptt::Resolved r;
     float floor_v;
     int rc = temporal_args(fn, moments, t, albedo_floor, io_in, &r, &floor_v);
     if (rc) return rc;
+    ptt::Lambda lam{};
+    if (adaptive && (rc = adaptive_args(fn, r, lambda, stride, &lam))) return rc;
     DeviceGuard guard;
     { int grc = guard.enter(S->device); if (grc) return grc; }
     pt_temporal_io io = *io_in;
@@ -1747,8 +1766,64 @@ int temporal_call(const char* fn, bool moments, pt_scene* S, const pt_temporal_p
                             {&io.hist_color, nullptr, 3}, {&io.hist_normal, nullptr, 3}, {&io.hist_depth, nullptr, 1},
                             {&io.hist_len, nullptr, 1}, {&io.hist_moments, nullptr, moments ? 2 : 0},
                             {nullptr, &io.out_color, 3}, {nullptr, &io.out_len, 1}, {nullptr, &io.out_moments, moments ? 2 : 0}};
-    return run_staged(fn, on_device, hip_stream, S->tp_host, (size_t)r.width * (size_t)r.height, planes,
-                      [&](void* stream) { return ptt::run_device(r, moments, floor_v, io, stream); });
+    // a staged adaptive call: the map rides behind the planes of the staging buffer (at most one float per pixel: a plane more)
+    const Plane planes_lam[] = {planes[0], planes[1], planes[2], planes[3], planes[4], planes[5], planes[6], planes[7], planes[8],
+                                planes[9], planes[10], planes[11], planes[12], {nullptr, nullptr, 1}};
+    const size_t npix = (size_t)r.width * (size_t)r.height;
+    if (adaptive && !on_device) {
+        // no history: the map is never read, and need not be readable
+        const bool read = io.hist_color != nullptr;
+        size_t floats = 0;
+        for (const Plane& pl : planes) floats += (size_t)pl.floats;
+        return run_staged(fn, 0, hip_stream, S->tp_host, npix, planes_lam, [&](void* stream) {
+            float* d_lam = S->tp_host.p + npix * floats;
+            if (read) {
+                const hipError_t e = hipMemcpy(d_lam, lam.map, (size_t)lam.tw * (size_t)lam.th * sizeof(float), hipMemcpyHostToDevice);
+                if (e != hipSuccess) return (int)e;
+            }
+            lam.map = d_lam;
+            return ptt::run_device(r, true, floor_v, io, &lam, stream);
+        });
+    }
+    return run_staged(fn, on_device, hip_stream, S->tp_host, npix, planes,
+                      [&](void* stream) { return ptt::run_device(r, moments, floor_v, io, adaptive ? &lam : nullptr, stream); });
+}
+
+// pt_temporal_gradient behind its argument checks: the record buffers, then the kernels; a call that comes in host memory is
+// staged through one buffer of the handle (the two frames in, the map out) on the default stream.
+int gradient_call(pt_scene* S, const ptg::Resolved& r, const float* prev_color, const float* resampled, float* lambda_out, int on_device,
+                  void* hip_stream) {
+    const char* fn = "pt_temporal_gradient";
+    DeviceGuard guard;
+    { int grc = guard.enter(S->device); if (grc) return grc; }
+    const size_t ntiles = (size_t)r.tw * (size_t)r.th;
+    int rc;
+    if ((rc = S->gr_x[0].ensure(2 * ntiles)) || (rc = S->gr_x[1].ensure(2 * ntiles))) return rc;
+    auto launch = [&](const float* a, const float* b, float* out, void* stream) {
+        const hipError_t e = (hipError_t)ptg::run_device(r, a, b, out, S->gr_x[0].p, S->gr_x[1].p, stream);
+        return e != hipSuccess ? fail(PT_ERR_DEVICE, std::string(fn) + ": " + hipGetErrorString(e)) : PT_OK;
+    };
+    if (on_device) return launch(prev_color, resampled, lambda_out, hip_stream);
+    const size_t n_prev = (size_t)r.width * (size_t)r.height * 3, n_res = (size_t)r.width * (size_t)r.th * 3;
+    if ((rc = S->gr_host.ensure(n_prev + n_res + ntiles))) return rc;
+    float *d_prev = S->gr_host.p, *d_res = d_prev + n_prev, *d_lam = d_res + n_res;
+    HIP_TRY(hipMemcpy(d_prev, prev_color, n_prev * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_res, resampled, n_res * sizeof(float), hipMemcpyHostToDevice));
+    if ((rc = launch(d_prev, d_res, d_lam, nullptr))) return rc;
+    HIP_TRY(hipMemcpy(lambda_out, d_lam, ntiles * sizeof(float), hipMemcpyDeviceToHost));
+    return PT_OK;
+}
+
+// Arguments of pt_temporal_gradient and its host twin.
+int gradient_args(const char* fn, const pt_gradient_params* g, const float* prev_color, const float* resampled, const float* lambda_out,
+                  ptg::Resolved* r) {
+    const std::string pre = std::string(fn) + ": ";
+    if (!g) return fail(PT_ERR_INVALID_ARG, pre + "null pt_gradient_params");
+    if (!prev_color) return fail(PT_ERR_INVALID_ARG, pre + "null prev_color");
+    if (!resampled) return fail(PT_ERR_INVALID_ARG, pre + "null resampled");
+    if (!lambda_out) return fail(PT_ERR_INVALID_ARG, pre + "null lambda_out");
+    if (const char* bad = ptg::resolve(g, r)) return fail(PT_ERR_INVALID_ARG, std::string("pt_gradient_params.") + bad + " out of range");
+    return PT_OK;
 }
 
 // pt_denoise and pt_denoise_variance behind their argument checks: the record buffers, then the kernels.  The frame is
@@ -1818,6 +1893,7 @@ int pt_scene_destroy(pt_scene* S) {
     S->ad_spp_tmp.release(); S->ad_err_tmp.release();
     S->dn_guide.release(); S->dn_x[0].release(); S->dn_x[1].release(); S->dn_host.release(); S->tp_host.release();
     S->vd_guide.release(); S->vd_x[0].release(); S->vd_x[1].release(); S->vd_host.release();
+    S->gr_x[0].release(); S->gr_x[1].release(); S->gr_host.release();
     S->st_prims.release(); S->prev_prims.release(); S->st_normals.release(); S->st_boxes.release(); S->st_status.release();
     for (auto& pl : S->refit_plan) ptf::plan_release(&pl);
     S->drop_events();
@@ -2004,6 +2080,45 @@ int pt_temporal_accumulate_moments_host(const pt_temporal_params* t, float albed
     int rc = temporal_args("pt_temporal_accumulate_moments", true, t, albedo_floor, io, &r, &floor_v);
     if (rc) return rc;
     ptt::run_host(r, true, floor_v, *io);
+    return PT_OK;
+}
+
+int pt_temporal_gradient(pt_scene* S, const pt_gradient_params* g, const float* prev_color, const float* resampled, float* lambda_out,
+                         int on_device, void* hip_stream) {
+    if (!S) return fail(PT_ERR_INVALID_ARG, "pt_temporal_gradient: null scene");
+    ptg::Resolved r;
+    int rc = gradient_args("pt_temporal_gradient", g, prev_color, resampled, lambda_out, &r);
+    if (rc) return rc;
+    return gradient_call(S, r, prev_color, resampled, lambda_out, on_device, hip_stream);
+}
+
+int pt_temporal_gradient_host(const pt_gradient_params* g, const float* prev_color, const float* resampled, float* lambda_out) {
+    ptg::Resolved r;
+    int rc = gradient_args("pt_temporal_gradient_host", g, prev_color, resampled, lambda_out, &r);
+    if (rc) return rc;
+    try {
+        ptg::run_host(r, prev_color, resampled, lambda_out);
+    } catch (const std::exception& e) {
+        return fail(PT_ERR_DEVICE, std::string("pt_temporal_gradient_host: ") + e.what());
+    }
+    return PT_OK;
+}
+
+int pt_temporal_accumulate_adaptive(pt_scene* S, const pt_temporal_params* t, float albedo_floor, const pt_temporal_io* io,
+                                    const float* lambda, int32_t stride, int on_device, void* hip_stream) {
+    return temporal_call("pt_temporal_accumulate_adaptive", true, S, t, albedo_floor, io, on_device, hip_stream, true, lambda, stride);
+}
+
+int pt_temporal_accumulate_adaptive_host(const pt_temporal_params* t, float albedo_floor, const pt_temporal_io* io, const float* lambda,
+                                         int32_t stride) {
+    const char* fn = "pt_temporal_accumulate_adaptive";
+    ptt::Resolved r;
+    float floor_v;
+    int rc = temporal_args(fn, true, t, albedo_floor, io, &r, &floor_v);
+    if (rc) return rc;
+    ptt::Lambda lam{};
+    if ((rc = adaptive_args(fn, r, lambda, stride, &lam))) return rc;
+    ptt::run_host(r, true, floor_v, *io, &lam);
     return PT_OK;
 }
 

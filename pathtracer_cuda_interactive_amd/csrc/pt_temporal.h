@@ -1,8 +1,9 @@
 // pt_temporal.h — the per-pixel rules of pt_render_guides' motion part and of pt_temporal_accumulate (include/pt_api.h,
 // DESIGN.md §19), written once for the device (aov_kernel<., true> in pt_kernels.h, pt_temporal.hip) and for the host twin
 // pt_temporal_accumulate_host.  pt_temporal_accumulate_moments is the same function, accumulate_pixel, with
-// MOMENTS = true: it carries two luminance moments on the same taps.  The host twins' frame loop, run_host, is here too, so a
-// plain host compile of this header runs what pt_temporal_accumulate*_host run (tests/native/post_rules_check.cpp).
+// MOMENTS = true: it carries two luminance moments on the same taps, and pt_temporal_accumulate_adaptive is that
+// with ADAPTIVE = true: pt_temporal_gradient's per-tile lambda shortens the history.  The host twins' frame loop, run_host, is
+// here too, so a plain host compile of this header runs what pt_temporal_accumulate*_host run (tests/native/post_rules_check.cpp).
 //
 // Every operation is an IEEE fp32 + - * / sqrt in the order written (no contraction: the build forbids it), so the device, the
 // host twin and a numpy restatement give the same bits.
@@ -73,13 +74,21 @@ inline const char* resolve(const pt_temporal_params* t, Resolved* r) {
     return nullptr;
 }
 
+// pt_temporal_gradient's map as pt_temporal_accumulate_adaptive reads it: [th, tw] tiles of stride x stride pixels
+struct Lambda {
+    const float* map;
+    int32_t stride, tw, th;
+};
+
 // One pixel of pt_temporal_accumulate (MOMENTS = false) and of pt_temporal_accumulate_moments (MOMENTS = true: the same
 // colour and length from the same instantiation of every line, and the first two moments of the demodulated luminance carried
 // on the same taps with the same weights).  io.hist_color == nullptr: no history.  The four tap addresses are formed only
 // after the clip to the frame.  io.out_color may be io.color: a pixel reads only its own colour.  MOMENTS = false never reads
-// io.albedo, io.hist_moments or io.out_moments (they are null there) nor albedo_floor.
-template <bool MOMENTS>
-PT_HD void accumulate_pixel(const Resolved& r, float albedo_floor, int px, int py, const pt_temporal_io& io) {
+// io.albedo, io.hist_moments or io.out_moments (they are null there) nor albedo_floor.  ADAPTIVE = true (with MOMENTS):
+// pt_temporal_accumulate_adaptive — a pixel that continues a history reads the lambda of the tile its motion vector lands in and,
+// where that is positive, blends with a larger weight; lam is read in no other case.
+template <bool MOMENTS, bool ADAPTIVE = false>
+PT_HD void accumulate_pixel(const Resolved& r, float albedo_floor, int px, int py, const pt_temporal_io& io, const Lambda& lam = Lambda{}) {
     const size_t p = (size_t)py * (size_t)r.width + (size_t)px;
     const float cr = io.color[3 * p] * r.scale, cg = io.color[3 * p + 1] * r.scale, cb = io.color[3 * p + 2] * r.scale;
     float m1 = 0.0f, m2 = 0.0f;
@@ -123,9 +132,25 @@ PT_HD void accumulate_pixel(const Resolved& r, float albedo_floor, int px, int p
                 const float inv = 1.0f / wsum;
                 const float hr = sr * inv, hg = sg * inv, hb = sb * inv;
                 const float n = ptm::fmin2(lsum * inv + 1.0f, r.max_history);
-                const float a = 1.0f / n;
+                float a = 1.0f / n;
+                if constexpr (ADAPTIVE) {
+                    int jx = (int)__builtin_floorf(io.motion[2 * p]), jy = (int)__builtin_floorf(io.motion[2 * p + 1]);
+                    jx = jx < 0 ? 0 : (jx > r.width - 1 ? r.width - 1 : jx);
+                    jy = jy < 0 ? 0 : (jy > r.height - 1 ? r.height - 1 : jy);
+                    const int tx = jx / lam.stride, ty_raw = jy / lam.stride;
+                    const int ty = ty_raw > lam.th - 1 ? lam.th - 1 : ty_raw;
+                    const float lv = lam.map[(size_t)ty * (size_t)lam.tw + (size_t)tx];
+                    const float L = lv > 1.0f ? 1.0f : lv;                              // a NaN stays one and fails the next test
+                    if (L > 0.0f) {
+                        a = a + L * (1.0f - a);
+                        o_len = 1.0f / a;
+                    } else {
+                        o_len = n;
+                    }
+                } else {
+                    o_len = n;
+                }
                 o_r = hr + (cr - hr) * a; o_g = hg + (cg - hg) * a; o_b = hb + (cb - hb) * a;
-                o_len = n;
                 if constexpr (MOMENTS) {
                     const float h1 = ms1 * inv, h2 = ms2 * inv;
                     o_m1 = h1 + (m1 - h1) * a; o_m2 = h2 + (m2 - h2) * a;
@@ -138,14 +163,16 @@ PT_HD void accumulate_pixel(const Resolved& r, float albedo_floor, int px, int p
     if constexpr (MOMENTS) { io.out_moments[2 * p] = o_m1; io.out_moments[2 * p + 1] = o_m2; }
 }
 
-// Device side (pt_temporal.hip): one kernel on `stream`, no host sync.  Returns a hipError_t.
-int run_device(const Resolved& r, bool moments, float albedo_floor, const pt_temporal_io& io, void* hip_stream);
+// Device side (pt_temporal.hip): one kernel on `stream`, no host sync.  lam: nullptr, or (with moments) the map of
+// pt_temporal_accumulate_adaptive.  Returns a hipError_t.
+int run_device(const Resolved& r, bool moments, float albedo_floor, const pt_temporal_io& io, const Lambda* lam, void* hip_stream);
 
 // Host twin: the same function over the frame.
-inline void run_host(const Resolved& r, bool moments, float albedo_floor, const pt_temporal_io& io) {
+inline void run_host(const Resolved& r, bool moments, float albedo_floor, const pt_temporal_io& io, const Lambda* lam = nullptr) {
     for (int py = 0; py < r.height; py++)
         for (int px = 0; px < r.width; px++) {
-            if (moments) accumulate_pixel<true>(r, albedo_floor, px, py, io);
+            if (lam) accumulate_pixel<true, true>(r, albedo_floor, px, py, io, *lam);
+            else if (moments) accumulate_pixel<true>(r, albedo_floor, px, py, io);
             else accumulate_pixel<false>(r, albedo_floor, px, py, io);
         }
 }

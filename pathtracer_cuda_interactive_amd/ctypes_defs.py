@@ -129,6 +129,12 @@ class PtVdenoiseParams(C.Structure):
                 ("min_history", C.c_int32), ("var_floor", C.c_float)]
 
 
+class PtGradientParams(C.Structure):
+    """pt_gradient_params (pt_api.h): the tile grid, filter and gain of pt_temporal_gradient."""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("stride", C.c_int32), ("iterations", C.c_int32),
+                ("gain", C.c_float), ("norm_floor", C.c_float)]
+
+
 class PtCamera(C.Structure):
     _fields_ = [("lookfrom", c_float3), ("lookat", c_float3), ("up", c_float3), ("vfov", C.c_float),
                 ("width", C.c_int32), ("height", C.c_int32), ("spp", C.c_int32)]

@@ -11,7 +11,7 @@ import numpy as np
 from . import _build
 from .ctypes_defs import (PT_MOTION_GEOMETRY_CURRENT, PT_MOTION_GEOMETRY_PREVIOUS, PT_OK, PT_SHAPE_SPHERE, PT_TRAVERSAL_DEFAULT,
                           PT_UPDATE_GEOMETRY, PT_UPDATE_SHADING, PtAdaptiveParams, PtBvhNode, PtCounters, PtDenoiseParams, PtError,
-                          PtGuideBuffers, PtLight, PtMaterial, PtMesh, PtMotionParams, PtRenderParams, PtSceneDesc, PtShape,
+                          PtGradientParams, PtGuideBuffers, PtLight, PtMaterial, PtMesh, PtMotionParams, PtRenderParams, PtSceneDesc, PtShape,
                           PtTemporalIo, PtTemporalParams, PtVdenoiseParams)
 from .host import NODE_DTYPE  # noqa: F401  (one definition; callers also read it from here)
 
@@ -24,6 +24,7 @@ EXPORTS = [
     "pt_debug_exact_math", "pt_render_adaptive", "pt_render_aov", "pt_denoise", "pt_denoise_host", "pt_scene_update",
     "pt_render_guides", "pt_temporal_accumulate", "pt_temporal_accumulate_host",
     "pt_temporal_accumulate_moments", "pt_temporal_accumulate_moments_host", "pt_denoise_variance", "pt_denoise_variance_host",
+    "pt_temporal_gradient", "pt_temporal_gradient_host", "pt_temporal_accumulate_adaptive", "pt_temporal_accumulate_adaptive_host",
 ]
 
 
@@ -56,6 +57,11 @@ def lib():
         L.pt_temporal_accumulate_moments_host.argtypes = [C.POINTER(PtTemporalParams), C.c_float, C.POINTER(PtTemporalIo)]
         L.pt_denoise_variance.argtypes = [vp, C.POINTER(PtVdenoiseParams)] + [vp] * 8 + [C.c_int, vp]
         L.pt_denoise_variance_host.argtypes = [C.POINTER(PtVdenoiseParams)] + [vp] * 8
+        L.pt_temporal_gradient.argtypes = [vp, C.POINTER(PtGradientParams), vp, vp, vp, C.c_int, vp]
+        L.pt_temporal_gradient_host.argtypes = [C.POINTER(PtGradientParams), vp, vp, vp]
+        L.pt_temporal_accumulate_adaptive.argtypes = [vp, C.POINTER(PtTemporalParams), C.c_float, C.POINTER(PtTemporalIo), vp, C.c_int32,
+                                                      C.c_int, vp]
+        L.pt_temporal_accumulate_adaptive_host.argtypes = [C.POINTER(PtTemporalParams), C.c_float, C.POINTER(PtTemporalIo), vp, C.c_int32]
         L.pt_get_counters.argtypes = [vp, C.POINTER(PtCounters)]
         L.pt_get_frame_times.argtypes = [vp, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int)]
         L.pt_scene_set_option.argtypes = [vp, C.c_char_p, C.c_int64]
@@ -267,6 +273,45 @@ class DeviceScene:
                           out_color_ptr, out_len_ptr, out_moments_ptr)
         _check(lib().pt_temporal_accumulate_moments(self._h, C.byref(t), float(albedo_floor), C.byref(io), 1, C.c_void_p(stream or 0)))
 
+    def temporal_gradient(self, prev_color, resampled, **kw):
+        """pt_temporal_gradient on host arrays (prev_color [H, W, 3]: the previous frame's noisy render; resampled [TH, W, 3]: the
+        render of gradient_rows_params(previous parameters, stride) on the current scene): lambda [TH, TW] as a new array.
+        Keywords: the fields of pt_gradient_params (gradient_params)."""
+        prev_color, resampled, g, shape = _gradient_args(prev_color, resampled, kw)
+        out = np.empty(shape, dtype=np.float32)
+        _check(lib().pt_temporal_gradient(self._h, C.byref(g), *_ptrs([prev_color, resampled, out]), 0, None))
+        return out
+
+    def temporal_gradient_into(self, width, height, prev_color_ptr, resampled_ptr, lambda_ptr, stream=None, **kw):
+        """pt_temporal_gradient on device memory, enqueued on a HIP stream without a host sync (lambda_ptr: [TH, TW] float32, the
+        shape gradient_grid gives)."""
+        g = gradient_params(width, height, **kw)
+        _check(lib().pt_temporal_gradient(self._h, C.byref(g), C.c_void_p(prev_color_ptr), C.c_void_p(resampled_ptr),
+                                          C.c_void_p(lambda_ptr), 1, C.c_void_p(stream or 0)))
+
+    def temporal_accumulate_adaptive(self, color, albedo, normal, motion, prev_depth, lam, history=None, stride=0, albedo_floor=0.0,
+                                     **kw):
+        """pt_temporal_accumulate_adaptive on host arrays: temporal_accumulate_moments with the map `lam` [TH, TW] of
+        temporal_gradient at `stride`.  Returns (out_color, out_len, out_moments) as new arrays."""
+        args, t = _temporal_moments_args(color, albedo, normal, motion, prev_depth, history, kw)
+        lam = _lambda_arg(lam, args[4].shape, stride)
+        outs = [np.empty_like(args[0]), np.empty_like(args[4]), np.empty_like(args[3])]
+        io = PtTemporalIo(*_ptrs(args + outs))
+        _check(lib().pt_temporal_accumulate_adaptive(self._h, C.byref(t), float(albedo_floor), C.byref(io), *_ptrs([lam]), int(stride),
+                                                     0, None))
+        return tuple(outs)
+
+    def temporal_accumulate_adaptive_into(self, width, height, color_ptr, albedo_ptr, normal_ptr, motion_ptr, prev_depth_ptr, hist_ptrs,
+                                          out_color_ptr, out_len_ptr, out_moments_ptr, lambda_ptr, stride=0, stream=None,
+                                          albedo_floor=0.0, **kw):
+        """pt_temporal_accumulate_adaptive on device memory, enqueued on a HIP stream without a host sync: the arguments of
+        temporal_accumulate_moments_into, and the map temporal_gradient_into wrote with the same stride."""
+        t = temporal_params(width, height, **kw)
+        io = PtTemporalIo(color_ptr, albedo_ptr, normal_ptr, motion_ptr, prev_depth_ptr, *(hist_ptrs if hist_ptrs else [None] * 5),
+                          out_color_ptr, out_len_ptr, out_moments_ptr)
+        _check(lib().pt_temporal_accumulate_adaptive(self._h, C.byref(t), float(albedo_floor), C.byref(io), C.c_void_p(lambda_ptr),
+                                                     int(stride), 1, C.c_void_p(stream or 0)))
+
     def denoise_variance(self, color, albedo, normal, depth, moments, hist_len, variance=False, **kw):
         """pt_denoise_variance on host arrays (moments [H, W, 2] and hist_len [H, W] from temporal_accumulate_moments): the
         filtered frame as a new array, or (frame, variance [H, W]) with variance=True.  Keywords: the fields of
@@ -412,6 +457,75 @@ def temporal_accumulate_moments_host(color, albedo, normal, motion, prev_depth, 
     outs = [out_color, np.empty_like(args[4]), np.empty_like(args[3])]
     io = PtTemporalIo(*_ptrs(args + outs))
     _check(lib().pt_temporal_accumulate_moments_host(C.byref(t), float(albedo_floor), C.byref(io)))
+    return tuple(outs)
+
+
+def gradient_params(width, height, stride=0, iterations=0, gain=0.0, norm_floor=0.0):
+    """pt_gradient_params; 0 = the library's default (stride 3, 3 iterations, gain 2, norm_floor 1e-6)."""
+    return PtGradientParams(int(width), int(height), int(stride), int(iterations), float(gain), float(norm_floor))
+
+
+def gradient_grid(width, height, stride=0):
+    """(r0, TH, TW) of pt_temporal_gradient's tile grid: the first sampled row and the shape of the lambda map."""
+    s = int(stride) or 3
+    r0 = s // 2
+    if not 1 <= s <= 16 or height <= r0:
+        raise ValueError("gradient_grid: stride must be 0 or 1..16 and height > stride // 2")
+    return r0, (height - r0 + s - 1) // s, (width + s - 1) // s
+
+
+def gradient_rows_params(prev_params, stride=0):
+    """A copy of the previous frame's PtRenderParams with the row selection pt_temporal_gradient's `resampled` is rendered with:
+    row_begin = stride // 2, row_end = height, row_stride = stride (0 = the default, 3)."""
+    q = prev_params.copy()
+    r0, _, _ = gradient_grid(q.width, q.height, stride)
+    q.row_begin, q.row_end, q.row_stride = r0, q.height, int(stride) or 3
+    return q
+
+
+def _gradient_args(prev_color, resampled, kw):
+    prev_color, resampled = (np.ascontiguousarray(a, dtype=np.float32) for a in (prev_color, resampled))
+    if prev_color.ndim != 3 or prev_color.shape[2] != 3:
+        raise ValueError("temporal_gradient: prev_color must be [H, W, 3]")
+    H, W = prev_color.shape[:2]
+    g = gradient_params(W, H, **kw)
+    _, TH, TW = gradient_grid(W, H, g.stride)
+    if resampled.shape != (TH, W, 3):
+        raise ValueError(f"temporal_gradient: resampled must be [{TH}, {W}, 3] (the rows of gradient_rows_params)")
+    return prev_color, resampled, g, (TH, TW)
+
+
+def temporal_gradient_host(prev_color, resampled, **kw):
+    """pt_temporal_gradient_host: the rule of pt_temporal_gradient run by the host half of the library (no GPU needed).  Returns
+    lambda [TH, TW]."""
+    prev_color, resampled, g, shape = _gradient_args(prev_color, resampled, kw)
+    out = np.empty(shape, dtype=np.float32)
+    _check(lib().pt_temporal_gradient_host(C.byref(g), *_ptrs([prev_color, resampled, out])))
+    return out
+
+
+def _lambda_arg(lam, frame_shape, stride):
+    lam = np.ascontiguousarray(lam, dtype=np.float32)
+    H, W = frame_shape
+    try:
+        shape = gradient_grid(W, H, stride)[1:]
+    except ValueError:
+        return lam                                                # a stride or frame the library rejects, naming it
+    if lam.shape != shape:
+        raise ValueError("temporal_accumulate_adaptive: lam must be the [TH, TW] map of temporal_gradient at this stride")
+    return lam
+
+
+def temporal_accumulate_adaptive_host(color, albedo, normal, motion, prev_depth, lam, history=None, stride=0, out_color=None,
+                                      albedo_floor=0.0, **kw):
+    """pt_temporal_accumulate_adaptive_host: the rule of pt_temporal_accumulate_adaptive run by the host half of the library (no
+    GPU needed).  Returns (out_color, out_len, out_moments); out_color as in temporal_accumulate_moments_host."""
+    args, t = _temporal_moments_args(color, albedo, normal, motion, prev_depth, history, kw)
+    lam = _lambda_arg(lam, args[4].shape, stride)
+    out_color = _out_like(out_color, args[0], "temporal_accumulate_adaptive_host: out_color")
+    outs = [out_color, np.empty_like(args[4]), np.empty_like(args[3])]
+    io = PtTemporalIo(*_ptrs(args + outs))
+    _check(lib().pt_temporal_accumulate_adaptive_host(C.byref(t), float(albedo_floor), C.byref(io), *_ptrs([lam]), int(stride)))
     return tuple(outs)
 
 

@@ -1,7 +1,7 @@
 """N frames of a .pts scene under a moving camera and, optionally, wobbling meshes, cleaned in image space.
 
   python tools/animate.py SCENE.pts [--frames 8] [--size 640x480] [--spp 2] [--translate DX,DY,DZ | --orbit DEG] [--wobble]
-                          [--denoise | --variance] [--reference-spp N] [--out PREFIX] [--time]
+                          [--denoise | --variance | --gradient] [--relight K:R,G,B] [--reference-spp N] [--out PREFIX] [--time]
 
 Per frame: pt_render at --spp, pt_render_guides against the previous frame's camera (and, with --wobble, the previous
 geometry: every mesh gets device.wobbled_desc's per-vertex wobble through DeviceScene.update), pt_temporal_accumulate, and with
@@ -11,6 +11,10 @@ pt_render of that many samples on the same geometry.  --translate is in units of
 frame (default 0.02,0.008,-0.013); --orbit turns the camera about its look-at point by that many degrees per frame instead.
 --variance: the temporal stage is pt_temporal_accumulate_moments and the spatial stage pt_denoise_variance on
 its colour, moments and history length (stages "accumulate_moments" and "denoise_variance", image _variance.ppm).
+--gradient (implies --variance): from the second frame on, pt_render of the previous frame's parameters on every
+third row of the current scene (stage "rows"), pt_temporal_gradient of the previous noisy frame against it (stage "gradient"),
+and pt_temporal_accumulate_adaptive with that map in place of pt_temporal_accumulate_moments (stage "accumulate_adaptive").
+--relight K:R,G,B: from frame K on every light's radiance is scaled by (R, G, B) through DeviceScene.update(shading=True).
 --time: after the animation, each stage again on the last frame's inputs, warm, in windows of at least 0.5 s, with
 pt_render_aov and one pt_denoise iteration as yardsticks and the bytes pt_temporal_accumulate must move."""
 import argparse
@@ -24,6 +28,7 @@ import torch
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 from pathtracer_cuda_interactive_amd import PT_BVH_SORT_REFERENCE, HostScene, host  # noqa: E402
+from pathtracer_cuda_interactive_amd import ctypes_defs as cd  # noqa: E402
 from pathtracer_cuda_interactive_amd import device as dev  # noqa: E402
 
 HBM_BYTES_PER_S = 6.29e12          # measured float4 copy rate of the MI355X
@@ -79,6 +84,13 @@ def rmse(a, b):
     return float(np.sqrt(np.mean((a.astype(np.float64) - b.astype(np.float64)) ** 2)))
 
 
+def relit_desc(desc, factor):
+    """A copy of `desc` with every light's radiance scaled per channel."""
+    lights = [cd.PtLight(l.type, l.shape_id, cd.c_float3(*(float(np.float32(c) * np.float32(f)) for c, f in zip(l.radiance, factor))),
+                         cd.c_float3(*l.position)) for l in (desc.lights[k] for k in range(desc.num_lights))]
+    return dev.edited_desc(desc, lights=lights)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("scene")
@@ -90,10 +102,16 @@ def main():
     ap.add_argument("--wobble", action="store_true")
     ap.add_argument("--denoise", action="store_true")
     ap.add_argument("--variance", action="store_true")
+    ap.add_argument("--gradient", action="store_true")
+    ap.add_argument("--relight", default="")
     ap.add_argument("--reference-spp", type=int, default=0)
     ap.add_argument("--out", default="")
     ap.add_argument("--time", action="store_true")
     a = ap.parse_args()
+    a.variance = a.variance or a.gradient
+    relight_at, relight_factor = None, None
+    if a.relight:
+        relight_at, relight_factor = int(a.relight.split(":")[0]), [float(v) for v in a.relight.split(":")[1].split(",")]
     w, h = (int(v) for v in a.size.split("x"))
     hs = HostScene.load(a.scene)
     d0 = hs.finalize(PT_BVH_SORT_REFERENCE)
@@ -109,6 +127,12 @@ def main():
     if a.variance:
         for st in sets:
             st["moments"] = torch.empty((h, w, 2), device="cuda")
+    if a.gradient:
+        # the noisy frame is kept for the next frame's gradient; the re-traced rows and the map
+        for st in sets:
+            st["color"] = f3()
+        _, th, tw = dev.gradient_grid(w, h)
+        rows, lam = torch.empty((th, w, 3), device="cuda"), torch.zeros((th, tw), device="cuda")
     p0 = hs.render_params(w, h, a.spp)
     ds.render_aov_into(p0, 0, 0, sets[0]["depth"].data_ptr(), 0)
     z = sets[0]["depth"]
@@ -116,6 +140,8 @@ def main():
     stages = ["render", "guides", "accumulate"] + (["denoise"] if a.denoise else [])
     if a.variance:
         stages = ["render", "guides", "accumulate_moments", "denoise_variance"]
+    if a.gradient:
+        stages = ["render", "rows", "gradient", "guides", "accumulate_adaptive", "denoise_variance"]
     times = {s: [] for s in stages}
     errors = {s: [] for s in ("noisy", "accumulated", "denoised", "variance")}
     p_prev = None
@@ -124,19 +150,36 @@ def main():
         p.seed = 1984 + k
         cur, old = sets[k & 1], sets[(k + 1) & 1]
         update_ms = 0.0
-        if a.wobble and k:
-            ds.update(dev.wobbled_desc(d0, k))
+        relit = relight_at is not None and k >= relight_at
+        moved = bool(a.wobble and k)
+        desc_k = None
+        if moved or (relit and (a.wobble or k == relight_at)):
+            desc_k = dev.wobbled_desc(d0, k) if moved else d0
+            if relit:
+                desc_k = relit_desc(desc_k, relight_factor)
+            ds.update(desc_k, geometry=moved, shading=relit)
             update_ms = ds.info("update_us0") / 1e3
+        if a.gradient:
+            color = cur["color"]
         times["render"].append(once(lambda: ds.render_into(p, color.data_ptr(), stream)))
+        if a.gradient:
+            times["rows"].append(once(lambda: ds.render_into(dev.gradient_rows_params(p_prev), rows.data_ptr(), stream)) if k else 0.0)
+            times["gradient"].append(once(lambda: ds.temporal_gradient_into(w, h, old["color"].data_ptr(), rows.data_ptr(),
+                                                                            lam.data_ptr(), stream)) if k else 0.0)
         times["guides"].append(once(lambda: ds.render_guides_into(
             p, p_prev or p, previous_geometry=True, albedo_ptr=albedo.data_ptr(), normal_ptr=cur["normal"].data_ptr(),
             depth_ptr=cur["depth"].data_ptr(), motion_ptr=motion.data_ptr(), prev_depth_ptr=prev_depth.data_ptr())))
         hist = [old[n].data_ptr() for n in ("out", "normal", "depth", "length")] if k else None
         if a.variance:
             hist5 = hist + [old["moments"].data_ptr()] if k else None
-            times["accumulate_moments"].append(once(lambda: ds.temporal_accumulate_moments_into(
-                w, h, color.data_ptr(), albedo.data_ptr(), cur["normal"].data_ptr(), motion.data_ptr(), prev_depth.data_ptr(), hist5,
-                cur["out"].data_ptr(), cur["length"].data_ptr(), cur["moments"].data_ptr(), stream, **TEMPORAL)))
+            if a.gradient:
+                times["accumulate_adaptive"].append(once(lambda: ds.temporal_accumulate_adaptive_into(
+                    w, h, color.data_ptr(), albedo.data_ptr(), cur["normal"].data_ptr(), motion.data_ptr(), prev_depth.data_ptr(), hist5,
+                    cur["out"].data_ptr(), cur["length"].data_ptr(), cur["moments"].data_ptr(), lam.data_ptr(), stream=stream, **TEMPORAL)))
+            else:
+                times["accumulate_moments"].append(once(lambda: ds.temporal_accumulate_moments_into(
+                    w, h, color.data_ptr(), albedo.data_ptr(), cur["normal"].data_ptr(), motion.data_ptr(), prev_depth.data_ptr(), hist5,
+                    cur["out"].data_ptr(), cur["length"].data_ptr(), cur["moments"].data_ptr(), stream, **TEMPORAL)))
             times["denoise_variance"].append(once(lambda: ds.denoise_variance_into(
                 w, h, cur["out"].data_ptr(), albedo.data_ptr(), cur["normal"].data_ptr(), cur["depth"].data_ptr(),
                 cur["moments"].data_ptr(), cur["length"].data_ptr(), denoised.data_ptr(), 0, stream)))
@@ -154,14 +197,16 @@ def main():
         elif a.denoise:
             images["denoised"] = denoised
         line = f"frame {k:3d}: " + "  ".join(f"{s} {times[s][-1]:7.3f} ms" for s in stages)
-        if a.wobble and k:
+        if desc_k is not None:
             line += f"  (update {update_ms:.3f} ms)"
+        if a.gradient and k:
+            line += f"  lambda: mean {float(lam.mean()):.3f}, {float((lam > 0).float().mean()):.3f} of the tiles positive"
         valid = prev_depth > 0
         line += f"  history: {float((cur['length'][valid] > 1).float().mean()) if valid.any() else 0.0:.3f} of the valid pixels, " \
                 f"mean length {float(cur['length'].mean()):.2f}"
         if ref is not None:
-            if a.wobble and k:
-                ref.update(dev.wobbled_desc(d0, k))
+            if desc_k is not None:
+                ref.update(desc_k, geometry=moved, shading=relit)
             q = p.copy()
             q.spp, q.seed = a.reference_spp, 7
             truth = ref.render(q)
@@ -196,6 +241,14 @@ def main():
             t["pt_temporal_accumulate_moments"] = timed(lambda: ds.temporal_accumulate_moments_into(
                 w, h, color.data_ptr(), albedo.data_ptr(), cur["normal"].data_ptr(), motion.data_ptr(), prev_depth.data_ptr(), hist5,
                 scratch.data_ptr(), cur["length"].data_ptr(), mom.data_ptr(), stream, **TEMPORAL))
+            if a.gradient:
+                t["pt_render, every 3rd row of the previous frame"] = timed(lambda: ds.render_into(dev.gradient_rows_params(p_prev),
+                                                                                                   rows.data_ptr(), stream))
+                t["pt_temporal_gradient"] = timed(lambda: ds.temporal_gradient_into(w, h, old["color"].data_ptr(), rows.data_ptr(),
+                                                                                    lam.data_ptr(), stream))
+                t["pt_temporal_accumulate_adaptive"] = timed(lambda: ds.temporal_accumulate_adaptive_into(
+                    w, h, color.data_ptr(), albedo.data_ptr(), cur["normal"].data_ptr(), motion.data_ptr(), prev_depth.data_ptr(), hist5,
+                    scratch.data_ptr(), cur["length"].data_ptr(), mom.data_ptr(), lam.data_ptr(), stream=stream, **TEMPORAL))
             t["pt_denoise, 5 iterations"] = timed(lambda: ds.denoise_into(w, h, cur["out"].data_ptr(), albedo.data_ptr(), cur["normal"].data_ptr(),
                                                                           cur["depth"].data_ptr(), scratch.data_ptr(), stream))
             t["pt_denoise_variance, 5 iterations"] = timed(lambda: ds.denoise_variance_into(

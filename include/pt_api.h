@@ -586,6 +586,12 @@ int pt_bvh_build_sweep_device(const pt_scene_desc* desc, pt_bvh_node* out_nodes,
  *                   rounds*100 + inner*10 + leaf steps (162 = 6 inner + 2 leaf steps); 1000 + burst = the same burst with
  *                   leaves set aside and tested together (internal tree only).  Only compiled-in variants are
  *                   accepted (PT_ERR_INVALID_ARG otherwise); every variant renders the same bits.
+ *   "reg_stack"     1 (default) trace_kernel_v2 keeps the traversal stack of a lane in one register instead of an LDS column
+ *                   where that is possible: an LDS-resident scene of triangles with diffuse materials on its automatic
+ *                   schedule ("v2_thresh" and "v2_inner" 0; "v2_minw" 0, 5 or 6), traversed on the internal tree, whose tree
+ *                   holds at most 4 stack entries ("stack_entries" <= 5) with at most 126 inner nodes and 127 primitives,
+ *                   rendered without PT_RENDER_NEE and outside the later rounds of pt_render_adaptive.  0 = always the LDS
+ *                   stack.  Same nodes, same leaves, same order: the same bits.  Info "reg_stack" reports the last launch.
  *   "octants"       1 (default) keep 8 ray-octant node tables in LDS for very small scenes, 0 = one table
  *   "fast_tree"     1 (default) traversal (exact and pruned) on the library's INTERNAL tree where pt_scene_create kept one,
  *                   0 = on the caller's tree.  Same image either way, bit for bit: the reference never prunes, so a leaf is tested iff the
@@ -627,9 +633,12 @@ int pt_bvh_build_sweep_device(const pt_scene_desc* desc, pt_bvh_node* out_nodes,
  *     bits  0-3  family: 1 trace_kernel, 2 trace_kernel_v2, 3 trace_kernel_q      bit  10  NEE
  *     bits  4-5  RES (family 1: LDS_SCENE)                                      bit  11  LIST
  *     bit   6    PRUNE       bit 7  STATS       bits 8-9  SPEC                    bit  12  POSTPONE
+ *     bit  13    register stack (trace_kernel_v2_reg: the trace_kernel_v2 of the other fields with the stack in a register)
  *     bits 16-23 THRESH      bits 24-39 INNER, 16-bit two's complement          bits 40-43 MINW
  *   a field the family's template does not have is 0), "path_bank" (1 = that kernel handed out path starts from a per-wave
- * register bank filled 64 at a time: trace_kernel_v2 on LDS-resident scenes of triangles with diffuse materials), "frames_in_flight", "sweep_on_device" (the internal tree was built on the GPU),
+ * register bank filled 64 at a time: trace_kernel_v2 on LDS-resident scenes of triangles with diffuse materials),
+ * "reg_stack" (1 = that kernel kept its traversal stack in a register, see option "reg_stack"; "lds_bytes" of such a launch has no
+ * stack columns), "frames_in_flight", "sweep_on_device" (the internal tree was built on the GPU),
  * "create_us0".."create_us6" (wall microseconds of pt_scene_create: total, primitive records, caller's tree checked and re-laid,
  * internal tree built, ... re-laid, uploads + probe, tie tables). */
 int pt_scene_set_option(pt_scene* scene, const char* key, int64_t value);

@@ -264,11 +264,12 @@ struct pt_scene {
                                      // 3 = paths regrouped across the waves of a workgroup (pt_kernel_q.h; LDS-resident scenes, else as 2)
     int64_t opt_q_target = 0, opt_q_swap = 0, opt_q_low = 0;   // schedule knobs of kernel 3; 0 = automatic
     int64_t opt_v2_thresh = 0, opt_v2_inner = 0, opt_v2_minw = 0;   // 0 = auto (see pick_kernel)
+    int64_t opt_reg_stack = 1;      // 1 = register traversal stack where it applies (launch_reg_stack), 0 = always the LDS stack
     // info of last launch
     // wall time of pt_scene_create's stages, microseconds: [0] total [1] primitive records [2] caller's tree checked and re-laid
     // [3] internal tree built [4] ... re-laid [5] uploads + probe [6] tie tables; built_on_device: the sweep ran on the GPU
     int64_t create_us[7] = {0, 0, 0, 0, 0, 0, 0}, sweep_on_device = 0;
-    int64_t info_grid = 0, info_lds_bytes = 0, info_lds_scene = 0, info_passes = 0, info_occupancy = 0, info_blocks_per_cu = 0, info_debug_reruns = 0, fast_cost_permille = 0, info_kernel = 0, info_trace_variant = 0, info_path_bank = 0;
+    int64_t info_grid = 0, info_lds_bytes = 0, info_lds_scene = 0, info_passes = 0, info_occupancy = 0, info_blocks_per_cu = 0, info_debug_reruns = 0, fast_cost_permille = 0, info_kernel = 0, info_trace_variant = 0, info_path_bank = 0, info_reg_stack = 0;
     struct PassEvents { hipEvent_t t0, t1, r0, r1; };            // trace begin, trace end (on the trace kernel's stream); resolve begin, end (caller's)
     // HIP events of the last `opt_timing_frames` render calls (a ring; default 1): a caller that enqueues frame after frame
     // without a host sync in between — bench.py's timed loop — reads every frame's kernel time afterwards (pt_get_frame_times)
@@ -843,7 +844,8 @@ int validate_and_build(const pt_scene_desc* d, pt_scene* S) {
 
 // res: 0 scene in global memory, 1 scene staged in LDS, 2 staged in LDS with the 8 octant node tables,
 //      3 scene in global memory with the top of the tree cached in LDS
-LdsPlan make_plan(const pt_scene* S, int res, bool stack16, int which = 0) {
+// reg_stack: the kernel keeps its traversal stack in a register (pt_reg_stack.h), the block has no stack columns
+LdsPlan make_plan(const pt_scene* S, int res, bool stack16, int which = 0, bool reg_stack = false) {
     LdsPlan lp{};
     const pt_scene::Tree& T = S->tree[which];
     uint32_t off = 0;
@@ -865,7 +867,7 @@ LdsPlan make_plan(const pt_scene* S, int res, bool stack16, int which = 0) {
         lp.emis_off = off; off = align16(off + (uint32_t)std::max(S->dev.num_emission, 1) * sizeof(DEmission));
     }
     lp.stack_off = off;
-    off += (uint32_t)(kBlock / 64) * (uint32_t)T.stack_cap * 64u * (stack16 ? 2u : 4u);
+    if (!reg_stack) off += (uint32_t)(kBlock / 64) * (uint32_t)T.stack_cap * 64u * (stack16 ? 2u : 4u);
     lp.total = align16(off);
     return lp;
 }
@@ -876,15 +878,16 @@ using TraceFn = void (*)(SceneDev, RenderDev, LdsPlan, float4*, uint32_t*, unsig
 // functions hand it back next to the kernel, both made from the same template arguments (v1k / v2k / qk), so that the
 // value reported for a launch cannot disagree with the kernel launched.
 constexpr int64_t trace_variant(int family, int res, bool prune, bool stats, int spec, bool nee, bool list, bool postpone,
-                                int thresh, int inner, int minw) {
+                                int thresh, int inner, int minw, bool reg = false) {
     return (int64_t)family | (int64_t)res << 4 | (int64_t)prune << 6 | (int64_t)stats << 7 | (int64_t)spec << 8 |
-           (int64_t)nee << 10 | (int64_t)list << 11 | (int64_t)postpone << 12 | (int64_t)thresh << 16 |
+           (int64_t)nee << 10 | (int64_t)list << 11 | (int64_t)postpone << 12 | (int64_t)reg << 13 | (int64_t)thresh << 16 |
            (int64_t)(uint16_t)(int16_t)inner << 24 | (int64_t)minw << 40;
 }
 struct TracePick {
     TraceFn fn;
     int64_t variant;
     int bank = 0;        // info "path_bank": the kernel hands out path starts from a register bank (pt_kernels.h: path_bank_on)
+    int reg = 0;         // info "reg_stack": the kernel keeps its traversal stack in a register (pt_reg_stack.h)
 };
 template <bool LDS_SCENE, bool PRUNE, bool STATS, bool LIST = false>
 TracePick v1k() {
@@ -895,6 +898,11 @@ TracePick v2k() {
     static_assert(INNER >= -32768 && INNER <= 32767 && THRESH >= 0 && THRESH < 256 && MINW >= 0 && MINW < 16, "trace_variant fields");
     return {trace_kernel_v2<RES, PRUNE, STATS, THRESH, INNER, MINW, SPEC, NEE, LIST>,
             trace_variant(2, RES, PRUNE, STATS, SPEC, NEE, LIST, false, THRESH, INNER, MINW), path_bank_on(RES, SPEC, NEE, LIST, THRESH, INNER)};
+}
+template <int RES, bool PRUNE, bool STATS, int MINW>
+TracePick v2rk() {           // trace_kernel_v2_reg: the template arguments of its trace_v2, and the register-stack bit
+    return {trace_kernel_v2_reg<RES, PRUNE, STATS, MINW>, trace_variant(2, RES, PRUNE, STATS, 2, false, false, false, 40, 162, MINW, true),
+            path_bank_on(RES, 2, false, false, 40, 162), 1};
 }
 
 TracePick pick_kernel_v1(bool lds, bool prune, bool stats) {
@@ -944,6 +952,19 @@ TracePick pick_kernel_v2(int res, bool prune, bool stats, int spec, int thresh, 
     PT_V2(32, 1231, 5) PT_V2(40, 162, 5)        // 96 VGPRs, 5 waves per SIMD: for the instantiations that spill under the 80-VGPR cap
 #undef PT_V2
     return {nullptr, 0};
+}
+
+// The register-stack instantiations (pt_kernels.h: trace_kernel_v2_reg; which launches take them: launch_reg_stack): the default schedule of
+// LDS-resident scenes of triangles with diffuse materials, both register caps.  Each keeps ScratchSize 0 within its cap
+// (profiles/r10_reg_stack.log has the table).
+template <int RES, int MINW>
+TracePick pick_reg_rw(bool prune, bool stats) {
+    if (prune) return stats ? v2rk<RES, true, true, MINW>() : v2rk<RES, true, false, MINW>();
+    return stats ? v2rk<RES, false, true, MINW>() : v2rk<RES, false, false, MINW>();
+}
+TracePick pick_kernel_reg(int res, bool prune, bool stats, int minw) {
+    if (res == 2) return minw == 5 ? pick_reg_rw<2, 5>(prune, stats) : pick_reg_rw<2, 6>(prune, stats);
+    return minw == 5 ? pick_reg_rw<1, 5>(prune, stats) : pick_reg_rw<1, 6>(prune, stats);
 }
 
 // Kernels with next-event estimation (PT_RENDER_NEE): exact traversal, the default schedule of the residency, generic
@@ -1038,23 +1059,51 @@ int scene_residency(const pt_scene* S, int which = 0) {
     return 1;
 }
 
-TracePick pick_kernel(const pt_scene* S, int res, bool prune, bool stats, bool internal_tree) {
+// The schedule of trace_kernel_v2 after the "v2_*" options, 0 = automatic, have been resolved for a residency and tree:
+// pick_kernel's launch and launch_reg_stack's question about it read the same one.
+// LDS-resident: 6 inner + 2 leaf steps; global memory: 4 + 1 on the caller's tree; on the internal tree two rounds of
+// 3 + 1 with leaves set aside (v2_inner 1000 + burst).  Setting leaves aside: bunny -2.2 %, dragon stand-in -3.4 %
+// against the plain 4 + 1 (LDS-resident scenes lose 9 % with it: profiles/r02_tune_round43_postponed_leaves.log); two
+// rounds of 3 + 1 instead of one of 4 + 1: teapot -8.5 %, bunny -1.2 %, buddha stand-in -1.5 %, dragon stand-in -1.8 %
+// (r02_tune_round48_global_thresh.log, r02_tune_round49_global_burst.log; thresholds 24 / 40 / 48 lose, so do three rounds of
+// 3 + 1 and two of 2 + 1, and every set-aside shape on LDS-resident scenes: r02_tune_round50_more_bursts_rejected.log; 7 / 8 waves per
+// SIMD by register cap, with the blocks to match: +11..16 % / +28..41 % from the spills, r02_tune_round51_more_waves_rejected.log).
+struct V2Schedule {
+    int thresh, inner, minw;
+};
+V2Schedule v2_schedule(const pt_scene* S, int res, bool internal_tree) {
+    const bool lds = res == 1 || res == 2;
+    V2Schedule s{(int)S->opt_v2_thresh, (int)S->opt_v2_inner, (int)S->opt_v2_minw};
+    if (s.thresh == 0) s.thresh = lds ? 40 : 32;
+    if (s.inner == 0) s.inner = lds ? 162 : (internal_tree ? 1231 : 4);
+    if (s.minw == 0) s.minw = 6;
+    return s;
+}
+
+// Does this launch keep its traversal stack in a register?  Option "reg_stack" allows it, the launch runs trace_kernel_v2
+// without next-event estimation or a pixel list on a scene of triangles with diffuse materials (the instantiations compiled
+// with it: pick_kernel_reg), and reg_stack_on holds for its residency, schedule and tree.  The schedule must be the automatic
+// one: options "v2_thresh" / "v2_inner" name an instantiation of trace_kernel_v2, and a caller who sets them gets that one
+// (the tuning tools and the test of every compiled instantiation select kernels that way).  Decided before the LDS plan is
+// made: such a block has no stack columns.
+bool launch_reg_stack(const pt_scene* S, int res, int which, bool nee, bool listed, bool use_q) {
+    if (!S->opt_reg_stack || S->opt_kernel < 2 || use_q || nee || listed) return false;
+    if (!(S->tri_only && S->diffuse_only && S->opt_specialize)) return false;
+    if (S->opt_v2_thresh || S->opt_v2_inner) return false;
+    const V2Schedule sc = v2_schedule(S, res, which == 1);
+    if (sc.minw != 5 && sc.minw != 6) return false;          // the register caps pick_kernel_reg is compiled for
+    const pt_scene::Tree& T = S->tree[which];
+    return reg_stack_on(res, sc.thresh, sc.inner, which == 1, T.stack_cap - 1, T.num_nodes, S->dev.num_prims);
+}
+
+TracePick pick_kernel(const pt_scene* S, int res, bool prune, bool stats, bool internal_tree, bool reg_stack) {
     if (S->opt_kernel >= 2) {
-        int t = (int)S->opt_v2_thresh, i = (int)S->opt_v2_inner, w = (int)S->opt_v2_minw;
-        const bool lds = res == 1 || res == 2;
-        if (t == 0) t = lds ? 40 : 32;
+        const V2Schedule sc = v2_schedule(S, res, internal_tree);
+        const int t = sc.thresh, i = sc.inner, w = sc.minw;
         const bool tri = S->tri_only && S->opt_specialize;
-        // LDS-resident: 6 inner + 2 leaf steps; global memory: 4 + 1 on the caller's tree; on the internal tree two rounds of
-        // 3 + 1 with leaves set aside (v2_inner 1000 + burst).  Setting leaves aside: bunny -2.2 %, dragon stand-in -3.4 %
-        // against the plain 4 + 1 (LDS-resident scenes lose 9 % with it: profiles/r02_tune_round43_postponed_leaves.log); two
-        // rounds of 3 + 1 instead of one of 4 + 1: teapot -8.5 %, bunny -1.2 %, buddha stand-in -1.5 %, dragon stand-in -1.8 %
-        // (r02_tune_round48_global_thresh.log, r02_tune_round49_global_burst.log; thresholds 24 / 40 / 48 lose, so do three rounds of
-        // 3 + 1 and two of 2 + 1, and every set-aside shape on LDS-resident scenes: r02_tune_round50_more_bursts_rejected.log; 7 / 8 waves per
-        // SIMD by register cap, with the blocks to match: +11..16 % / +28..41 % from the spills, r02_tune_round51_more_waves_rejected.log).
-        if (i == 0) i = lds ? 162 : (internal_tree ? 1231 : 4);
         if (i >= 1000 && !internal_tree) return {nullptr, 0};   // order-free leaf tests need the internal tree's tie handling
-        if (w == 0) w = 6;
         const int spec = !tri ? 0 : (S->diffuse_only ? 2 : 1);
+        if (reg_stack) return pick_kernel_reg(res, prune, stats, w);     // launch_reg_stack: spec 2, thresh 40, burst 162
         return pick_kernel_v2(res, prune, stats, spec, t, i, w);
     }
     return pick_kernel_v1(res == 1 || res == 2, prune, stats);
@@ -1201,6 +1250,7 @@ int launch_render(pt_scene* S, const pt_render_params* p, float* out_dev, int mo
     if (rows.count == 0) {           // nothing to trace: the frame's counters read zero
         S->info_trace_variant = 0;
         S->info_path_bank = 0;
+        S->info_reg_stack = 0;
         if (slot.used && slot.free_stream != stream) HIP_TRY(hipStreamWaitEvent(stream, slot.free_ev, 0));
         HIP_TRY(hipMemsetAsync(slot.ctl.p, 0, (kWorkWords + kTimelineBase) * sizeof(unsigned long long), stream));
         HIP_TRY(hipEventRecord(slot.free_ev, stream));
@@ -1246,8 +1296,6 @@ int launch_render(pt_scene* S, const pt_render_params* p, float* out_dev, int mo
     const int which = which_tree(S);
     const int res = scene_residency(S, which);
     const bool lds_scene = res == 1 || res == 2;
-    LdsPlan lp = make_plan(S, res, lds_scene && S->opt_kernel >= 2, which);   // trace_kernel_v2 keeps 16-bit stacks for LDS scenes
-    if (lp.total > S->lds_per_block_max) return fail(PT_ERR_DEVICE, "LDS plan exceeds the per-block limit");
     if (p->flags & ~PT_RENDER_NEE) return fail(PT_ERR_INVALID_ARG, "unknown bits in pt_render_params.flags");
     const bool nee = (p->flags & PT_RENDER_NEE) != 0;
     if (nee && (S->opt_kernel < 2 || traversal != PT_TRAVERSAL_EXACT))
@@ -1255,11 +1303,14 @@ int launch_render(pt_scene* S, const pt_render_params* p, float* out_dev, int mo
     // kernel 3 (paths regrouped across the waves of a workgroup) serves exact traversal without next-event estimation; those run
     // on kernel 2
     const bool use_q = S->opt_kernel == 3 && !nee && traversal == PT_TRAVERSAL_EXACT && !listed;
+    const bool reg_stack = launch_reg_stack(S, res, which, nee, listed, use_q);
+    LdsPlan lp = make_plan(S, res, lds_scene && S->opt_kernel >= 2, which, reg_stack);   // trace_kernel_v2 keeps 16-bit stacks for LDS scenes
+    if (lp.total > S->lds_per_block_max) return fail(PT_ERR_DEVICE, "LDS plan exceeds the per-block limit");
     QParams qp{};
     TraceFnQ fnq = nullptr;
     TraceFn fn = nullptr;
     int64_t variant = 0;
-    int path_bank = 0;
+    int path_bank = 0, reg_stack_used = 0;
     if (use_q) {
         qp = make_plan_q(S, lp, which, res);
         if (lp.total > S->lds_per_block_max) return fail(PT_ERR_DEVICE, "LDS plan exceeds the per-block limit");
@@ -1268,8 +1319,8 @@ int launch_render(pt_scene* S, const pt_render_params* p, float* out_dev, int mo
     } else {
         const TracePick pk = listed ? pick_kernel_list(S, res, traversal == PT_TRAVERSAL_PRUNED, S->opt_stats != 0, which == 1, nee)
                            : nee ? pick_kernel_nee(res, S->opt_stats != 0, (S->tri_only && S->diffuse_only && S->opt_specialize) ? 2 : 0)
-                                 : pick_kernel(S, res, traversal == PT_TRAVERSAL_PRUNED, S->opt_stats != 0, which == 1);
-        fn = pk.fn; variant = pk.variant; path_bank = pk.bank;
+                                 : pick_kernel(S, res, traversal == PT_TRAVERSAL_PRUNED, S->opt_stats != 0, which == 1, reg_stack);
+        fn = pk.fn; variant = pk.variant; path_bank = pk.bank; reg_stack_used = pk.reg;
         if (!fn) return fail(PT_ERR_INVALID_ARG, "no kernel variant compiled for these v2_thresh / v2_inner options");
     }
     const void* fn_any = use_q ? reinterpret_cast<const void*>(fnq) : reinterpret_cast<const void*>(fn);
@@ -1298,6 +1349,7 @@ int launch_render(pt_scene* S, const pt_render_params* p, float* out_dev, int mo
     S->info_kernel = use_q ? 3 : S->opt_kernel == 1 ? 1 : 2;
     S->info_trace_variant = variant;
     S->info_path_bank = path_bank;
+    S->info_reg_stack = reg_stack_used;
     S->info_occupancy = occ;
     S->info_blocks_per_cu = bpc;
     S->info_lds_bytes = lp.total;
@@ -2230,6 +2282,7 @@ int pt_scene_set_option(pt_scene* S, const char* key, int64_t value) {
     else if (k == "v2_thresh") S->opt_v2_thresh = value;
     else if (k == "v2_inner") S->opt_v2_inner = value;
     else if (k == "v2_minw") S->opt_v2_minw = value;
+    else if (k == "reg_stack") { if (value != 0 && value != 1) return fail(PT_ERR_INVALID_ARG, "reg_stack must be 0 or 1"); S->opt_reg_stack = value; }
     else return fail(PT_ERR_INVALID_ARG, "unknown option " + k);
     return PT_OK;
 }
@@ -2280,6 +2333,7 @@ int pt_scene_get_info(pt_scene* S, const char* key, int64_t* value) {
     else if (k == "kernel") *value = S->info_kernel;                      // the kernel the last render ran on (1, 2 or 3)
     else if (k == "trace_variant") *value = S->info_trace_variant;        // ... and its template arguments (include/pt_api.h)
     else if (k == "path_bank") *value = S->info_path_bank;                // ... which handed out path starts from a register bank (1) or not
+    else if (k == "reg_stack") *value = S->info_reg_stack;                // ... with the traversal stack in a register (1) or in LDS / global memory (0)
     else if (k == "block_threads") *value = S->info_kernel == 3 ? kQBlock : kBlock;
     else if (k == "frames_in_flight") *value = S->opt_frames_in_flight;
     else if (k.rfind("qdiag", 0) == 0 && k.size() >= 6 && k.size() <= 7 && k.find_first_not_of("0123456789", 5) == std::string::npos &&
@@ -2318,7 +2372,7 @@ int pt_scene_get_info(pt_scene* S, const char* key, int64_t* value) {
         if (S->opt_kernel == 3 && k == "vgprs") {
             f = reinterpret_cast<const void*>(pick_kernel_q(S, res, w == 1).fn);
         } else {
-            TraceFn fn = pick_kernel(S, res, k == "vgprs_pruned", S->opt_stats != 0, w == 1).fn;
+            TraceFn fn = pick_kernel(S, res, k == "vgprs_pruned", S->opt_stats != 0, w == 1, launch_reg_stack(S, res, w, false, false, false)).fn;
             if (!fn) return fail(PT_ERR_INVALID_ARG, "no such kernel variant");
             f = reinterpret_cast<const void*>(fn);
         }

@@ -255,13 +255,14 @@ __global__ __launch_bounds__(kQBlock, PT_Q_MINW) void trace_kernel_q(SceneDev sc
         // ---------------------------------------------------------------------------------- traversal role
         STK* stk = reinterpret_cast<STK*>(smem + lp.stack_off) + (size_t)wave * scn.stack_cap * 64 + lane;
         ptd::stack_init(stk);
+        const ptd::LdsStack<STK> stack{stk};
         bool has = false;
         ptd::Ray ray;
         ray.org = ptm::mk(0, 0, 0); ray.dir = ptm::mk(0, 0, 1); ray.tnear = 0; ray.tfar = 0;
         ptd::Trav tv;
         tv.inv = ptm::mk(1, 1, 1);
         tv.best.t = 0; tv.best.u = 0; tv.best.v = 0; tv.best.prim = -1;
-        tv.cur = DONE; tv.sp = 1; tv.node_off = 0; tv.redo = false;
+        tv.cur = DONE; stack.reset(tv); tv.node_off = 0; tv.redo = false;
         int32_t pend = DONE;                    // POSTPONE: the leaf set aside
         // what the lane only carries from ring to ring
         ptm::V3 cL = ptm::mk(0, 0, 0), cT = ptm::mk(1, 1, 1);
@@ -283,11 +284,10 @@ __global__ __launch_bounds__(kQBlock, PT_Q_MINW) void trace_kernel_q(SceneDev sc
                         }
                         if (tv.cur >= 0) {
                             if (STATS) st.nodes++;
-                            ptd::inner_step<false, false, STK, TOP>(sv, ray.org, tv, stk);
+                            ptd::inner_step<false, false, TOP>(sv, ray.org, tv, stack);
                             if (tv.cur < 0 && tv.cur != DONE && pend == DONE) {       // a leaf: set it aside, take the next entry
                                 pend = tv.cur;
-                                tv.sp--;
-                                tv.cur = stk[tv.sp * 64];
+                                stack.pop(tv);
                             }
                         }
                     }
@@ -301,8 +301,7 @@ __global__ __launch_bounds__(kQBlock, PT_Q_MINW) void trace_kernel_q(SceneDev sc
                         pend = DONE;
                         if (tv.cur < 0 && tv.cur != DONE) {                           // the lane was blocked on a second leaf
                             pend = tv.cur;
-                            tv.sp--;
-                            tv.cur = stk[tv.sp * 64];
+                            stack.pop(tv);
                         }
                     }
                 }
@@ -315,7 +314,7 @@ __global__ __launch_bounds__(kQBlock, PT_Q_MINW) void trace_kernel_q(SceneDev sc
                     }
                     if (tv.cur >= 0) {
                         if (STATS) st.nodes++;
-                        ptd::inner_step<false, RES == 2, STK, TOP>(sv, ray.org, tv, stk);
+                        ptd::inner_step<false, RES == 2, TOP>(sv, ray.org, tv, stack);
                     }
                 }
 #pragma unroll
@@ -326,7 +325,7 @@ __global__ __launch_bounds__(kQBlock, PT_Q_MINW) void trace_kernel_q(SceneDev sc
                     }
                     if (tv.cur < 0 && tv.cur != DONE) {
                         if (STATS) st.leaves++;
-                        ptd::leaf_step<STK, TRI_ONLY, false>(sv, ray, tv, stk, false, fbk);
+                        ptd::leaf_step<TRI_ONLY, false>(sv, ray, tv, stack, false, fbk);
                     }
                 }
             }
@@ -379,7 +378,7 @@ __global__ __launch_bounds__(kQBlock, PT_Q_MINW) void trace_kernel_q(SceneDev sc
                     tv.inv = ptm::mk(p.a0, p.a1, p.a2);
                     tv.best.t = FLT_MAX; tv.best.u = 0.0f; tv.best.v = 0.0f; tv.best.prim = -1;
                     tv.cur = sv.root_ref;
-                    tv.sp = 1;
+                    stack.reset(tv);
                     tv.redo = (p.depth_flags & kQRedoBit) != 0u;
                     if (tv.redo) tv.cur = DONE;          // traced on the caller's tree by the S-wave that shades it
                     const uint32_t oct = (tv.inv.x < 0.0f ? 1u : 0u) | (tv.inv.y < 0.0f ? 2u : 0u) | (tv.inv.z < 0.0f ? 4u : 0u);

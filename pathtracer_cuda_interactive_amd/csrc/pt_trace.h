@@ -17,6 +17,7 @@
 
 #include "pt_layout.h"
 #include "pt_math.h"
+#include "pt_reg_stack.h"
 
 namespace ptd {
 
@@ -70,7 +71,8 @@ struct Trav {
     V3 inv;            // 1/dir, hoisted out of Hit() (bbox.cuh:36) — same bits
     Hit best;          // closest hit so far (scene.h:248-249,270-273)
     int32_t cur;       // node reference being visited; kDone = traversal finished
-    int32_t sp;        // entries on this lane's LDS stack column
+    int32_t stack_state;   // the stack policy's one register of state, read and written by the policy alone (reset / pop /
+                       // advance): LdsStack: entries on this lane's column; RegStack: the four-byte stack itself (pt_reg_stack.h)
     uint32_t node_off; // byte offset of the node table this ray reads (octant copy), 0 when there is one table
     bool redo;         // traversal of the internal tree: 1/d is infinite on an axis (0 * inf in the slab test lies outside the
                        // argument that lets that tree stand in) — this ray is traced on the caller's tree in the reference's order
@@ -83,11 +85,52 @@ template <class STK> __device__ __forceinline__ constexpr int32_t done_value() {
 // Entry 0 of the column holds the done value, so popping an empty stack ends the traversal without an emptiness test.
 template <class STK> __device__ __forceinline__ void stack_init(STK* stk) { stk[0] = (STK)done_value<STK>(); }
 
-__device__ __forceinline__ void trav_begin(const SceneView& sv, const Ray& ray, Trav& t) {
+// The step functions below reach the stack through one of two policies.
+// LdsStack<STK>: the LDS column `col` of this lane, t.stack_state its height.  The push and the pop of a node visit are masked regions.
+template <class STK> struct LdsStack {
+    static constexpr int32_t kDone = sizeof(STK) == 2 ? -32768 : ptl::kDone;       // = done_value<STK>()
+    static constexpr bool kLeftFirst = false;       // the visit order is the tree's (SceneView::fixed_order)
+    STK* col;
+    __device__ __forceinline__ void reset(Trav& t) const { t.stack_state = 1; }                  // entry 0 is the done sentinel
+    __device__ __forceinline__ void pop(Trav& t) const { t.stack_state--; t.cur = col[t.stack_state * 64]; }
+    // after a node visit: `both` children hit -> go to `next`, keep `other`; `any` -> go to `next`; none -> pop
+    __device__ __forceinline__ void advance(Trav& t, const bool both, const bool any, const int32_t next, const int32_t other) const {
+        if (both) {
+            col[t.stack_state * 64] = (STK)other;
+            t.stack_state++;
+        }
+        if (any) {
+            t.cur = next;
+        } else {
+            pop(t);
+        }
+    }
+};
+// RegStack: t.stack_state IS the stack, four signed bytes (pt_reg_stack.h; the launches that take it: reg_stack_on).  No LDS access,
+// no stack pointer, and everything is a select, so a node visit holds no masked region for the stack.  These kernels exist
+// for the internal tree only, whose order is left-first: a compile-time fact here.
+struct RegStack {
+    static constexpr int32_t kDone = kRegStackDone;
+    static constexpr bool kLeftFirst = true;
+    __device__ __forceinline__ void reset(Trav& t) const { t.stack_state = (int32_t)kRegStackEmpty; }
+    __device__ __forceinline__ void pop(Trav& t) const {
+        const uint32_t w = (uint32_t)t.stack_state;
+        t.cur = reg_stack_top(w);
+        t.stack_state = (int32_t)reg_stack_drop(w);
+    }
+    __device__ __forceinline__ void advance(Trav& t, const bool both, const bool any, const int32_t next, const int32_t other) const {
+        const uint32_t w = (uint32_t)t.stack_state;
+        t.cur = any ? next : reg_stack_top(w);
+        t.stack_state = (int32_t)(both ? reg_stack_push(w, other) : (any ? w : reg_stack_drop(w)));
+    }
+};
+
+template <class S>
+__device__ __forceinline__ void trav_begin(const SceneView& sv, const Ray& ray, Trav& t, const S& s) {
     t.inv = mk(rcp_exact(ray.dir.x), rcp_exact(ray.dir.y), rcp_exact(ray.dir.z));
     t.best.t = FLT_MAX; t.best.u = 0.0f; t.best.v = 0.0f; t.best.prim = -1;
     t.cur = sv.root_ref;           // scene.h:256: the root is pushed without a box test
-    t.sp = 1;                      // entry 0 is the kDone sentinel
+    s.reset(t);
     t.redo = false;
     // octant = which of the swaps of bbox.cuh:40-55 apply to this ray (inv < 0 per axis)
     const uint32_t oct = (t.inv.x < 0.0f ? 1u : 0u) | (t.inv.y < 0.0f ? 2u : 0u) | (t.inv.z < 0.0f ? 4u : 0u);
@@ -126,8 +169,8 @@ __device__ __forceinline__ void slab_distances(const float4 a, const float4 b, c
 }
 
 // Everything of an inner visit after the node has been fetched (a, b, c, d = the node's four 16-B pieces).
-template <bool PRUNE, bool OCT, class STK>
-__device__ __forceinline__ void visit_node(const float4 a, const float4 b, const float4 c, const float4 d, const V3& o, Trav& t, STK* stk,
+template <bool PRUNE, bool OCT, class S>
+__device__ __forceinline__ void visit_node(const float4 a, const float4 b, const float4 c, const float4 d, const V3& o, Trav& t, const S& s,
                                            const bool fixed_order) {
     const V3 inv = t.inv;
     float ltn, ltf, rtn, rtf;
@@ -153,24 +196,16 @@ __device__ __forceinline__ void visit_node(const float4 a, const float4 b, const
     const int32_t R = __builtin_bit_cast(int32_t, d.y);
     // scene.h:281-297: both hit -> visit the nearer box first (on a tie the right one) and keep the other on the
     // stack; one hit -> descend into it; none -> pop.  The stack bottom holds a kDone sentinel (trav_begin), so a
-    // pop needs no emptiness test.  Written with selects so that only the push and the pop are masked regions.
+    // pop needs no emptiness test.  Written with selects so that only the push and the pop are masked regions (LdsStack; RegStack
+    // has none: its advance() is selects throughout).
     // fixed_order (wave-uniform; the internal tree only, where exact traversal may visit in ANY order — rays whose answer
     // depends on it are rerun on the caller's tree): left first.  The builder puts the child that needs the SHALLOWER stack
     // on the left, which bounds the stack by the tree's Strahler number, <= log2(leaves) + 1, however deep the tree is
     // (pt_api.hip: convert_tree).
-    const bool left_first = fixed_order || ltn < rtn;
+    const bool left_first = S::kLeftFirst || fixed_order || ltn < rtn;
     const bool both = hl && hr;
     const int32_t next = (hl && (!hr || left_first)) ? L : R;
-    if (both) {
-        stk[t.sp * 64] = (STK)(left_first ? R : L);
-        t.sp++;
-    }
-    if (hl || hr) {
-        t.cur = next;
-    } else {
-        t.sp--;
-        t.cur = stk[t.sp * 64];
-    }
+    s.advance(t, both, hl || hr, next, left_first ? R : L);
 }
 
 typedef float f4v __attribute__((ext_vector_type(4)));
@@ -186,8 +221,8 @@ __device__ __forceinline__ void ld_node_lds(const P* p, float4& a, float4& b, fl
     c = make_float4(vc.x, vc.y, vc.z, vc.w); d = make_float4(vd.x, vd.y, vd.z, vd.w);
 }
 
-template <bool PRUNE, bool OCT, class STK, int TOP = 0>
-__device__ __forceinline__ void inner_step(const SceneView& sv, const V3& o, Trav& t, STK* stk) {
+template <bool PRUNE, bool OCT, int TOP = 0, class S>
+__device__ __forceinline__ void inner_step(const SceneView& sv, const V3& o, Trav& t, const S& s) {
     float4 a, b, c, d;
     if (TOP == 1 && (uint32_t)t.cur < sv.top_count) {
         ld_node_lds(reinterpret_cast<const unsigned char*>(sv.top_nodes) + (uint32_t)t.cur * (uint32_t)sizeof(DNode), a, b, c, d);
@@ -198,7 +233,7 @@ __device__ __forceinline__ void inner_step(const SceneView& sv, const V3& o, Tra
         c = ld4(nd, 2);    // rmin.z   rmax.xyz    (OCT: rnear.z  rfar.xyz)
         d = ld4(nd, 3);    // left right - -
     }
-    visit_node<PRUNE, OCT, STK>(a, b, c, d, o, t, stk, sv.fixed_order != 0);
+    visit_node<PRUNE, OCT>(a, b, c, d, o, t, s, sv.fixed_order != 0);
 }
 
 // Two primitives, both tested by this ray, give the same t: the reference keeps the one it VISITS first (scene.h:270, strict <).
@@ -287,13 +322,12 @@ __device__ __forceinline__ void leaf_test(const SceneView& sv, const Ray& ray, T
     }
 }
 
-template <class STK, bool TRI_ONLY, bool ANYHIT = false>
-__device__ __forceinline__ void leaf_step(const SceneView& sv, const Ray& ray, Trav& t, STK* stk, const bool shadow = false,
+template <bool TRI_ONLY, bool ANYHIT = false, class S>
+__device__ __forceinline__ void leaf_step(const SceneView& sv, const Ray& ray, Trav& t, const S& s, const bool shadow = false,
                                           const bool ties = false) {
     leaf_test<TRI_ONLY>(sv, ray, t, t.cur, ties);
-    if (ANYHIT && shadow && t.best.prim >= 0) t.sp = 1;      // occluded: drop the rest of the stack, the pop below ends the traversal
-    t.sp--;                       // sentinel at the stack bottom: popping an empty stack yields kDone
-    t.cur = stk[t.sp * 64];
+    if (ANYHIT && shadow && t.best.prim >= 0) s.reset(t);    // occluded: drop the rest of the stack, the pop below ends the traversal
+    s.pop(t);                     // popping an empty stack yields the done value
 }
 
 // Closest hit of one ray, run to completion (while-while loop): intersect() of scene.h:246-301.
@@ -301,16 +335,17 @@ __device__ __forceinline__ void leaf_step(const SceneView& sv, const Ray& ray, T
 template <bool PRUNE, bool STATS>
 __device__ __forceinline__ Hit intersect(const SceneView& sv, const Ray& ray, int32_t* stk, TravStats& st) {
     Trav t;
+    const LdsStack<int32_t> s{stk};
     stack_init(stk);
-    trav_begin(sv, ray, t);
+    trav_begin(sv, ray, t, s);
     while (t.cur != kDone) {
         while (t.cur >= 0) {                    // descend through inner nodes until this lane holds a leaf
             if (STATS) st.nodes++;
-            inner_step<PRUNE, false, int32_t>(sv, ray.org, t, stk);
+            inner_step<PRUNE, false>(sv, ray.org, t, s);
         }
         if (t.cur != kDone) {                   // one primitive test, then pop
             if (STATS) st.leaves++;
-            leaf_step<int32_t, false>(sv, ray, t, stk);
+            leaf_step<false>(sv, ray, t, s);
         }
     }
     return t.best;
@@ -326,15 +361,16 @@ __device__ __forceinline__ Hit intersect_any_tree(const SceneView& sv, const Sce
     Trav t;
     TravStats st;
     st.nodes = 0; st.leaves = 0;
+    const LdsStack<int32_t> s{stk};
     stack_init(stk);
-    trav_begin(sv, ray, t);
+    trav_begin(sv, ray, t, s);
     if (!(__builtin_isfinite(t.inv.x) && __builtin_isfinite(t.inv.y) && __builtin_isfinite(t.inv.z))) {
         t.redo = true;
         t.cur = kDone;
     }
     while (t.cur != kDone) {
-        while (t.cur >= 0) inner_step<PRUNE, false, int32_t>(sv, ray.org, t, stk);
-        if (t.cur != kDone) leaf_step<int32_t, false>(sv, ray, t, stk, false, true);
+        while (t.cur >= 0) inner_step<PRUNE, false>(sv, ray.org, t, s);
+        if (t.cur != kDone) leaf_step<false>(sv, ray, t, s, false, true);
     }
     rerun = t.redo;
     return t.redo ? intersect<false, false>(sv_ref, ray, stk, st) : t.best;

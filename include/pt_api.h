@@ -592,6 +592,14 @@ int pt_bvh_build_sweep_device(const pt_scene_desc* desc, pt_bvh_node* out_nodes,
  *                   holds at most 4 stack entries ("stack_entries" <= 5) with at most 126 inner nodes and 127 primitives,
  *                   rendered without PT_RENDER_NEE and outside the later rounds of pt_render_adaptive.  0 = always the LDS
  *                   stack.  Same nodes, same leaves, same order: the same bits.  Info "reg_stack" reports the last launch.
+ *   "leaf_sweep"    1 (default) a launch that "reg_stack" admits, with exact traversal, without "stats", on a scene of at most 64
+ *                   primitives staged with its octant tables ("residency" 2), finds the leaves a segment tests without the
+ *                   tree: the leaves of the internal tree are grouped by the bit pattern of their boxes at pt_scene_create
+ *                   (info "sweep_boxes": the number of groups; at most 32 are admitted), every group's box is tested once when
+ *                   the segment starts, and the candidates are kept as a 64-bit mask (trace_kernel_v2_sweep).  Exact traversal
+ *                   tests a leaf iff the ray hits the leaf's own box (see "fast_tree"), so the same leaves are tested and the
+ *                   frame is the same, bit for bit.  0 = always the tree.  A handle whose geometry was updated keeps to the
+ *                   tree.  Info "leaf_sweep" reports the last launch; node visits ("stats") always count the tree's.
  *   "octants"       1 (default) keep 8 ray-octant node tables in LDS for very small scenes, 0 = one table
  *   "fast_tree"     1 (default) traversal (exact and pruned) on the library's INTERNAL tree where pt_scene_create kept one,
  *                   0 = on the caller's tree.  Same image either way, bit for bit: the reference never prunes, so a leaf is tested iff the
@@ -633,12 +641,15 @@ int pt_bvh_build_sweep_device(const pt_scene_desc* desc, pt_bvh_node* out_nodes,
  *     bits  0-3  family: 1 trace_kernel, 2 trace_kernel_v2, 3 trace_kernel_q      bit  10  NEE
  *     bits  4-5  RES (family 1: LDS_SCENE)                                      bit  11  LIST
  *     bit   6    PRUNE       bit 7  STATS       bits 8-9  SPEC                    bit  12  POSTPONE
- *     bit  13    register stack (trace_kernel_v2_reg: the trace_kernel_v2 of the other fields with the stack in a register)
+ *     bit  13    the traversal state of a lane is a register (trace_kernel_v2_reg: the trace_kernel_v2 of the other fields with
+ *                the stack in a register; info "leaf_sweep" says which body ran: 0 that one, 1 trace_kernel_v2_sweep, which
+ *                stands in for it with the same fields, "reg_stack", "path_bank" and "lds_bytes")
  *     bits 16-23 THRESH      bits 24-39 INNER, 16-bit two's complement          bits 40-43 MINW
  *   a field the family's template does not have is 0), "path_bank" (1 = that kernel handed out path starts from a per-wave
  * register bank filled 64 at a time: trace_kernel_v2 on LDS-resident scenes of triangles with diffuse materials),
  * "reg_stack" (1 = that kernel kept its traversal stack in a register, see option "reg_stack"; "lds_bytes" of such a launch has no
- * stack columns), "frames_in_flight", "sweep_on_device" (the internal tree was built on the GPU),
+ * stack columns), "leaf_sweep" (1 = that kernel found its leaves by the box sweep, see option "leaf_sweep"), "sweep_boxes",
+ * "frames_in_flight", "sweep_on_device" (the internal tree was built on the GPU),
  * "create_us0".."create_us6" (wall microseconds of pt_scene_create: total, primitive records, caller's tree checked and re-laid,
  * internal tree built, ... re-laid, uploads + probe, tie tables). */
 int pt_scene_set_option(pt_scene* scene, const char* key, int64_t value);

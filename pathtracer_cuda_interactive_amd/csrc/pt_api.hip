@@ -265,11 +265,17 @@ struct pt_scene {
     int64_t opt_q_target = 0, opt_q_swap = 0, opt_q_low = 0;   // schedule knobs of kernel 3; 0 = automatic
     int64_t opt_v2_thresh = 0, opt_v2_inner = 0, opt_v2_minw = 0;   // 0 = auto (see pick_kernel)
     int64_t opt_reg_stack = 1;      // 1 = register traversal stack where it applies (launch_reg_stack), 0 = always the LDS stack
+    int64_t opt_leaf_sweep = 1;     // 1 = leaves found by the box sweep where it applies (launch_leaf_sweep), 0 = always the tree
+    // the groups of equal leaf boxes of tree[1] (pt_leaf_sweep.h), made at scene creation where the tree was built on the host
+    // and the scene has at most 64 primitives.  sweep_groups = 0: none (also after a geometry update: boxes that were equal need
+    // not be any more); it may exceed what a launch admits, sweep.count then stays 0.
+    SweepTable sweep{};
+    int sweep_groups = 0;
     // info of last launch
     // wall time of pt_scene_create's stages, microseconds: [0] total [1] primitive records [2] caller's tree checked and re-laid
     // [3] internal tree built [4] ... re-laid [5] uploads + probe [6] tie tables; built_on_device: the sweep ran on the GPU
     int64_t create_us[7] = {0, 0, 0, 0, 0, 0, 0}, sweep_on_device = 0;
-    int64_t info_grid = 0, info_lds_bytes = 0, info_lds_scene = 0, info_passes = 0, info_occupancy = 0, info_blocks_per_cu = 0, info_debug_reruns = 0, fast_cost_permille = 0, info_kernel = 0, info_trace_variant = 0, info_path_bank = 0, info_reg_stack = 0;
+    int64_t info_grid = 0, info_lds_bytes = 0, info_lds_scene = 0, info_passes = 0, info_occupancy = 0, info_blocks_per_cu = 0, info_debug_reruns = 0, fast_cost_permille = 0, info_kernel = 0, info_trace_variant = 0, info_path_bank = 0, info_reg_stack = 0, info_leaf_sweep = 0;
     struct PassEvents { hipEvent_t t0, t1, r0, r1; };            // trace begin, trace end (on the trace kernel's stream); resolve begin, end (caller's)
     // HIP events of the last `opt_timing_frames` render calls (a ring; default 1): a caller that enqueues frame after frame
     // without a host sync in between — bench.py's timed loop — reads every frame's kernel time afterwards (pt_get_frame_times)
@@ -830,6 +836,20 @@ int validate_and_build(const pt_scene_desc* d, pt_scene* S) {
             S->ref_levels = levels;
         }
     }
+    // the leaf sweep's groups of equal leaf boxes (pt_leaf_sweep.h), from the internal tree as the host built it
+    S->sweep = SweepTable{};
+    S->sweep_groups = 0;
+    if (S->have_fast && hosts[1] && !S->fast_is_callers_topology && N <= kSweepMaxPrims) {
+        SweepGroup groups[kSweepMaxPrims];
+        const int n = build_sweep_groups(fast.nodes.data(), (int)fast.nodes.size(), N, kLdsNodeStride, groups);
+        if (n > 0) {
+            S->sweep_groups = n;
+            if (n <= kSweepMaxBoxes) {
+                S->sweep.count = (uint32_t)n;
+                std::copy(groups, groups + n, S->sweep.g);
+            }
+        }
+    }
     // everything the scene holds is complete from here on: trace kernels run on streams of the handle's own (FrameSlot) that do
     // not synchronise with the stream the preparation kernels ran on
     HIP_TRY(hipDeviceSynchronize());
@@ -1096,6 +1116,18 @@ bool launch_reg_stack(const pt_scene* S, int res, int which, bool nee, bool list
     return reg_stack_on(res, sc.thresh, sc.inner, which == 1, T.stack_cap - 1, T.num_nodes, S->dev.num_prims);
 }
 
+// Does this launch find its leaves by the box sweep (pt_leaf_sweep.h)?  Option "leaf_sweep" allows it, the launch is one of
+// trace_kernel_v2_reg<2, false, false, MINW> (register stack, octant tables, exact, not counting), and the handle holds a group
+// table that fits: made at scene creation, dropped by a geometry update.  The kernel stands in for that table entry: same
+// LDS plan, and it reports that entry's "trace_variant", "reg_stack" and "path_bank"; info "leaf_sweep" alone tells them apart.
+using SweepFn = void (*)(SceneDev, RenderDev, LdsPlan, float4*, uint32_t*, unsigned long long*, SweepTable);
+bool launch_leaf_sweep(const pt_scene* S, int res, bool reg_stack, bool exact) {
+    return S->opt_leaf_sweep && leaf_sweep_on(reg_stack, exact, S->opt_stats != 0, res, S->dev.num_prims, (int)S->sweep.count);
+}
+SweepFn pick_kernel_sweep(int minw) {
+    return minw == 5 ? trace_kernel_v2_sweep<5> : trace_kernel_v2_sweep<6>;
+}
+
 TracePick pick_kernel(const pt_scene* S, int res, bool prune, bool stats, bool internal_tree, bool reg_stack) {
     if (S->opt_kernel >= 2) {
         const V2Schedule sc = v2_schedule(S, res, internal_tree);
@@ -1251,6 +1283,7 @@ int launch_render(pt_scene* S, const pt_render_params* p, float* out_dev, int mo
         S->info_trace_variant = 0;
         S->info_path_bank = 0;
         S->info_reg_stack = 0;
+        S->info_leaf_sweep = 0;
         if (slot.used && slot.free_stream != stream) HIP_TRY(hipStreamWaitEvent(stream, slot.free_ev, 0));
         HIP_TRY(hipMemsetAsync(slot.ctl.p, 0, (kWorkWords + kTimelineBase) * sizeof(unsigned long long), stream));
         HIP_TRY(hipEventRecord(slot.free_ev, stream));
@@ -1309,6 +1342,7 @@ int launch_render(pt_scene* S, const pt_render_params* p, float* out_dev, int mo
     QParams qp{};
     TraceFnQ fnq = nullptr;
     TraceFn fn = nullptr;
+    SweepFn fns = nullptr;           // set: this launch runs trace_kernel_v2_sweep in place of fn
     int64_t variant = 0;
     int path_bank = 0, reg_stack_used = 0;
     if (use_q) {
@@ -1322,8 +1356,11 @@ int launch_render(pt_scene* S, const pt_render_params* p, float* out_dev, int mo
                                  : pick_kernel(S, res, traversal == PT_TRAVERSAL_PRUNED, S->opt_stats != 0, which == 1, reg_stack);
         fn = pk.fn; variant = pk.variant; path_bank = pk.bank; reg_stack_used = pk.reg;
         if (!fn) return fail(PT_ERR_INVALID_ARG, "no kernel variant compiled for these v2_thresh / v2_inner options");
+        // the sweep kernel in place of the register-stack entry just picked, whose variant and plan it keeps
+        if (!listed && !nee && launch_leaf_sweep(S, res, reg_stack, traversal == PT_TRAVERSAL_EXACT))
+            fns = pick_kernel_sweep(v2_schedule(S, res, which == 1).minw);
     }
-    const void* fn_any = use_q ? reinterpret_cast<const void*>(fnq) : reinterpret_cast<const void*>(fn);
+    const void* fn_any = use_q ? reinterpret_cast<const void*>(fnq) : fns ? reinterpret_cast<const void*>(fns) : reinterpret_cast<const void*>(fn);
     const int block_threads = use_q ? kQBlock : kBlock;
     if (S->cfg_fn != fn_any || S->cfg_lds != lp.total) {
         if (lp.total > 64 * 1024)
@@ -1350,6 +1387,7 @@ int launch_render(pt_scene* S, const pt_render_params* p, float* out_dev, int mo
     S->info_trace_variant = variant;
     S->info_path_bank = path_bank;
     S->info_reg_stack = reg_stack_used;
+    S->info_leaf_sweep = fns ? 1 : 0;
     S->info_occupancy = occ;
     S->info_blocks_per_cu = bpc;
     S->info_lds_bytes = lp.total;
@@ -1453,6 +1491,9 @@ int launch_render(pt_scene* S, const pt_render_params* p, float* out_dev, int mo
         if (use_q)
             hipLaunchKernelGGL(fnq, dim3(grid), dim3(kQBlock), lp.total, tstream, S->dev, rd, lp, qp, slot.samples.p,
                                S->work_counter(), S->counters());
+        else if (fns)
+            hipLaunchKernelGGL(fns, dim3(grid), dim3(kBlock), lp.total, tstream, S->dev, rd, lp, slot.samples.p,
+                               S->work_counter(), S->counters(), S->sweep);
         else
             hipLaunchKernelGGL(fn, dim3(grid), dim3(kBlock), lp.total, tstream, S->dev, rd, lp, slot.samples.p,
                                S->work_counter(), S->counters());
@@ -1598,6 +1639,7 @@ int update_scene(pt_scene* S, const pt_scene_desc* d, int flags) {
         std::swap(S->normals.p, S->st_normals.p); std::swap(S->normals.n, S->st_normals.n);
         S->dev.prims = S->prims.p; S->dev.normals = S->normals.p;
         S->tri_only = !has_sphere;
+        S->sweep_groups = 0; S->sweep.count = 0;     // leaf boxes that were equal need not be any more: back to the tree
         us_refit = us_since(t_stage);
     }
     if (shading) {
@@ -2283,6 +2325,7 @@ int pt_scene_set_option(pt_scene* S, const char* key, int64_t value) {
     else if (k == "v2_inner") S->opt_v2_inner = value;
     else if (k == "v2_minw") S->opt_v2_minw = value;
     else if (k == "reg_stack") { if (value != 0 && value != 1) return fail(PT_ERR_INVALID_ARG, "reg_stack must be 0 or 1"); S->opt_reg_stack = value; }
+    else if (k == "leaf_sweep") { if (value != 0 && value != 1) return fail(PT_ERR_INVALID_ARG, "leaf_sweep must be 0 or 1"); S->opt_leaf_sweep = value; }
     else return fail(PT_ERR_INVALID_ARG, "unknown option " + k);
     return PT_OK;
 }
@@ -2333,6 +2376,8 @@ int pt_scene_get_info(pt_scene* S, const char* key, int64_t* value) {
     else if (k == "kernel") *value = S->info_kernel;                      // the kernel the last render ran on (1, 2 or 3)
     else if (k == "trace_variant") *value = S->info_trace_variant;        // ... and its template arguments (include/pt_api.h)
     else if (k == "path_bank") *value = S->info_path_bank;                // ... which handed out path starts from a register bank (1) or not
+    else if (k == "leaf_sweep") *value = S->info_leaf_sweep;              // ... finding its leaves by the box sweep (1: trace_kernel_v2_sweep) or on the tree (0)
+    else if (k == "sweep_boxes") *value = S->sweep_groups;                // groups of equal leaf boxes the handle holds for the sweep (0: none)
     else if (k == "reg_stack") *value = S->info_reg_stack;                // ... with the traversal stack in a register (1) or in LDS / global memory (0)
     else if (k == "block_threads") *value = S->info_kernel == 3 ? kQBlock : kBlock;
     else if (k == "frames_in_flight") *value = S->opt_frames_in_flight;

@@ -12,6 +12,7 @@
 #include <type_traits>
 
 #include "pt_layout.h"
+#include "pt_leaf_sweep.h"
 #include "pt_math.h"
 #include "pt_path_bank.h"
 #include "pt_temporal.h"
@@ -408,6 +409,30 @@ __global__ __launch_bounds__(kBlock, (kBlock > 256 ? 1 : MINW)) void trace_kerne
     constexpr int THRESH = 40, INNER = 162, SPEC = 2;
     constexpr bool NEE = false, LIST = false, REG = true;
 #include "pt_trace_v2_body.h"
+}
+
+// The leaf-sweep kernel (pt_leaf_sweep.h, body: pt_trace_sweep_body.h): trace_kernel_v2_reg<2, false, false, MINW>'s launches on
+// scenes of at most 64 primitives in at most kSweepMaxBoxes groups of equal leaf boxes (leaf_sweep_on) find their leaves by
+// testing every group's box when a segment starts instead of walking the tree.  Same leaves tested, same closest hit, same
+// frame.  A third text rather than a flag of the body above: what that body compiles to for every other instantiation stays
+// as it is.  The group table travels by value behind the arguments every trace kernel takes (SweepKernelArgs, for offsetof).
+// PT_SWEEP_LEAF_STEPS: leaf tests per iteration between two scheduler checks (-D: A/B libraries).  4: cbox 640x480x64 at
+// 2.020 / 1.989 / 1.940 ms per frame with 2 / 3 / 4 against the tree kernel's 2.112 (profiles/r11_leaf_sweep.log §3).
+#ifndef PT_SWEEP_LEAF_STEPS
+#define PT_SWEEP_LEAF_STEPS 4
+#endif
+struct SweepKernelArgs {
+    SceneDev scn; RenderDev rp; LdsPlan lp; float4* samples; uint32_t* work_counter; unsigned long long* counters; SweepTable sweep;
+};
+static_assert(offsetof(SweepKernelArgs, rp) == offsetof(TraceKernelArgs, rp), "reload_render_args reads rp at TraceKernelArgs' offset");
+template <int MINW>
+__global__ __launch_bounds__(kBlock, (kBlock > 256 ? 1 : MINW)) void trace_kernel_v2_sweep(SceneDev scn, RenderDev rp, LdsPlan lp,
+                                                                float4* __restrict__ samples,
+                                                                uint32_t* __restrict__ work_counter,
+                                                                unsigned long long* __restrict__ counters,
+                                                                SweepTable sweep) {
+    constexpr int N_LEAF = PT_SWEEP_LEAF_STEPS;
+#include "pt_trace_sweep_body.h"
 }
 
 // mode 0: fb = (prev + sum) * scale   (prev = accum if !first)        [final pass of pt_render]

@@ -1,0 +1,162 @@
+// pt_trace_sweep_body.h — the body of trace_kernel_v2_sweep (pt_kernels.h), included inside it.
+// The schedule of trace_kernel_v2 (scheduler phase at THRESH lanes, path bank) around a traversal without a tree
+// (pt_leaf_sweep.h): step (3) of the phase tests every distinct leaf box of the scene against the new segment and leaves the
+// lane a 64-bit mask of candidate primitives; the burst is leaf tests alone, lowest candidate first.  No inner step, no stack,
+// and 1/d is dead once the phase ends.  The launches that take it: leaf_sweep_on — residency 2, exact traversal on the
+// internal tree (so scn.fallback is set: ties on t are settled in the caller's visit order and a ray with a non-finite 1/d is
+// traced on the caller's tree), triangles with diffuse materials, no counting, no next-event estimation, no pixel list.
+// It expects the kernel's parameters (scn, rp, lp, samples, work_counter, counters, sweep) and MINW, N_LEAF in scope.
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    constexpr int THRESH = 40;
+    const ptd::SceneView sv = make_scene_view<2>(scn, lp, smem);
+    typedef const __attribute__((address_space(3))) unsigned char* LdsBytes;
+    typedef float f2v __attribute__((ext_vector_type(2)));
+    typedef const __attribute__((address_space(3))) f2v* LdsF2;
+
+    const int lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
+
+    WorkFeed feed;
+    feed_init(feed, rp);
+    PathBank bank;
+    bank_init(bank);
+    float bank_dx = 0.0f, bank_dy = 0.0f, bank_dz = 0.0f;
+    uint32_t bank_lo = 0, bank_hi = 0;
+    bool alive = false;
+    ptd::Ray ray;
+    ray.org = ptm::mk(0, 0, 0); ray.dir = ptm::mk(0, 0, 1); ray.tnear = 0; ray.tfar = 0;
+    ptd::Trav tv;                                  // best and redo alone are live: no node, no stack, no 1/d
+    tv.inv = ptm::mk(1, 1, 1);
+    tv.best.t = 0; tv.best.u = 0; tv.best.v = 0; tv.best.prim = -1;
+    tv.cur = 0; tv.stack_state = 0; tv.node_off = 0; tv.redo = false;
+    uint64_t cand = 0;                             // primitives whose leaf box this segment hits and that are not yet tested
+    ptm::V3 L = ptm::mk(0, 0, 0), T = ptm::mk(1, 1, 1);
+    ptm::Pcg rng;
+    rng.state = 0; rng.inc = 1;
+    int depth = 0;
+    uint32_t my_w = 0;
+    uint32_t n_paths = 0, n_segs = 0;              // of the wave (scalar registers: a phase has no vector register to spare)
+    ptd::TravStats st;
+    st.nodes = 0; st.leaves = 0;
+    ptd::SceneView sv_ref = sv;
+    sv_ref.nodes = scn.ref_nodes; sv_ref.root_ref = scn.ref_root_ref; sv_ref.node_stride = sizeof(DNode);
+    sv_ref.oct_stride = 0; sv_ref.top_nodes = nullptr; sv_ref.top_count = 0; sv_ref.fixed_order = 0;
+    int32_t* redo_stk = scn.redo_stack + ((size_t)(blockIdx.x * (kBlock / 64) + wave) * (size_t)scn.redo_cap) * 64 + lane;
+
+    for (;;) {
+        const bool idle = cand == 0ull;
+        const unsigned long long idle_mask = __ballot(idle);
+        const bool work_left = bank_work_left(bank, feed.exhausted, feed.cur, feed.end);
+        const int n_pend = __popcll(__ballot(idle && (alive || work_left)));
+        if (n_pend >= THRESH || idle_mask == ~0ull) {
+            if (n_pend == 0) break;          // every lane idle, no live path, no work left
+            // (1) finish the segments whose candidates are used up (radiance.cuh:26-75)
+            if (idle && alive && tv.redo) {
+                // 1/d is not finite: trace this ray the reference's way on the caller's tree, to completion.  tfar is not kept
+                // across the burst (the leaf tests here do not read it): a path's first segment is the camera's.
+                ptd::TravStats st_redo;
+                st_redo.nodes = 0; st_redo.leaves = 0;
+                ray.tfar = depth == 0 ? __builtin_inff() : FLT_MAX;
+                tv.best = ptd::intersect<false, false>(sv_ref, ray, redo_stk, st_redo);
+                tv.redo = false;
+            }
+            if (idle && alive) {
+                bool cont = false;
+                if (tv.best.prim < 0) {
+                    L = L + T * sv.bg;
+                } else {
+                    const ptd::Surface sf = ptd::make_surface<true>(sv, ray, tv.best);
+                    cont = ptd::shade_and_bounce<true, false>(sv, sf, ray, rng, L, T, depth, rp.rr_depth, nullptr);
+                    depth++;
+                    if (depth >= rp.max_depth) cont = false;
+                }
+                if (!cont) {
+                    samples[my_w] = make_float4(L.x, L.y, L.z, 0.0f);
+                    alive = false;
+                }
+            }
+            // (2) refill dead lanes out of the wave's path bank (pt_trace_v2_body.h has the account of it)
+            unsigned long long want = __ballot(idle && !alive);
+#pragma nounroll
+            for (int round = 0; round < 2 && want; round++) {
+                if (bank.left == 0) {
+                    feed_reserve(feed, rp, work_counter, lane);
+                    if (feed.cur >= feed.end) break;                 // every band exhausted
+                    bank_fill(bank, feed.cur, feed.end);
+                    const RenderDev rg = reload_render_args<false>();
+                    const PathStart ps = start_path<false>(rg, feed.region, bank_item(feed.cur, (uint32_t)lane));
+                    bank_dx = ps.ray.dir.x; bank_dy = ps.ray.dir.y; bank_dz = ps.ray.dir.z;
+                    bank_lo = (uint32_t)ps.rng.state; bank_hi = (uint32_t)(ps.rng.state >> 32);
+                }
+                uint32_t first;
+                const uint32_t k = bank_take(bank, (uint32_t)__popcll(want), first);
+                const uint32_t rank = lane_rank(want);
+                const bool take = idle && !alive && rank < k;
+                const int src = take ? (int)(first + rank) : lane;
+                const float dx = __shfl(bank_dx, src, 64), dy = __shfl(bank_dy, src, 64), dz = __shfl(bank_dz, src, 64);
+                const uint32_t lo = __shfl(bank_lo, src, 64), hi = __shfl(bank_hi, src, 64);
+                if (take) {
+                    const PathIndex px = path_index<false>(rp, feed.region, bank_item(feed.cur, first + rank));
+                    ray.org = ptm::mk(rp.cam_origin[0], rp.cam_origin[1], rp.cam_origin[2]);
+                    ray.dir = ptm::mk(dx, dy, dz);
+                    ray.tnear = 0.0f;
+                    rng.state = (uint64_t)hi << 32 | lo;
+                    rng.inc = (px.stream << 1u) | 1u;
+                    my_w = px.sample_index;
+                    L = ptm::mk(0, 0, 0);
+                    T = ptm::mk(1, 1, 1);
+                    depth = 0;
+                    alive = true;
+                }
+                n_paths += k;
+                want = __ballot(idle && !alive);
+            }
+            // (3) start the next segment (scene.h:247-256): the box sweep
+            n_segs += (uint32_t)__popcll(__ballot(idle && alive));
+            if (idle && alive) {
+                const ptm::V3 inv = ptm::mk(ptm::rcp_exact(ray.dir.x), ptm::rcp_exact(ray.dir.y), ptm::rcp_exact(ray.dir.z));
+                tv.best.t = FLT_MAX; tv.best.u = 0.0f; tv.best.v = 0.0f; tv.best.prim = -1;
+                // 1/d infinite on an axis: 0 * inf in the slab test is outside the argument that lets the leaf boxes alone decide
+                // (pt_api.hip: validate_and_build) -> the reference-order rerun in the next phase, no candidates
+                tv.redo = !(__builtin_isfinite(inv.x) && __builtin_isfinite(inv.y) && __builtin_isfinite(inv.z));
+                if (!tv.redo) {
+                    // the lane's octant table (trav_begin), in LDS's 32-bit address space; group offsets and masks are
+                    // wave-uniform and come from the kernel-argument segment by scalar loads
+                    const uint32_t oct = (inv.x < 0.0f ? 1u : 0u) | (inv.y < 0.0f ? 2u : 0u) | (inv.z < 0.0f ? 4u : 0u);
+                    LdsBytes table = (LdsBytes)smem + lp.nodes_off + oct * sv.oct_stride;
+                    typedef const __attribute__((address_space(4))) unsigned char* KernargPtr;
+                    typedef uint32_t u4v __attribute__((ext_vector_type(4)));
+                    typedef const __attribute__((address_space(4))) u4v* KernargGroups;
+                    KernargPtr ka = (KernargPtr)__builtin_amdgcn_kernarg_segment_ptr() + offsetof(SweepKernelArgs, sweep);
+                    const uint32_t n_groups = *(const __attribute__((address_space(4))) uint32_t*)ka;
+                    KernargGroups gp = (KernargGroups)(ka + offsetof(SweepTable, g));
+                    const ptm::V3 o = ray.org;
+                    uint32_t c_lo = 0, c_hi = 0;
+                    // one group per iteration (the loop vectoriser would pair them up into packed fp32, which issues at half rate)
+#pragma clang loop vectorize(disable) interleave(disable) unroll(disable)
+                    for (uint32_t k = 0; k < n_groups; k++) {
+                        const u4v grp = gp[k];                                    // box offset, mask low, mask high, -
+                        LdsF2 bx = (LdsF2)(table + grp.x);
+                        const f2v p0 = bx[0], p1 = bx[1], p2 = bx[2];             // near.xy | near.z far.x | far.yz
+                        // visit_node<false, true>: the same operations on the same operands
+                        const float tn = ptm::fmax2(ptm::fmax2((p0.x - o.x) * inv.x, (p0.y - o.y) * inv.y), (p1.x - o.z) * inv.z);
+                        const float tf = ptm::fmin2(ptm::fmin2((p1.y - o.x) * inv.x, (p2.x - o.y) * inv.y), (p2.y - o.z) * inv.z);
+                        const bool hit = tf >= ptm::fmax2(0.0f, tn);
+                        c_lo |= hit ? grp.y : 0u;
+                        c_hi |= hit ? grp.z : 0u;
+                    }
+                    cand = (uint64_t)c_hi << 32 | c_lo;
+                }
+            }
+        }
+        // ---- burst: N_LEAF leaf tests, lowest candidate first (exact traversal on the internal tree may test in any order)
+#pragma unroll
+        for (int k = 0; k < N_LEAF; k++) {
+            if (cand != 0ull) {
+                const int32_t prim = sweep_lowest(cand);
+                cand = sweep_clear_lowest(cand);
+                ptd::leaf_test<true, true>(sv, ray, tv, ~prim, true);
+            }
+        }
+    }
+    flush_counters<false>(counters, lane, lane == 0 ? n_paths : 0u, lane == 0 ? n_segs : 0u, st);

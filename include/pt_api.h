@@ -596,7 +596,8 @@ int pt_bvh_build_sweep_device(const pt_scene_desc* desc, pt_bvh_node* out_nodes,
  *                   primitives staged with its octant tables ("residency" 2), finds the leaves a segment tests without the
  *                   tree: the leaves of the internal tree are grouped by the bit pattern of their boxes at pt_scene_create
  *                   (info "sweep_boxes": the number of groups; at most 32 are admitted), every group's box is tested once when
- *                   the segment starts, and the candidates are kept as a 64-bit mask (trace_kernel_v2_sweep).  Exact traversal
+ *                   the segment starts, and a lane keeps one hit bit per group; a group's primitives are tested along a chain
+ *                   of records the block stages in place of the octant tables (trace_kernel_v2_sweep).  Exact traversal
  *                   tests a leaf iff the ray hits the leaf's own box (see "fast_tree"), so the same leaves are tested and the
  *                   frame is the same, bit for bit.  0 = always the tree.  A handle whose geometry was updated keeps to the
  *                   tree.  Info "leaf_sweep" reports the last launch; node visits ("stats") always count the tree's.

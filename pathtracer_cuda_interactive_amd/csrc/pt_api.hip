@@ -271,6 +271,9 @@ struct pt_scene {
     // not be any more); it may exceed what a launch admits, sweep.count then stays 0.
     SweepTable sweep{};
     int sweep_groups = 0;
+    // what a sweep launch stages in place of the octant node tables (pt_sweep_layout.h: box tables, then slot records), made
+    // and uploaded with sweep.count, dropped with it
+    DevBuf<unsigned char> sweep_tab;
     // info of last launch
     // wall time of pt_scene_create's stages, microseconds: [0] total [1] primitive records [2] caller's tree checked and re-laid
     // [3] internal tree built [4] ... re-laid [5] uploads + probe [6] tie tables; built_on_device: the sweep ran on the GPU
@@ -844,7 +847,10 @@ int validate_and_build(const pt_scene_desc* d, pt_scene* S) {
         const int n = build_sweep_groups(fast.nodes.data(), (int)fast.nodes.size(), N, kLdsNodeStride, groups);
         if (n > 0) {
             S->sweep_groups = n;
-            if (n <= kSweepMaxBoxes) {
+            std::vector<unsigned char> tab(n <= kSweepMaxBoxes ? sweep_layout_bytes((uint32_t)n, (uint32_t)N) : 0);
+            if (n <= kSweepMaxBoxes && build_sweep_layout(groups, n, fast.nodes.data(), (int)fast.nodes.size(), kLdsNodeStride, prims.data(), N, tab.data())) {
+                if ((rc = S->sweep_tab.ensure(tab.size()))) return rc;
+                HIP_TRY(hipMemcpy(S->sweep_tab.p, tab.data(), tab.size(), hipMemcpyHostToDevice));
                 S->sweep.count = (uint32_t)n;
                 std::copy(groups, groups + n, S->sweep.g);
             }
@@ -1120,9 +1126,12 @@ bool launch_reg_stack(const pt_scene* S, int res, int which, bool nee, bool list
 // trace_kernel_v2_reg<2, false, false, MINW> (register stack, octant tables, exact, not counting), and the handle holds a group
 // table that fits: made at scene creation, dropped by a geometry update.  The kernel stands in for that table entry: same
 // LDS plan, and it reports that entry's "trace_variant", "reg_stack" and "path_bank"; info "leaf_sweep" alone tells them apart.
-using SweepFn = void (*)(SceneDev, RenderDev, LdsPlan, float4*, uint32_t*, unsigned long long*, SweepTable);
-bool launch_leaf_sweep(const pt_scene* S, int res, bool reg_stack, bool exact) {
-    return S->opt_leaf_sweep && leaf_sweep_on(reg_stack, exact, S->opt_stats != 0, res, S->dev.num_prims, (int)S->sweep.count);
+// The sweep's own tables (pt_sweep_layout.h) go where that plan has the octant node tables: a launch whose tables do not fit
+// there takes the tree (a binary tree over 3 primitives or more always leaves the room).
+using SweepFn = void (*)(SceneDev, RenderDev, LdsPlan, float4*, uint32_t*, unsigned long long*, SweepLayoutDev);
+bool launch_leaf_sweep(const pt_scene* S, int res, int which, bool reg_stack, bool exact) {
+    return S->opt_leaf_sweep && leaf_sweep_on(reg_stack, exact, S->opt_stats != 0, res, S->dev.num_prims, (int)S->sweep.count) &&
+           S->sweep_tab.p && sweep_layout_fits(S->sweep.count, (uint32_t)S->dev.num_prims, (uint32_t)S->tree[which].num_nodes, kLdsNodeStride);
 }
 SweepFn pick_kernel_sweep(int minw) {
     return minw == 5 ? trace_kernel_v2_sweep<5> : trace_kernel_v2_sweep<6>;
@@ -1357,7 +1366,7 @@ int launch_render(pt_scene* S, const pt_render_params* p, float* out_dev, int mo
         fn = pk.fn; variant = pk.variant; path_bank = pk.bank; reg_stack_used = pk.reg;
         if (!fn) return fail(PT_ERR_INVALID_ARG, "no kernel variant compiled for these v2_thresh / v2_inner options");
         // the sweep kernel in place of the register-stack entry just picked, whose variant and plan it keeps
-        if (!listed && !nee && launch_leaf_sweep(S, res, reg_stack, traversal == PT_TRAVERSAL_EXACT))
+        if (!listed && !nee && launch_leaf_sweep(S, res, which, reg_stack, traversal == PT_TRAVERSAL_EXACT))
             fns = pick_kernel_sweep(v2_schedule(S, res, which == 1).minw);
     }
     const void* fn_any = use_q ? reinterpret_cast<const void*>(fnq) : fns ? reinterpret_cast<const void*>(fns) : reinterpret_cast<const void*>(fn);
@@ -1493,7 +1502,7 @@ int launch_render(pt_scene* S, const pt_render_params* p, float* out_dev, int mo
                                S->work_counter(), S->counters());
         else if (fns)
             hipLaunchKernelGGL(fns, dim3(grid), dim3(kBlock), lp.total, tstream, S->dev, rd, lp, slot.samples.p,
-                               S->work_counter(), S->counters(), S->sweep);
+                               S->work_counter(), S->counters(), SweepLayoutDev{S->sweep_tab.p, S->sweep.count, 0u});
         else
             hipLaunchKernelGGL(fn, dim3(grid), dim3(kBlock), lp.total, tstream, S->dev, rd, lp, slot.samples.p,
                                S->work_counter(), S->counters());
@@ -1640,6 +1649,7 @@ int update_scene(pt_scene* S, const pt_scene_desc* d, int flags) {
         S->dev.prims = S->prims.p; S->dev.normals = S->normals.p;
         S->tri_only = !has_sphere;
         S->sweep_groups = 0; S->sweep.count = 0;     // leaf boxes that were equal need not be any more: back to the tree
+        S->sweep_tab.release();                      // (no frame is in flight: the update synchronised before it wrote)
         us_refit = us_since(t_stage);
     }
     if (shading) {
@@ -1982,7 +1992,7 @@ int pt_scene_destroy(pt_scene* S) {
     (void)guard.enter(S->device);
     if (S->last_stream || S->have_timing) (void)hipDeviceSynchronize();
     for (auto& T : S->tree) { T.nodes.release(); T.nodes_oct.release(); } S->drop_slots(); S->prims.release(); S->normals.release(); S->materials.release(); S->emission.release();
-    S->lights.release(); S->accum.release(); S->fb_tmp.release();
+    S->lights.release(); S->sweep_tab.release(); S->accum.release(); S->fb_tmp.release();
     S->ad_sum.release(); S->ad_mom.release(); S->ad_list[0].release(); S->ad_list[1].release(); S->ad_count.release();
     S->ad_spp_tmp.release(); S->ad_err_tmp.release();
     S->dn_guide.release(); S->dn_x[0].release(); S->dn_x[1].release(); S->dn_host.release(); S->tp_host.release();

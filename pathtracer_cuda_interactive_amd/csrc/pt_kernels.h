@@ -15,6 +15,7 @@
 #include "pt_leaf_sweep.h"
 #include "pt_math.h"
 #include "pt_path_bank.h"
+#include "pt_sweep_layout.h"
 #include "pt_temporal.h"
 #include "pt_trace.h"
 
@@ -415,22 +416,78 @@ __global__ __launch_bounds__(kBlock, (kBlock > 256 ? 1 : MINW)) void trace_kerne
 // scenes of at most 64 primitives in at most kSweepMaxBoxes groups of equal leaf boxes (leaf_sweep_on) find their leaves by
 // testing every group's box when a segment starts instead of walking the tree.  Same leaves tested, same closest hit, same
 // frame.  A third text rather than a flag of the body above: what that body compiles to for every other instantiation stays
-// as it is.  The group table travels by value behind the arguments every trace kernel takes (SweepKernelArgs, for offsetof).
-// PT_SWEEP_LEAF_STEPS: leaf tests per iteration between two scheduler checks (-D: A/B libraries).  4: cbox 640x480x64 at
-// 2.020 / 1.989 / 1.940 ms per frame with 2 / 3 / 4 against the tree kernel's 2.112 (profiles/r11_leaf_sweep.log §3).
+// as it is.  The sweep's tables (pt_sweep_layout.h) come behind the arguments every trace kernel takes (SweepKernelArgs, for
+// offsetof) as a pointer and the group count, and are staged into the node region of the tree kernel's LdsPlan.
+// PT_SWEEP_LEAF_STEPS: leaf tests per iteration between two scheduler checks; PT_SWEEP_THRESH: lanes that must be able to make
+// progress for a scheduler phase to run (-D: A/B libraries).  A phase carries the whole sweep whatever its width, so it pays to
+// wait for a fuller one than the tree kernel's 40: cbox 640x480x64 at 1.669 / 1.649 / 1.693 ms per frame with 40 / 48 / 56, and
+// 1.706 / 1.669 / 1.698 / 1.679 with 3 / 4 / 5 / 6 leaf steps at 40 (profiles/r12_sweep_layout.log §7).
 #ifndef PT_SWEEP_LEAF_STEPS
 #define PT_SWEEP_LEAF_STEPS 4
 #endif
+#ifndef PT_SWEEP_THRESH
+#define PT_SWEEP_THRESH 48
+#endif
+struct SweepLayoutDev {
+    const unsigned char* tab;       // box tables, then slot records (build_sweep_layout), global memory
+    uint32_t groups;                // 1 .. kSweepMaxBoxes
+    uint32_t pad;
+};
 struct SweepKernelArgs {
-    SceneDev scn; RenderDev rp; LdsPlan lp; float4* samples; uint32_t* work_counter; unsigned long long* counters; SweepTable sweep;
+    SceneDev scn; RenderDev rp; LdsPlan lp; float4* samples; uint32_t* work_counter; unsigned long long* counters; SweepLayoutDev sweep;
 };
 static_assert(offsetof(SweepKernelArgs, rp) == offsetof(TraceKernelArgs, rp), "reload_render_args reads rp at TraceKernelArgs' offset");
+
+// make_scene_view<2> for the sweep kernel: the node region of the plan takes the box tables as they are and the slot records
+// with their edges made here (sweep_stage_record); prims, normals, materials and emission are staged where every kernel has
+// them, shading reads them by primitive id.  sv.nodes names the region but nothing walks it.  Called by every thread of the block.
+__device__ __forceinline__ ptd::SceneView make_sweep_view(const SceneDev& scn, const LdsPlan& lp, const SweepLayoutDev& sweep,
+                                                          unsigned char* smem) {
+    const uint32_t slots_off = sweep_slots_off(sweep.groups);
+    stage_to_lds(smem + lp.nodes_off, sweep.tab, slots_off);
+    const DPrim* gslots = reinterpret_cast<const DPrim*>(sweep.tab + slots_off);
+    DPrim* lslots = reinterpret_cast<DPrim*>(smem + lp.nodes_off + slots_off);
+    for (uint32_t i = threadIdx.x; i < (uint32_t)scn.num_prims; i += blockDim.x) {
+        const float4 a = ptd::ld4(gslots + i, 0), b = ptd::ld4(gslots + i, 1), c = ptd::ld4(gslots + i, 2);
+        DPrim g;
+        g.v[0] = a.x; g.v[1] = a.y; g.v[2] = a.z; g.v[3] = a.w; g.v[4] = b.x; g.v[5] = b.y; g.v[6] = b.z; g.v[7] = b.w; g.v[8] = c.x;
+        g.info = __builtin_bit_cast(int32_t, c.y); g.light = __builtin_bit_cast(int32_t, c.z); g.pad = __builtin_bit_cast(int32_t, c.w);
+        const DPrim r = sweep_stage_record(g);
+        float4* d = reinterpret_cast<float4*>(lslots + i);
+        d[0] = make_float4(r.v[0], r.v[1], r.v[2], r.v[3]);
+        d[1] = make_float4(r.v[4], r.v[5], r.v[6], r.v[7]);
+        d[2] = make_float4(r.v[8], c.y, c.z, c.w);
+    }
+    stage_to_lds(smem + lp.prims_off, scn.prims, (uint32_t)scn.num_prims * sizeof(DPrim));
+    stage_to_lds(smem + lp.normals_off, scn.normals, (uint32_t)scn.num_prims * sizeof(DNormals));
+    stage_to_lds(smem + lp.mats_off, scn.materials, (uint32_t)scn.num_materials * sizeof(DMaterial));
+    stage_to_lds(smem + lp.emis_off, scn.emission, (uint32_t)scn.num_emission * sizeof(DEmission));
+    __syncthreads();
+    ptd::SceneView sv;
+    sv.top_nodes = nullptr;
+    sv.top_count = 0;
+    sv.nodes = reinterpret_cast<const DNode*>(smem + lp.nodes_off);
+    sv.prims = reinterpret_cast<const DPrim*>(smem + lp.prims_off);
+    sv.normals = reinterpret_cast<const DNormals*>(smem + lp.normals_off);
+    sv.materials = reinterpret_cast<const DMaterial*>(smem + lp.mats_off);
+    sv.emission = reinterpret_cast<const DEmission*>(smem + lp.emis_off);
+    sv.node_stride = kLdsNodeStride;
+    sv.oct_stride = sweep_box_pitch(sweep.groups);
+    sv.lights = scn.lights;
+    sv.num_emission = scn.num_emission;
+    sv.root_ref = scn.root_ref;
+    sv.fixed_order = scn.fixed_order;
+    sv.ref_nodes = scn.ref_nodes; sv.ref_path = scn.ref_path; sv.ref_anc = scn.ref_anc; sv.ref_levels = scn.ref_levels;
+    sv.bg = ptm::mk(scn.bg[0], scn.bg[1], scn.bg[2]);
+    return sv;
+}
+
 template <int MINW>
 __global__ __launch_bounds__(kBlock, (kBlock > 256 ? 1 : MINW)) void trace_kernel_v2_sweep(SceneDev scn, RenderDev rp, LdsPlan lp,
                                                                 float4* __restrict__ samples,
                                                                 uint32_t* __restrict__ work_counter,
                                                                 unsigned long long* __restrict__ counters,
-                                                                SweepTable sweep) {
+                                                                SweepLayoutDev sweep) {
     constexpr int N_LEAF = PT_SWEEP_LEAF_STEPS;
 #include "pt_trace_sweep_body.h"
 }

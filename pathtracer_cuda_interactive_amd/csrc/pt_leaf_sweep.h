@@ -3,11 +3,12 @@
 // On the internal tree exact traversal tests a leaf if and only if the ray hits the leaf's own box (pt_api.hip,
 // validate_and_build: the slab test is monotone in the box and every box contains its children's).  The tree is one way to
 // find that set; for a scene of a few dozen primitives it is cheaper to test every DISTINCT leaf box once when the segment
-// starts, at the width of the scheduler phase, and to keep the candidates as a 64-bit mask of primitives.  Leaves whose boxes
-// are equal bit for bit (the two triangles of an axis-aligned quad) pass or fail together and share one test: a group.
+// starts, at the width of the scheduler phase.  Leaves whose boxes are equal bit for bit (the two triangles of an axis-aligned
+// quad) pass or fail together and share one test: a group.
 //
-// A group names its box by the byte offset inside the staged node table: a leaf's box is the left or the right half of its
-// parent's record, and every octant table holds it at that offset as (near planes, far planes).
+// A group names its box by the byte offset inside a node table: a leaf's box is the left or the right half of its parent's
+// record, and every octant table holds it at that offset as (near planes, far planes).  The groups made here are what
+// pt_sweep_layout.h lays out for the kernel: one box table per octant, one chained record per primitive.
 //
 // The header needs no HIP header, so the CPU test tests/native/leaf_sweep_check.cpp runs the same code.
 #pragma once
@@ -39,7 +40,7 @@ struct alignas(16) SweepGroup {
 };
 static_assert(sizeof(SweepGroup) == 16, "SweepGroup is one 16-byte scalar load");
 
-// What the kernel receives (by value, after the arguments every trace kernel takes): read with scalar loads, one group each.
+// The groups of a scene as the handle keeps them (the kernel receives the layout made of them: pt_sweep_layout.h).
 struct SweepTable {
     uint32_t count;
     uint32_t pad[3];
@@ -48,7 +49,7 @@ struct SweepTable {
 
 PT_SWEEP_HD uint64_t sweep_group_mask(const SweepGroup& g) { return (uint64_t)g.mask_hi << 32 | g.mask_lo; }
 
-// The candidate mask of a lane: take the lowest primitive, clear it.  (m != 0.)
+// A mask of primitives: take the lowest, clear it.  (m != 0.)
 PT_SWEEP_HD int32_t sweep_lowest(uint64_t m) { return (int32_t)__builtin_ctzll(m); }
 PT_SWEEP_HD uint64_t sweep_clear_lowest(uint64_t m) { return m & (m - 1ull); }
 

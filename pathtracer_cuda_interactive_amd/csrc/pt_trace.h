@@ -258,30 +258,13 @@ __device__ __forceinline__ bool ref_visits_first(const SceneView& sv, const V3& 
 // TRI_ONLY: the scene holds no sphere, the sphere branch is compiled out.
 // ANYHIT (kernels built with next-event estimation): a lane tracing a shadow ray (`shadow`) stops at the first hit.
 // leaf_test: the primitive test alone, for leaf reference `ref` (= ~primitive); leaf_step: test of t.cur, then pop.
-// SWEEP (trace_kernel_v2_sweep alone; every other caller compiles the text it always had): the leaf test of a kernel that
-// holds no 1/d across its burst and traces no shadow ray, on a scene of triangles staged in LDS.
-//   - The primitive record is addressed in LDS's own 32-bit address space.
-//   - `tt < ray.tfar` is not tested.  tfar is +inf (camera ray) or FLT_MAX (after a bounce), and a hit is kept only if
-//     tt < best.t, or tt == best.t with a hit already recorded; best.t starts at FLT_MAX and only ever takes a kept tt, so
-//     best.t <= FLT_MAX <= tfar and every kept tt satisfies tt < tfar already (strictly in the tie case too: a recorded
-//     hit's t is below FLT_MAX).  Dropping the compare changes no kept hit.
-//   - A tie on t recomputes 1/d from the direction (rcp_exact of the same bits trav_begin's was made from), so the three
-//     reciprocals and the sign compares of the box test on the caller's tree live inside the tie branch only.
-template <bool TRI_ONLY, bool SWEEP = false>
+template <bool TRI_ONLY>
 __device__ __forceinline__ void leaf_test(const SceneView& sv, const Ray& ray, Trav& t, const int32_t ref, const bool ties) {
-    static_assert(!SWEEP || TRI_ONLY, "the sweep kernel is compiled for triangles");
     const int32_t prim = ~ref;
-    float4 a, b, c;
-    if constexpr (SWEEP) {
-        const lds_f4v* pr = (const lds_f4v*)sv.prims + (uint32_t)prim * (uint32_t)(sizeof(DPrim) / 16);
-        const f4v va = pr[0], vb = pr[1], vc = pr[2];
-        a = make_float4(va.x, va.y, va.z, va.w); b = make_float4(vb.x, vb.y, vb.z, vb.w); c = make_float4(vc.x, vc.y, vc.z, vc.w);
-    } else {
-        const DPrim* pr = sv.prims + prim;
-        a = ld4(pr, 0);
-        b = ld4(pr, 1);
-        c = ld4(pr, 2);
-    }
+    const DPrim* pr = sv.prims + prim;
+    const float4 a = ld4(pr, 0);
+    const float4 b = ld4(pr, 1);
+    const float4 c = ld4(pr, 2);
     const V3 o = ray.org;
     const int32_t info = __builtin_bit_cast(int32_t, c.y);
     if (TRI_ONLY || info >= 0) {
@@ -298,12 +281,10 @@ __device__ __forceinline__ void leaf_test(const SceneView& sv, const Ray& ray, T
             const V3 s2 = cross(s, e1);
             const float v = dot(ray.dir, s2) * inv_divisor;
             const float tt = dot(e2, s2) * inv_divisor;
-            if (tt > ray.tnear && (SWEEP || tt < ray.tfar) && u >= 0.0f && v >= 0.0f && u + v <= 1.0f) {
+            if (tt > ray.tnear && tt < ray.tfar && u >= 0.0f && v >= 0.0f && u + v <= 1.0f) {
                 bool take = tt < t.best.t;
                 if (ties && tt == t.best.t && t.best.prim >= 0) {
-                    V3 inv = t.inv;
-                    if constexpr (SWEEP) inv = mk(rcp_exact(ray.dir.x), rcp_exact(ray.dir.y), rcp_exact(ray.dir.z));
-                    take = ref_visits_first(sv, o, inv, t.best.prim, prim);
+                    take = ref_visits_first(sv, o, t.inv, t.best.prim, prim);
                 }
                 if (take) { t.best.t = tt; t.best.u = u; t.best.v = v; t.best.prim = prim; }
             }
@@ -341,6 +322,53 @@ __device__ __forceinline__ void leaf_test(const SceneView& sv, const Ray& ray, T
             }
         }
     }
+}
+
+// The leaf test of trace_kernel_v2_sweep, a kernel that holds no 1/d across its burst and traces no shadow ray, on a scene of
+// triangles: Möller–Trumbore as in leaf_test on slot record `slot` of the sweep layout (pt_sweep_layout.h) as the block staged
+// it into LDS at `slots` — p0, the edges e1 = p1 - p0 and e2 = p2 - p0 (subtracted when the record was staged: the same
+// operation on the same operands), info, light and the link word.  The link names the primitive, which goes into best.prim
+// and into ref_visits_first; what is left of it is returned: the next slot of the group's chain, 0 = none.
+//   - The record is addressed in LDS's own 32-bit address space.
+//   - `tt < ray.tfar` is not tested.  tfar is +inf (camera ray) or FLT_MAX (after a bounce), and a hit is kept only if
+//     tt < best.t, or tt == best.t with a hit already recorded; best.t starts at FLT_MAX and only ever takes a kept tt, so
+//     best.t <= FLT_MAX <= tfar and every kept tt satisfies tt < tfar already (strictly in the tie case too: a recorded
+//     hit's t is below FLT_MAX).  Dropping the compare changes no kept hit.
+//   - A tie on t recomputes 1/d from the direction (rcp_exact of the same bits trav_begin's was made from), so the three
+//     reciprocals and the sign compares of the box test on the caller's tree live inside the tie branch only.
+__device__ __forceinline__ uint32_t leaf_test_slot(const SceneView& sv, const lds_f4v* slots, const Ray& ray, Trav& t, const uint32_t slot) {
+    typedef const __attribute__((address_space(3))) unsigned char* LdsBytes;
+    static_assert(sizeof(DPrim) == 48, "slot * 48 as two shift-adds (the compiler's own choice is a 64-bit multiply-add)");
+    const lds_f4v* pr = (const lds_f4v*)(((LdsBytes)slots + (slot << 5)) + (slot << 4));
+    const f4v a = pr[0], b = pr[1], c = pr[2];
+    const float link_bits = c.w;            // (a copy: __builtin_bit_cast on the vector element itself reads element 0)
+    const uint32_t link = __builtin_bit_cast(uint32_t, link_bits);
+    const int32_t prim = (int32_t)(link & 0xffu);
+    const V3 o = ray.org;
+    const V3 p0 = mk(a.x, a.y, a.z), e1 = mk(a.w, b.x, b.y), e2 = mk(b.z, b.w, c.x);
+    const V3 s1 = cross(ray.dir, e2);
+    const float divisor = dot(s1, e1);
+    if (divisor != 0.0f) {
+        const float inv_divisor = rcp_exact(divisor);
+        const V3 s = o - p0;
+        const float u = dot(s, s1) * inv_divisor;
+        const V3 s2 = cross(s, e1);
+        const float v = dot(ray.dir, s2) * inv_divisor;
+        const float tt = dot(e2, s2) * inv_divisor;
+        if (tt > ray.tnear && u >= 0.0f && v >= 0.0f && u + v <= 1.0f) {
+            bool take = tt < t.best.t;
+            if (tt == t.best.t && t.best.prim >= 0) {
+                // (the empty asm keeps the reciprocals in here: left alone, the compiler computes them once ahead of the unrolled
+                // leaf steps of a burst, ~50 instructions on every iteration for a branch that is almost never taken)
+                float dx = ray.dir.x, dy = ray.dir.y, dz = ray.dir.z;
+                asm volatile("" : "+v"(dx), "+v"(dy), "+v"(dz));
+                const V3 inv = mk(rcp_exact(dx), rcp_exact(dy), rcp_exact(dz));
+                take = ref_visits_first(sv, o, inv, t.best.prim, prim);
+            }
+            if (take) { t.best.t = tt; t.best.u = u; t.best.v = v; t.best.prim = prim; }
+        }
+    }
+    return link >> 8;
 }
 
 template <bool TRI_ONLY, bool ANYHIT = false, class S>

@@ -1,17 +1,22 @@
 // pt_trace_sweep_body.h — the body of trace_kernel_v2_sweep (pt_kernels.h), included inside it.
 // The schedule of trace_kernel_v2 (scheduler phase at THRESH lanes, path bank) around a traversal without a tree
-// (pt_leaf_sweep.h): step (3) of the phase tests every distinct leaf box of the scene against the new segment and leaves the
-// lane a 64-bit mask of candidate primitives; the burst is leaf tests alone, lowest candidate first.  No inner step, no stack,
-// and 1/d is dead once the phase ends.  The launches that take it: leaf_sweep_on — residency 2, exact traversal on the
-// internal tree (so scn.fallback is set: ties on t are settled in the caller's visit order and a ray with a non-finite 1/d is
-// traced on the caller's tree), triangles with diffuse materials, no counting, no next-event estimation, no pixel list.
+// (pt_leaf_sweep.h, pt_sweep_layout.h): step (3) of the phase tests every distinct leaf box of the scene against the new segment
+// and leaves the lane one hit bit per group; the burst is leaf tests alone, group by group, each group's primitives along the
+// chain of its slot records.  No inner step, no stack, and 1/d is dead once the phase ends.  The block stages the sweep's own
+// tables (box tables, slot records) where the tree kernel stages the 8 octant node tables: the tree is never walked here, and
+// a rerun reads the caller's tree in global memory.  The launches that take it: leaf_sweep_on — residency 2, exact traversal
+// on the internal tree (so scn.fallback is set: ties on t are settled in the caller's visit order and a ray with a non-finite
+// 1/d is traced on the caller's tree), triangles with diffuse materials, no counting, no next-event estimation, no pixel list.
 // It expects the kernel's parameters (scn, rp, lp, samples, work_counter, counters, sweep) and MINW, N_LEAF in scope.
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    constexpr int THRESH = 40;
-    const ptd::SceneView sv = make_scene_view<2>(scn, lp, smem);
+    constexpr int THRESH = PT_SWEEP_THRESH;
     typedef const __attribute__((address_space(3))) unsigned char* LdsBytes;
     typedef float f2v __attribute__((ext_vector_type(2)));
     typedef const __attribute__((address_space(3))) f2v* LdsF2;
+    const uint32_t n_groups = sweep.groups;                        // 1 .. kSweepMaxBoxes, the loop's only scalar input
+    const uint32_t box_pitch = sweep_box_pitch(n_groups);
+    const ptd::SceneView sv = make_sweep_view(scn, lp, sweep, smem);
+    const ptd::lds_f4v* slots = (const ptd::lds_f4v*)(smem + lp.nodes_off + sweep_slots_off(n_groups));
 
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
@@ -29,7 +34,8 @@
     tv.inv = ptm::mk(1, 1, 1);
     tv.best.t = 0; tv.best.u = 0; tv.best.v = 0; tv.best.prim = -1;
     tv.cur = 0; tv.stack_state = 0; tv.node_off = 0; tv.redo = false;
-    uint64_t cand = 0;                             // primitives whose leaf box this segment hits and that are not yet tested
+    uint32_t hits = 0;                             // groups whose box this segment hits and that are not yet taken up: group k = bit 31 - k
+    uint32_t pend = 0;                             // the slot to test next inside the group taken up last, 0 = none
     ptm::V3 L = ptm::mk(0, 0, 0), T = ptm::mk(1, 1, 1);
     ptm::Pcg rng;
     rng.state = 0; rng.inc = 1;
@@ -44,7 +50,7 @@
     int32_t* redo_stk = scn.redo_stack + ((size_t)(blockIdx.x * (kBlock / 64) + wave) * (size_t)scn.redo_cap) * 64 + lane;
 
     for (;;) {
-        const bool idle = cand == 0ull;
+        const bool idle = (hits | pend) == 0u;
         const unsigned long long idle_mask = __ballot(idle);
         const bool work_left = bank_work_left(bank, feed.exhausted, feed.cur, feed.end);
         const int n_pend = __popcll(__ballot(idle && (alive || work_left)));
@@ -120,42 +126,47 @@
                 // (pt_api.hip: validate_and_build) -> the reference-order rerun in the next phase, no candidates
                 tv.redo = !(__builtin_isfinite(inv.x) && __builtin_isfinite(inv.y) && __builtin_isfinite(inv.z));
                 if (!tv.redo) {
-                    // the lane's octant table (trav_begin), in LDS's 32-bit address space; group offsets and masks are
-                    // wave-uniform and come from the kernel-argument segment by scalar loads
+                    // the lane's octant box table, in LDS's 32-bit address space, read front to back: two groups per
+                    // iteration, no table of offsets or masks, one hit bit per group shifted in (hits = 2 * hits + hit)
                     const uint32_t oct = (inv.x < 0.0f ? 1u : 0u) | (inv.y < 0.0f ? 2u : 0u) | (inv.z < 0.0f ? 4u : 0u);
-                    LdsBytes table = (LdsBytes)smem + lp.nodes_off + oct * sv.oct_stride;
-                    typedef const __attribute__((address_space(4))) unsigned char* KernargPtr;
-                    typedef uint32_t u4v __attribute__((ext_vector_type(4)));
-                    typedef const __attribute__((address_space(4))) u4v* KernargGroups;
-                    KernargPtr ka = (KernargPtr)__builtin_amdgcn_kernarg_segment_ptr() + offsetof(SweepKernelArgs, sweep);
-                    const uint32_t n_groups = *(const __attribute__((address_space(4))) uint32_t*)ka;
-                    KernargGroups gp = (KernargGroups)(ka + offsetof(SweepTable, g));
+                    LdsF2 bx = (LdsF2)((LdsBytes)smem + lp.nodes_off + oct * box_pitch);
                     const ptm::V3 o = ray.org;
-                    uint32_t c_lo = 0, c_hi = 0;
-                    // one group per iteration (the loop vectoriser would pair them up into packed fp32, which issues at half rate)
-#pragma clang loop vectorize(disable) interleave(disable) unroll(disable)
-                    for (uint32_t k = 0; k < n_groups; k++) {
-                        const u4v grp = gp[k];                                    // box offset, mask low, mask high, -
-                        LdsF2 bx = (LdsF2)(table + grp.x);
-                        const f2v p0 = bx[0], p1 = bx[1], p2 = bx[2];             // near.xy | near.z far.x | far.yz
-                        // visit_node<false, true>: the same operations on the same operands
+                    // visit_node<false, true>: the same operations on the same operands (near.xy | near.z far.x | far.yz)
+                    auto box_hit = [&](const f2v p0, const f2v p1, const f2v p2) -> uint32_t {
                         const float tn = ptm::fmax2(ptm::fmax2((p0.x - o.x) * inv.x, (p0.y - o.y) * inv.y), (p1.x - o.z) * inv.z);
                         const float tf = ptm::fmin2(ptm::fmin2((p1.y - o.x) * inv.x, (p2.x - o.y) * inv.y), (p2.y - o.z) * inv.z);
-                        const bool hit = tf >= ptm::fmax2(0.0f, tn);
-                        c_lo |= hit ? grp.y : 0u;
-                        c_hi |= hit ? grp.z : 0u;
+                        return tf >= ptm::fmax2(0.0f, tn) ? 1u : 0u;
+                    };
+                    uint32_t h = 0;
+                    // (the loop vectoriser would pair the groups up into packed fp32, which issues at half rate)
+#pragma clang loop vectorize(disable) interleave(disable) unroll(disable)
+                    for (uint32_t k = n_groups >> 1; k != 0; k--) {
+                        const f2v a0 = bx[0], a1 = bx[1], a2 = bx[2], b0 = bx[3], b1 = bx[4], b2 = bx[5];
+                        bx += 6;
+                        h = 2u * h + box_hit(a0, a1, a2);
+                        h = 2u * h + box_hit(b0, b1, b2);
                     }
-                    cand = (uint64_t)c_hi << 32 | c_lo;
+                    if (n_groups & 1u) h = 2u * h + box_hit(bx[0], bx[1], bx[2]);      // an odd count: the last group alone
+                    hits = sweep_hits_align(h, n_groups);
                 }
             }
         }
-        // ---- burst: N_LEAF leaf tests, lowest candidate first (exact traversal on the internal tree may test in any order)
+        // ---- burst: N_LEAF leaf tests.  A lane goes on inside the group it took up last (pend: the link of the record just
+        // tested), else it takes up the first group whose hit bit is set: groups in table order, a group's primitives in ascending
+        // order.  That is not the order of the tree kernel, and need not be: exact traversal on the internal tree may test the
+        // leaves in ANY order (pt_api.hip: validate_and_build) — the set of leaves tested is the set whose box the ray hits,
+        // the closest hit is the minimum over that set, and where two of them tie on t the leaf test asks the caller's tree
+        // which one the reference visits first (ref_visits_first), a question of the two primitives alone, not of which was
+        // tested first.
 #pragma unroll
         for (int k = 0; k < N_LEAF; k++) {
-            if (cand != 0ull) {
-                const int32_t prim = sweep_lowest(cand);
-                cand = sweep_clear_lowest(cand);
-                ptd::leaf_test<true, true>(sv, ray, tv, ~prim, true);
+            if ((hits | pend) != 0u) {
+                uint32_t slot = pend;
+                if (pend == 0u) {
+                    slot = sweep_first_group(hits);
+                    hits = sweep_clear_group(hits, slot);
+                }
+                pend = ptd::leaf_test_slot(sv, slots, ray, tv, slot);
             }
         }
     }

@@ -15,6 +15,7 @@
 #include "pt_leaf_sweep.h"
 #include "pt_math.h"
 #include "pt_path_bank.h"
+#include "pt_path_index.h"
 #include "pt_sweep_layout.h"
 #include "pt_temporal.h"
 #include "pt_trace.h"
@@ -55,12 +56,6 @@ struct WorkFeed {
     bool exhausted;
 };
 
-__device__ __forceinline__ uint32_t region_rows(const RenderDev& rp, uint32_t region) {
-    const uint32_t first = region * (uint32_t)rp.rows_per_region;
-    const uint32_t nrows = (uint32_t)rp.num_rows;
-    return first >= nrows ? 0u : min((uint32_t)rp.rows_per_region, nrows - first);
-}
-
 __device__ __forceinline__ void feed_init(WorkFeed& f, const RenderDev& rp) {
     f.cur = 0; f.end = 0; f.tried = 0; f.exhausted = false;
     const uint32_t xcc = (uint32_t)__builtin_amdgcn_s_getreg(6164) & 15u;     // hwreg(HW_REG_XCC_ID, 0, 4)
@@ -93,55 +88,6 @@ struct PathStart {
     ptm::Pcg rng;
     uint32_t sample_index;   // slot in the sample-major scratch buffer
 };
-
-// What a work item stands for: pixel, PCG stream and slot in the scratch buffer.  Pure integer arithmetic on the item number
-// and launch constants, shared by start_path and by the hand-out of the path bank (trace_kernel_v2).
-struct PathIndex {
-    int col, j;              // image column and row
-    int32_t img_width;
-    uint64_t stream;         // PCG stream of the (pixel, sample)
-    uint32_t sample_index;   // slot in the sample-major scratch buffer
-};
-
-// LIST: an adaptive round after the first (RenderDev::list), a compile-time variant so that plain frames keep their code.
-template <bool LIST = false>
-__device__ __forceinline__ PathIndex path_index(const RenderDev& rp, uint32_t region, uint32_t item) {
-    const uint32_t npix_r = region_rows(rp, region) * (uint32_t)rp.width;
-    uint32_t s_local, rr;
-    int i;
-    if (rp.row_major) {
-        // all samples of a row before the next row: the waves of an XCD work on a few rows of its band at a time, so the
-        // primary rays (and what they hit) of one moment come from a small part of the scene
-        const uint32_t row_s = fastdiv(item, rp.div_width);                    // item / width = row * spp + sample
-        i = (int)(item - row_s * (uint32_t)rp.width);
-        rr = fastdiv(row_s, rp.div_spp);                                       // / spp_pass
-        s_local = row_s - rr * (uint32_t)rp.spp_pass;
-    } else {
-        s_local = fastdiv(item, (int)region == rp.short_region ? rp.div_npix_last : rp.div_npix_full);   // item / npix_r
-        const uint32_t pix_r = item - s_local * npix_r;
-        rr = fastdiv(pix_r, rp.div_width);                                                                // pix_r / width
-        i = (int)(pix_r - rr * (uint32_t)rp.width);
-    }
-    const uint32_t local_row = region * (uint32_t)rp.rows_per_region + rr;
-    // adaptive rounds: local_row is a position in the list of pixels still sampled (a frame of width 1, i == 0)
-    uint32_t img_row = local_row;
-    int col = i;
-    if (LIST) {
-        const uint32_t e = rp.list[local_row];
-        img_row = fastdiv(e, rp.div_img_width);
-        col = (int)(e - img_row * (uint32_t)rp.img_width);
-    }
-    const int32_t img_width = LIST ? rp.img_width : rp.width;
-    const int j = rp.row_begin + (int)img_row * rp.row_step;
-    const uint64_t pixel_index = (uint64_t)j * (uint64_t)img_width + (uint64_t)col;
-    PathIndex px;
-    px.col = col;
-    px.j = j;
-    px.img_width = img_width;
-    px.stream = pixel_index * (uint64_t)rp.stream_stride + (uint64_t)(rp.sample_base + (int)s_local);
-    px.sample_index = s_local * rp.npix + local_row * (uint32_t)rp.width + (uint32_t)i;
-    return px;
-}
 
 // main.cu:32-44 for region-local work item `item` of `region`: (sample, pixel) -> PCG stream, jitter, primary ray.
 template <bool LIST = false>
@@ -199,6 +145,13 @@ __device__ __forceinline__ RenderDev reload_render_args() {
 constexpr bool path_bank_on(int res, int spec, bool nee, bool list, int thresh, int inner) {
     return PT_PATH_BANK && (res == 1 || res == 2) && spec == 2 && !nee && !list && thresh == 40 && inner == 162;
 }
+
+// Which bank kernels also carry the item's index (BankIndex: three more registers per lane) and hand it out in place of
+// computing path_index again in the lane that takes a path.  The sweep kernel always does (pt_trace_sweep_body.h).  Of the
+// tree kernels those that keep ScratchSize 0 and their occupancy with it: at 5 blocks per CU the register-stack kernels and the
+// LDS-stack kernels that do not count; every instantiation at 6 blocks per CU sits at its cap of 80 registers and would spill
+// (profiles/r13_phase_overhead.log §2).
+constexpr bool bank_index_on(bool reg, bool stats, int minw) { return minw <= 5 && (reg || !stats); }
 
 __device__ __forceinline__ void stage_to_lds(void* dst, const void* src, uint32_t bytes) {
     float4* d = reinterpret_cast<float4*>(dst);

@@ -338,8 +338,11 @@ __device__ __forceinline__ void leaf_test(const SceneView& sv, const Ray& ray, T
 //     reciprocals and the sign compares of the box test on the caller's tree live inside the tie branch only.
 __device__ __forceinline__ uint32_t leaf_test_slot(const SceneView& sv, const lds_f4v* slots, const Ray& ray, Trav& t, const uint32_t slot) {
     typedef const __attribute__((address_space(3))) unsigned char* LdsBytes;
-    static_assert(sizeof(DPrim) == 48, "slot * 48 as two shift-adds (the compiler's own choice is a 64-bit multiply-add)");
-    const lds_f4v* pr = (const lds_f4v*)(((LdsBytes)slots + (slot << 5)) + (slot << 4));
+    // slot * 48 + base as one 24-bit multiply-add at full rate, exact for a slot below 64 (the compiler's own choice for the
+    // 32-bit product is two shifts and a three-way add)
+    static_assert(sizeof(DPrim) == 48 && ptl::kSweepMaxPrims * sizeof(DPrim) < (1u << 24), "slot * 48 in 24 bits");
+    __builtin_assume(slot < (uint32_t)ptl::kSweepMaxPrims);
+    const lds_f4v* pr = (const lds_f4v*)((LdsBytes)slots + slot * (uint32_t)sizeof(DPrim));
     const f4v a = pr[0], b = pr[1], c = pr[2];
     const float link_bits = c.w;            // (a copy: __builtin_bit_cast on the vector element itself reads element 0)
     const uint32_t link = __builtin_bit_cast(uint32_t, link_bits);

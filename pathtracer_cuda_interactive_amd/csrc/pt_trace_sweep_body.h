@@ -27,6 +27,7 @@
     bank_init(bank);
     float bank_dx = 0.0f, bank_dy = 0.0f, bank_dz = 0.0f;
     uint32_t bank_lo = 0, bank_hi = 0;
+    uint32_t bank_w = 0, bank_inc_lo = 0, bank_inc_hi = 0;     // BankIndex (pt_path_index.h)
     bool alive = false;
     ptd::Ray ray;
     ray.org = ptm::mk(0, 0, 0); ray.dir = ptm::mk(0, 0, 1); ray.tnear = 0; ray.tfar = 0;
@@ -93,6 +94,8 @@
                     const PathStart ps = start_path<false>(rg, feed.region, bank_item(feed.cur, (uint32_t)lane));
                     bank_dx = ps.ray.dir.x; bank_dy = ps.ray.dir.y; bank_dz = ps.ray.dir.z;
                     bank_lo = (uint32_t)ps.rng.state; bank_hi = (uint32_t)(ps.rng.state >> 32);
+                    const BankIndex bi = bank_index_pack(ps.sample_index, ps.rng.inc);
+                    bank_w = bi.sample_index; bank_inc_lo = bi.inc_lo; bank_inc_hi = bi.inc_hi;
                 }
                 uint32_t first;
                 const uint32_t k = bank_take(bank, (uint32_t)__popcll(want), first);
@@ -101,14 +104,14 @@
                 const int src = take ? (int)(first + rank) : lane;
                 const float dx = __shfl(bank_dx, src, 64), dy = __shfl(bank_dy, src, 64), dz = __shfl(bank_dz, src, 64);
                 const uint32_t lo = __shfl(bank_lo, src, 64), hi = __shfl(bank_hi, src, 64);
+                const uint32_t w = __shfl(bank_w, src, 64), inc_lo = __shfl(bank_inc_lo, src, 64), inc_hi = __shfl(bank_inc_hi, src, 64);
                 if (take) {
-                    const PathIndex px = path_index<false>(rp, feed.region, bank_item(feed.cur, first + rank));
                     ray.org = ptm::mk(rp.cam_origin[0], rp.cam_origin[1], rp.cam_origin[2]);
                     ray.dir = ptm::mk(dx, dy, dz);
                     ray.tnear = 0.0f;
                     rng.state = (uint64_t)hi << 32 | lo;
-                    rng.inc = (px.stream << 1u) | 1u;
-                    my_w = px.sample_index;
+                    rng.inc = bank_index_inc(inc_lo, inc_hi);
+                    my_w = w;
                     L = ptm::mk(0, 0, 0);
                     T = ptm::mk(1, 1, 1);
                     depth = 0;
@@ -131,22 +134,40 @@
                     const uint32_t oct = (inv.x < 0.0f ? 1u : 0u) | (inv.y < 0.0f ? 2u : 0u) | (inv.z < 0.0f ? 4u : 0u);
                     LdsF2 bx = (LdsF2)((LdsBytes)smem + lp.nodes_off + oct * box_pitch);
                     const ptm::V3 o = ray.org;
-                    // visit_node<false, true>: the same operations on the same operands (near.xy | near.z far.x | far.yz)
-                    auto box_hit = [&](const f2v p0, const f2v p1, const f2v p2) -> uint32_t {
+                    // visit_node<false, true>: the same operations on the same operands (near.xy | near.z far.x | far.yz);
+                    // the two sides of the compare that decides a group: tf >= max(0, tn)
+                    auto box_sides = [&](const f2v p0, const f2v p1, const f2v p2, float& tf, float& tn0) {
                         const float tn = ptm::fmax2(ptm::fmax2((p0.x - o.x) * inv.x, (p0.y - o.y) * inv.y), (p1.x - o.z) * inv.z);
-                        const float tf = ptm::fmin2(ptm::fmin2((p1.y - o.x) * inv.x, (p2.x - o.y) * inv.y), (p2.y - o.z) * inv.z);
-                        return tf >= ptm::fmax2(0.0f, tn) ? 1u : 0u;
+                        tf = ptm::fmin2(ptm::fmin2((p1.y - o.x) * inv.x, (p2.x - o.y) * inv.y), (p2.y - o.z) * inv.z);
+                        tn0 = ptm::fmax2(0.0f, tn);
                     };
+                    // h = 2 * h + hit as the compare and ONE add-with-carry, h + h + the compare's lane mask, where the compiler's
+                    // own choice is a select per group and a shift and an or per pair (2.5 per group on top of the compare).
+                    // gfx950 wants two wait states between a vector instruction that writes a lane mask and one that reads it,
+                    // and nothing inserts them inside an asm statement: a pair interleaves its two compares and adds and needs
+                    // one s_nop, the odd group alone waits two.
                     uint32_t h = 0;
                     // (the loop vectoriser would pair the groups up into packed fp32, which issues at half rate)
 #pragma clang loop vectorize(disable) interleave(disable) unroll(disable)
                     for (uint32_t k = n_groups >> 1; k != 0; k--) {
                         const f2v a0 = bx[0], a1 = bx[1], a2 = bx[2], b0 = bx[3], b1 = bx[4], b2 = bx[5];
                         bx += 6;
-                        h = 2u * h + box_hit(a0, a1, a2);
-                        h = 2u * h + box_hit(b0, b1, b2);
+                        float tfa, tna, tfb, tnb;
+                        box_sides(a0, a1, a2, tfa, tna);
+                        box_sides(b0, b1, b2, tfb, tnb);
+                        unsigned long long mb;
+                        asm("v_cmp_ge_f32_e32 vcc, %2, %3\n\t"
+                            "v_cmp_ge_f32_e64 %1, %4, %5\n\t"
+                            "s_nop 0\n\t"
+                            "v_addc_co_u32_e32 %0, vcc, %0, %0, vcc\n\t"
+                            "v_addc_co_u32_e64 %0, vcc, %0, %0, %1"
+                            : "+v"(h), "=&s"(mb) : "v"(tfa), "v"(tna), "v"(tfb), "v"(tnb) : "vcc");
                     }
-                    if (n_groups & 1u) h = 2u * h + box_hit(bx[0], bx[1], bx[2]);      // an odd count: the last group alone
+                    if (n_groups & 1u) {                                                // an odd count: the last group alone
+                        float tf, tn0;
+                        box_sides(bx[0], bx[1], bx[2], tf, tn0);
+                        asm("v_cmp_ge_f32_e32 vcc, %1, %2\n\ts_nop 1\n\tv_addc_co_u32_e32 %0, vcc, %0, %0, vcc" : "+v"(h) : "v"(tf), "v"(tn0) : "vcc");
+                    }
                     hits = sweep_hits_align(h, n_groups);
                 }
             }

@@ -29,12 +29,16 @@
     WorkFeed feed;
     feed_init(feed, rp);
     // path bank: slot `lane` of the wave's bank = direction of the primary ray and PCG state after the two jitter draws of
-    // work item bank_item(feed.cur, lane); everything else of a path start follows from the item number (path_index)
+    // work item bank_item(feed.cur, lane).  Where BANK_INDEX, also what start_path computed of the item's index, its slot in the
+    // scratch buffer and its PCG increment (BankIndex), so that the hand-out computes nothing; elsewhere the lane that takes
+    // a path works both out again from the item number (path_index)
     constexpr bool BANK = path_bank_on(RES, SPEC, NEE, LIST, THRESH, INNER);
     PathBank bank;
     bank_init(bank);
     float bank_dx = 0.0f, bank_dy = 0.0f, bank_dz = 0.0f;
     uint32_t bank_lo = 0, bank_hi = 0;
+    constexpr bool BANK_INDEX = BANK && bank_index_on(REG, STATS, MINW);
+    uint32_t bank_w = 0, bank_inc_lo = 0, bank_inc_hi = 0;     // BankIndex (pt_path_index.h), where BANK_INDEX
     bool alive = false;
     ptd::Ray ray;
     ray.org = ptm::mk(0, 0, 0); ray.dir = ptm::mk(0, 0, 1); ray.tnear = 0; ray.tfar = 0;
@@ -149,6 +153,10 @@
                         const PathStart ps = start_path<LIST>(rg, feed.region, bank_item(feed.cur, (uint32_t)lane));
                         bank_dx = ps.ray.dir.x; bank_dy = ps.ray.dir.y; bank_dz = ps.ray.dir.z;
                         bank_lo = (uint32_t)ps.rng.state; bank_hi = (uint32_t)(ps.rng.state >> 32);
+                        if constexpr (BANK_INDEX) {
+                            const BankIndex bi = bank_index_pack(ps.sample_index, ps.rng.inc);
+                            bank_w = bi.sample_index; bank_inc_lo = bi.inc_lo; bank_inc_hi = bi.inc_hi;
+                        }
                     }
                     uint32_t first;
                     const uint32_t k = bank_take(bank, (uint32_t)__popcll(want), first);
@@ -158,15 +166,24 @@
                     // the permutes run with every lane active (a switched-off lane gives a permute nothing to read)
                     const float dx = __shfl(bank_dx, src, 64), dy = __shfl(bank_dy, src, 64), dz = __shfl(bank_dz, src, 64);
                     const uint32_t lo = __shfl(bank_lo, src, 64), hi = __shfl(bank_hi, src, 64);
+                    uint32_t w = 0, inc_lo = 0, inc_hi = 0;
+                    if constexpr (BANK_INDEX) {
+                        w = __shfl(bank_w, src, 64); inc_lo = __shfl(bank_inc_lo, src, 64); inc_hi = __shfl(bank_inc_hi, src, 64);
+                    }
                     if (take) {
-                        const PathIndex px = path_index<LIST>(rp, feed.region, bank_item(feed.cur, first + rank));
                         ray.org = ptm::mk(rp.cam_origin[0], rp.cam_origin[1], rp.cam_origin[2]);
                         ray.dir = ptm::mk(dx, dy, dz);
                         ray.tnear = 0.0f;
                         ray.tfar = __builtin_inff();
                         rng.state = (uint64_t)hi << 32 | lo;
-                        rng.inc = (px.stream << 1u) | 1u;
-                        my_w = px.sample_index;
+                        if constexpr (BANK_INDEX) {
+                            rng.inc = bank_index_inc(inc_lo, inc_hi);
+                            my_w = w;
+                        } else {
+                            const PathIndex px = path_index<LIST>(rp, feed.region, bank_item(feed.cur, first + rank));
+                            rng.inc = stream_inc(px.stream);
+                            my_w = px.sample_index;
+                        }
                         L = ptm::mk(0, 0, 0);
                         T = ptm::mk(1, 1, 1);
                         depth = 0;

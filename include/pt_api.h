@@ -266,6 +266,31 @@ typedef struct pt_adaptive_params {
 int pt_render_adaptive(pt_scene* scene, const pt_render_params* p, const pt_adaptive_params* a,
                        float* fb, int32_t* spp_map, float* err_map, int on_device);
 
+/* An explicit list of pixels — an EXTENSION, like PT_RENDER_NEE: the reference renders whole frames.  Picking, a region of
+ * interest, sparse probes, and the re-trace pt_temporal_gradient_sparse reads.  DESIGN.md §22.
+ *   pixels[k] = j * width + i, the pixel index the PCG stream uses; out is [n, 3].  out[k] holds the bits pt_render writes to fb
+ *   for that pixel with the same parameters and every row selected — for any spp, seed, sample_offset, stream_stride, depths,
+ *   traversal, PT_RENDER_NEE and any option.  Order is free, duplicates are allowed, every entry is independent.
+ *   p->row_begin / row_end / row_stride must select every row (0, 0 or 0, height; 0 or 1): PT_ERR_INVALID_ARG otherwise.
+ *   on_device != 0: pixels and out are device pointers; the call is enqueued on hip_stream without a host sync, as
+ *   pt_render_async is, and what the caller observes is written in the order of that stream.  It is a plain frame (not an
+ *   adaptive round) and takes its turn in the "frames_in_flight" rotation of scratch memory, but always runs on the caller's
+ *   stream: its trace kernel reads the caller's list, which must stay valid until the stream has passed the call.  The library
+ *   cannot inspect such a list: out[k] of an entry outside [0, W * H) is unspecified and nothing else is affected — no address
+ *   is formed from an entry, only u, v and the PCG stream (out and the scratch memory are indexed by k).
+ *   on_device == 0: host pointers, blocking, on the default stream, staged through memory of the handle (grown on demand,
+ *   freed with the scene); an entry outside [0, W * H): PT_ERR_INVALID_ARG, pt_last_error() names pixels[k].
+ *   n < 0, n > 2^30, n > 0 with a NULL pixels or out: PT_ERR_INVALID_ARG, pt_last_error() names the argument; pt_render's own
+ *   parameter errors as in pt_render.  n == 0: PT_OK, nothing is written, the counters read zero.
+ *   The launch is a frame of n rows of width 1 run by the LIST instantiation of the trace kernel that the later rounds of
+ *   pt_render_adaptive run (info "trace_variant" has bit 11 set), and options mean what they mean there: "kernel" 1 is
+ *   honoured, 3 runs on 2; "v2_thresh" / "v2_inner" / "v2_minw" are ignored (the LIST kernels are compiled for the automatic
+ *   schedule of each residency only; no schedule changes a bit); "reg_stack", "leaf_sweep" and the path bank do not apply;
+ *   "scratch_bytes", "xcd_regions", "item_order", "chunk", "blocks_per_cu", "stats", "force_global", "fast_tree" and the rest
+ *   act on the n x 1 frame.  pt_get_counters covers the call (paths = n * spp). */
+int pt_render_pixels(pt_scene* scene, const pt_render_params* p, const int32_t* pixels, int32_t n, float* out, int on_device,
+                     void* hip_stream);
+
 /* Guide buffers of the first hit ("AOVs") — an EXTENSION, like PT_RENDER_NEE: the reference's only per-pixel output is radiance.
  * Never part of a parity or roofline number; no other entry point's output changes by a bit.
  *   One ray per selected pixel through the pixel CENTRE, u = ((float)i + 0.5f) / (float)width, v = ((float)j + 0.5f) / (float)height,
@@ -518,6 +543,33 @@ int pt_temporal_gradient(pt_scene* scene, const pt_gradient_params* g, const flo
 /* The same per-tile source (csrc/pt_gradient.h) compiled for the HOST: needs no GPU and no scene. */
 int pt_temporal_gradient_host(const pt_gradient_params* g, const float* prev_color, const float* resampled, float* lambda_out);
 
+/* The sparse variant: one re-traced PIXEL per tile in place of a row, 1 / s^2 of the previous frame's paths instead of 1 / s.
+ * DESIGN.md §22.  The grid — s, r0, TW, TH, tile t = ty * TW + tx — is pt_temporal_gradient's, so lambda_out [TH, TW] feeds
+ * pt_temporal_accumulate_adaptive as it is; field checks and their messages are pt_temporal_gradient's.
+ *   pt_gradient_pixels writes pixels_out [TH * TW]: the pixel of every tile at `seed` (callers pass the frame number, so that
+ *   the sampled pixel of a tile moves from frame to frame).  All arithmetic in uint32, wrapping:
+ *     v = t * 747796405 + (seed * 2891336453 + 1);  w = ((v >> ((v >> 28) + 4)) ^ v) * 277803737;  h = (w >> 22) ^ w;
+ *     ox = (h & 0xffff) % s, oy = (h >> 16) % s;  x = min(s tx + ox, W - 1), y = min(s ty + oy, H - 1);  pixels_out[t] = y * W + x.
+ *   Every tile of the grid has at least pixel (s tx, s ty) inside the frame.  on_device != 0: a device pointer, one kernel
+ *   enqueued on hip_stream without a host sync; on_device == 0: a host pointer, blocking.
+ *   resampled [TH * TW, 3] is what pt_render_pixels writes for the previous frame's parameters and this list on the current
+ *   scene; prev_color [H, W, 3] as in pt_temporal_gradient.
+ *   Reduce, tile t: e = pixels[t]; a_c = prev_color[3 e + c], b_c = resampled[3 t + c]; d_c = b_c - a_c, m_c = a_c < b_c ? b_c : a_c;
+ *     x_0 = (d_r, d_g, d_b, m_r, m_g, m_b).  An entry outside [0, W * H) forms no address and that tile takes a = b (in both
+ *     call forms and in the host twin).
+ *   Filter and Final: pt_temporal_gradient's, unchanged; 1 + iterations kernels on the same ping-pong buffers of the handle.
+ *   Call forms, staging and errors as in pt_temporal_gradient; pt_last_error() names pixels_out, prev_color, pixels, resampled
+ *   or lambda_out.
+ *   A property callers may rely on: prev_color equal to resampled at every listed pixel gives lambda == +0 (the bits) at every
+ *   tile. */
+int pt_gradient_pixels(pt_scene* scene, const pt_gradient_params* g, uint32_t seed, int32_t* pixels_out, int on_device, void* hip_stream);
+int pt_temporal_gradient_sparse(pt_scene* scene, const pt_gradient_params* g, const float* prev_color, const int32_t* pixels,
+                                const float* resampled, float* lambda_out, int on_device, void* hip_stream);
+/* The same per-tile source (csrc/pt_gradient.h) compiled for the HOST: need no GPU and no scene. */
+int pt_gradient_pixels_host(const pt_gradient_params* g, uint32_t seed, int32_t* pixels_out);
+int pt_temporal_gradient_sparse_host(const pt_gradient_params* g, const float* prev_color, const int32_t* pixels,
+                                     const float* resampled, float* lambda_out);
+
 /* pt_temporal_accumulate_moments with pt_temporal_gradient's map.  Buffers, call forms, aliases, staging and errors are
  * pt_temporal_accumulate_moments'.  lambda [TH, TW] and stride (0 -> 3; else 1..16) are the map and the stride of the
  * pt_temporal_gradient call for the same frame size; lambda == NULL, a stride out of range, H <= r0: PT_ERR_INVALID_ARG,
@@ -638,7 +690,7 @@ int pt_bvh_build_sweep_device(const pt_scene_desc* desc, pt_bvh_node* out_nodes,
  * "fast_tree_cost_permille" (probe-ray node visits, internal / caller's x 1000; 0 = none built), "stack_entries" (per lane),
  * "prev_geometry", "redo_segments" (with "stats": segments of the last frame traced on the caller's tree), "debug_reruns" (same for pt_debug_intersect),
  * "kernel" / "block_threads" (what the last render ran on), "trace_variant" (the template arguments of the trace kernel that call
- * launched last — for pt_render_adaptive the LIST kernel of its last round; 0 = none launched — packed into one value:
+ * launched last — for pt_render_adaptive the LIST kernel of its last round, for pt_render_pixels a LIST kernel; 0 = none launched — packed into one value:
  *     bits  0-3  family: 1 trace_kernel, 2 trace_kernel_v2, 3 trace_kernel_q      bit  10  NEE
  *     bits  4-5  RES (family 1: LDS_SCENE)                                      bit  11  LIST
  *     bit   6    PRUNE       bit 7  STATS       bits 8-9  SPEC                    bit  12  POSTPONE

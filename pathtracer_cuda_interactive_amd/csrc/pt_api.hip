@@ -10,10 +10,12 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <limits>
 #include <mutex>
 #include <queue>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/pt_api.h"
@@ -211,6 +213,8 @@ struct pt_scene {
     // grown when a larger frame arrives, and staging of a call that comes in host memory
     DevBuf<float4> gr_x[2];
     DevBuf<float> gr_host;
+    // pt_render_pixels: staging of a list that comes in host memory (the colours go back through fb_tmp)
+    DevBuf<int32_t> px_list;
     // What a frame's trace kernel writes lives in a frame slot; render call k uses slot k % frames_in_flight.  With more than one
     // slot a single-pass frame runs on the slot's own stream: the trace kernel at once (it reads the immutable scene and writes
     // the slot only), the resolve — the one step that touches the caller's buffer — once the caller's stream has reached the
@@ -1234,17 +1238,26 @@ int select_rows(const pt_render_params* p, RowSel* out) {
 
 // One round of pt_render_adaptive.  Round 0 opens a frame like any render call (slot, counters, timing record) and traces every
 // selected pixel; later rounds continue that frame — same slot, counters and timing record — and trace only the pixels of
-// args.list_in.  The resolve of every pass is adaptive_resolve_kernel.  Adaptive frames run on the caller's stream.
+// args.list_in (handed to launch_render as its pixel list).  The resolve of every pass is adaptive_resolve_kernel.  Adaptive
+// frames run on the caller's stream.
 struct AdaptiveRound {
     int round;
-    uint32_t n_list;                 // rounds > 0: entries of args.list_in
     AdaptiveArgs args;               // n, spp_pass, first and check are set per pass by launch_render
 };
 
-// mode: 0 = pt_render (fb = mean), 2 = pt_render_accumulate (accum (+)= sum); ad: a round of pt_render_adaptive (mode 0)
+// A pixel list (RenderDev::list): the launch is a frame of n rows of width 1 whose row k is the pixel list[k], a packed id
+// (selected row * image width + column; under "all rows" the pixel index).  Device memory, read by the trace kernel.  The
+// later rounds of pt_render_adaptive and pt_render_pixels.
+struct PixelList {
+    const uint32_t* list;
+    uint32_t n;
+};
+
+// mode: 0 = pt_render (fb = mean), 2 = pt_render_accumulate (accum (+)= sum); ad: a round of pt_render_adaptive (mode 0);
+// pl: the pixels to trace in place of the selected rows (out_dev is then [n, 3]; n == 0: an empty frame, out_dev may be null)
 int launch_render(pt_scene* S, const pt_render_params* p, float* out_dev, int mode, hipStream_t stream,
-                  const AdaptiveRound* ad = nullptr) {
-    if (!S || !p || !out_dev) return fail(PT_ERR_INVALID_ARG, "null argument");
+                  const AdaptiveRound* ad = nullptr, const PixelList* pl = nullptr) {
+    if (!S || !p || (!out_dev && !(pl && pl->n == 0))) return fail(PT_ERR_INVALID_ARG, "null argument");
     if (p->width <= 0 || p->height <= 0 || p->spp <= 0) return fail(PT_ERR_INVALID_ARG, "width, height and spp must be positive");
     if (p->sample_offset < 0 || p->stream_stride < 0) return fail(PT_ERR_INVALID_ARG, "negative sample_offset / stream_stride");
     // PCG stream = pixel_index*stride + sample_offset + s: samples [sample_offset, sample_offset + spp) must stay below the
@@ -1288,7 +1301,7 @@ int launch_render(pt_scene* S, const pt_render_params* p, float* out_dev, int mo
     }
     pt_scene::FrameRec& frec = S->frames[(S->frame_seq - 1) % S->frames.size()];
     const size_t pass_base = frec.passes;               // passes of earlier adaptive rounds of this frame
-    if (rows.count == 0) {           // nothing to trace: the frame's counters read zero
+    if (rows.count == 0 || (pl && pl->n == 0)) {           // nothing to trace: the frame's counters read zero
         S->info_trace_variant = 0;
         S->info_path_bank = 0;
         S->info_reg_stack = 0;
@@ -1300,9 +1313,9 @@ int launch_render(pt_scene* S, const pt_render_params* p, float* out_dev, int mo
         return PT_OK;
     }
 
-    // a listed adaptive round is a frame of n_list rows of width 1 (RenderDev::list)
-    const bool listed = ad && ad->args.list_in;
-    const int vrows = listed ? (int)ad->n_list : rows.count, vwidth = listed ? 1 : p->width;
+    // a pixel list is a frame of n rows of width 1 (RenderDev::list)
+    const bool listed = pl != nullptr;
+    const int vrows = listed ? (int)pl->n : rows.count, vwidth = listed ? 1 : p->width;
     const uint64_t npix = (uint64_t)vrows * (uint64_t)vwidth;
     if (npix > (1ull << 30)) return fail(PT_ERR_INVALID_ARG, "more than 2^30 pixels per call");
     // samples per pass: bounded by the scratch budget and by 2^30 work items per launch
@@ -1390,7 +1403,8 @@ int launch_render(pt_scene* S, const pt_render_params* p, float* out_dev, int mo
     // With three slots a frame takes half of each CU — two frames are resident side by side, half a frame apart, the third
     // enters where the first leaves — with two slots all but one block per CU (cbox 2.55 ms per frame with full grids,
     // 2.50 with 5 + 1 of 6, 2.49 with 3 + 3 and three slots; bunny 4.64 / 4.53 / 4.39; profiles/r03_frames_in_flight.log).
-    const bool own_stream = !ad && in_flight > 1 && n_pass == 1 && prev_busy;
+    // (a pixel list stays on the caller's stream: its trace kernel reads the caller's memory)
+    const bool own_stream = !ad && !listed && in_flight > 1 && n_pass == 1 && prev_busy;
     if (own_stream && S->opt_blocks_per_cu <= 0) bpc = std::max(1, in_flight >= 3 ? bpc / 2 : bpc - 1);
     S->info_kernel = use_q ? 3 : S->opt_kernel == 1 ? 1 : 2;
     S->info_trace_variant = variant;
@@ -1447,7 +1461,7 @@ int launch_render(pt_scene* S, const pt_render_params* p, float* out_dev, int mo
         std::memcpy(rd.cam_vertical, p->cam_vertical, 12);
         rd.width = vwidth; rd.height = p->height;
         rd.row_begin = rows.begin; rd.row_step = rows.step; rd.num_rows = vrows;
-        rd.list = listed ? ad->args.list_in : nullptr;
+        rd.list = listed ? pl->list : nullptr;
         rd.img_width = p->width;
         rd.div_img_width = make_fastdiv((uint32_t)p->width);
         rd.spp_pass = sn;
@@ -1930,6 +1944,63 @@ int gradient_args(const char* fn, const pt_gradient_params* g, const float* prev
     return PT_OK;
 }
 
+// Arguments of the sparse variant's four entry points: the struct, then the pointers in the order of the parameter list.
+int sparse_args(const char* fn, const pt_gradient_params* g, std::initializer_list<std::pair<const char*, const void*>> ptrs, ptg::Resolved* r) {
+    const std::string pre = std::string(fn) + ": ";
+    if (!g) return fail(PT_ERR_INVALID_ARG, pre + "null pt_gradient_params");
+    for (const auto& q : ptrs)
+        if (!q.second) return fail(PT_ERR_INVALID_ARG, pre + "null " + q.first);
+    if (const char* bad = ptg::resolve(g, r)) return fail(PT_ERR_INVALID_ARG, std::string("pt_gradient_params.") + bad + " out of range");
+    return PT_OK;
+}
+
+// pt_gradient_pixels behind its argument checks: one kernel; a list that goes to host memory is made in the handle's staging
+// buffer on the default stream and copied out.
+int gradient_pixels_call(pt_scene* S, const ptg::Resolved& r, uint32_t seed, int32_t* pixels_out, int on_device, void* hip_stream) {
+    const char* fn = "pt_gradient_pixels";
+    DeviceGuard guard;
+    { int grc = guard.enter(S->device); if (grc) return grc; }
+    const size_t ntiles = (size_t)r.tw * (size_t)r.th;
+    int rc;
+    int32_t* d_out = pixels_out;
+    if (!on_device) {
+        if ((rc = S->px_list.ensure(ntiles))) return rc;
+        d_out = S->px_list.p;
+    }
+    const hipError_t e = (hipError_t)ptg::pixels_device(r, seed, d_out, on_device ? hip_stream : nullptr);
+    if (e != hipSuccess) return fail(PT_ERR_DEVICE, std::string(fn) + ": " + hipGetErrorString(e));
+    if (!on_device) HIP_TRY(hipMemcpy(pixels_out, d_out, ntiles * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return PT_OK;
+}
+
+// pt_temporal_gradient_sparse behind its argument checks, as gradient_call: the staging buffer of a call in host memory holds
+// the frame, the re-traced pixels, the list (4 bytes per entry, like a float) and the map.
+int gradient_sparse_call(pt_scene* S, const ptg::Resolved& r, const float* prev_color, const int32_t* pixels, const float* resampled,
+                         float* lambda_out, int on_device, void* hip_stream) {
+    const char* fn = "pt_temporal_gradient_sparse";
+    DeviceGuard guard;
+    { int grc = guard.enter(S->device); if (grc) return grc; }
+    const size_t ntiles = (size_t)r.tw * (size_t)r.th;
+    int rc;
+    if ((rc = S->gr_x[0].ensure(2 * ntiles)) || (rc = S->gr_x[1].ensure(2 * ntiles))) return rc;
+    auto launch = [&](const float* a, const int32_t* px, const float* b, float* out, void* stream) {
+        const hipError_t e = (hipError_t)ptg::run_device_sparse(r, a, px, b, out, S->gr_x[0].p, S->gr_x[1].p, stream);
+        return e != hipSuccess ? fail(PT_ERR_DEVICE, std::string(fn) + ": " + hipGetErrorString(e)) : PT_OK;
+    };
+    if (on_device) return launch(prev_color, pixels, resampled, lambda_out, hip_stream);
+    static_assert(sizeof(int32_t) == sizeof(float), "the list rides in the float staging buffer");
+    const size_t n_prev = (size_t)r.width * (size_t)r.height * 3, n_res = ntiles * 3;
+    if ((rc = S->gr_host.ensure(n_prev + n_res + 2 * ntiles))) return rc;
+    float *d_prev = S->gr_host.p, *d_res = d_prev + n_prev, *d_lam = d_res + n_res;
+    int32_t* d_px = reinterpret_cast<int32_t*>(d_lam + ntiles);
+    HIP_TRY(hipMemcpy(d_prev, prev_color, n_prev * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_res, resampled, n_res * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_px, pixels, ntiles * sizeof(int32_t), hipMemcpyHostToDevice));
+    if ((rc = launch(d_prev, d_px, d_res, d_lam, nullptr))) return rc;
+    HIP_TRY(hipMemcpy(lambda_out, d_lam, ntiles * sizeof(float), hipMemcpyDeviceToHost));
+    return PT_OK;
+}
+
 // pt_denoise and pt_denoise_variance behind their argument checks: the record buffers, then the kernels.  The frame is
 // written over the colour plane of a staged call.
 int denoise_call(const char* fn, pt_scene* S, const ptdn::Resolved& r, ptdn::Frames f, DevBuf<float4>& guide, DevBuf<float4> (&x)[2],
@@ -1997,7 +2068,7 @@ int pt_scene_destroy(pt_scene* S) {
     S->ad_spp_tmp.release(); S->ad_err_tmp.release();
     S->dn_guide.release(); S->dn_x[0].release(); S->dn_x[1].release(); S->dn_host.release(); S->tp_host.release();
     S->vd_guide.release(); S->vd_x[0].release(); S->vd_x[1].release(); S->vd_host.release();
-    S->gr_x[0].release(); S->gr_x[1].release(); S->gr_host.release();
+    S->gr_x[0].release(); S->gr_x[1].release(); S->gr_host.release(); S->px_list.release();
     S->st_prims.release(); S->prev_prims.release(); S->st_normals.release(); S->st_boxes.release(); S->st_status.release();
     for (auto& pl : S->refit_plan) ptf::plan_release(&pl);
     S->drop_events();
@@ -2041,6 +2112,37 @@ int pt_render(pt_scene* S, const pt_render_params* p, float* fb, int fb_on_devic
     if (rc) return rc;
     HIP_TRY(hipMemcpy(fb, S->fb_tmp.p, n * sizeof(float), hipMemcpyDeviceToHost));
     return check_schedule_error(S);
+}
+
+int pt_render_pixels(pt_scene* S, const pt_render_params* p, const int32_t* pixels, int32_t n, float* out, int on_device,
+                     void* hip_stream) {
+    const std::string pre = "pt_render_pixels: ";
+    if (!S) return fail(PT_ERR_INVALID_ARG, pre + "null scene");
+    if (!p) return fail(PT_ERR_INVALID_ARG, pre + "null p");
+    if (n < 0) return fail(PT_ERR_INVALID_ARG, pre + "n is negative");
+    if (n > (1 << 30)) return fail(PT_ERR_INVALID_ARG, pre + "n above 2^30");
+    if (n > 0 && !pixels) return fail(PT_ERR_INVALID_ARG, pre + "null pixels");
+    if (n > 0 && !out) return fail(PT_ERR_INVALID_ARG, pre + "null out");
+    if (p->row_begin != 0 || (p->row_end != 0 && p->row_end != p->height) || (p->row_stride != 0 && p->row_stride != 1))
+        return fail(PT_ERR_INVALID_ARG, pre + "row_begin / row_end / row_stride must select every row: the list names the pixels");
+    if (on_device || n == 0) {
+        const PixelList pl{reinterpret_cast<const uint32_t*>(pixels), (uint32_t)n};
+        return launch_render(S, p, out, 0, reinterpret_cast<hipStream_t>(hip_stream), nullptr, &pl);
+    }
+    if (p->width <= 0 || p->height <= 0 || p->spp <= 0) return fail(PT_ERR_INVALID_ARG, "width, height and spp must be positive");
+    const int64_t frame = (int64_t)p->width * (int64_t)p->height;
+    for (int32_t k = 0; k < n; k++)
+        if (pixels[k] < 0 || (int64_t)pixels[k] >= frame)
+            return fail(PT_ERR_INVALID_ARG, pre + "pixels[" + std::to_string(k) + "] = " + std::to_string(pixels[k]) + " is outside the frame");
+    DeviceGuard guard;
+    { int grc = guard.enter(S->device); if (grc) return grc; }
+    int rc;
+    if ((rc = S->px_list.ensure((size_t)n)) || (rc = S->fb_tmp.ensure((size_t)n * 3))) return rc;
+    HIP_TRY(hipMemcpy(S->px_list.p, pixels, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice));
+    const PixelList pl{reinterpret_cast<const uint32_t*>(S->px_list.p), (uint32_t)n};
+    if ((rc = launch_render(S, p, S->fb_tmp.p, 0, nullptr, nullptr, &pl))) return rc;
+    HIP_TRY(hipMemcpy(out, S->fb_tmp.p, (size_t)n * 3 * sizeof(float), hipMemcpyDeviceToHost));
+    return PT_OK;
 }
 
 int pt_render_adaptive(pt_scene* S, const pt_render_params* p, const pt_adaptive_params* a, float* fb, int32_t* spp_map,
@@ -2115,12 +2217,12 @@ int pt_render_adaptive(pt_scene* S, const pt_render_params* p, const pt_adaptive
         pr.spp = spp_r;
         pr.sample_offset = n;
         ar.round = round;
-        ar.n_list = n_list;
         ar.args.list_in = round == 0 ? nullptr : S->ad_list[(round - 1) & 1].p;
         ar.args.list_out = S->ad_list[round & 1].p;
         ar.args.n_total = n + spp_r;
         HIP_TRY(hipMemsetAsync(S->ad_count.p, 0, sizeof(uint32_t), nullptr));
-        if ((rc = launch_render(S, &pr, fb_d, 0, nullptr, &ar))) return rc;
+        const PixelList pl{ar.args.list_in, n_list};
+        if ((rc = launch_render(S, &pr, fb_d, 0, nullptr, &ar, round == 0 ? nullptr : &pl))) return rc;
         n += spp_r;
         S->info_adaptive_rounds = round + 1;
         HIP_TRY(hipMemcpy(&n_list, S->ad_count.p, sizeof(uint32_t), hipMemcpyDeviceToHost));   // the one read-back per round
@@ -2204,6 +2306,46 @@ int pt_temporal_gradient_host(const pt_gradient_params* g, const float* prev_col
         ptg::run_host(r, prev_color, resampled, lambda_out);
     } catch (const std::exception& e) {
         return fail(PT_ERR_DEVICE, std::string("pt_temporal_gradient_host: ") + e.what());
+    }
+    return PT_OK;
+}
+
+int pt_gradient_pixels(pt_scene* S, const pt_gradient_params* g, uint32_t seed, int32_t* pixels_out, int on_device, void* hip_stream) {
+    if (!S) return fail(PT_ERR_INVALID_ARG, "pt_gradient_pixels: null scene");
+    ptg::Resolved r;
+    int rc = sparse_args("pt_gradient_pixels", g, {{"pixels_out", pixels_out}}, &r);
+    if (rc) return rc;
+    return gradient_pixels_call(S, r, seed, pixels_out, on_device, hip_stream);
+}
+
+int pt_gradient_pixels_host(const pt_gradient_params* g, uint32_t seed, int32_t* pixels_out) {
+    ptg::Resolved r;
+    int rc = sparse_args("pt_gradient_pixels_host", g, {{"pixels_out", pixels_out}}, &r);
+    if (rc) return rc;
+    ptg::pixels_host(r, seed, pixels_out);
+    return PT_OK;
+}
+
+int pt_temporal_gradient_sparse(pt_scene* S, const pt_gradient_params* g, const float* prev_color, const int32_t* pixels,
+                                const float* resampled, float* lambda_out, int on_device, void* hip_stream) {
+    if (!S) return fail(PT_ERR_INVALID_ARG, "pt_temporal_gradient_sparse: null scene");
+    ptg::Resolved r;
+    int rc = sparse_args("pt_temporal_gradient_sparse", g,
+                         {{"prev_color", prev_color}, {"pixels", pixels}, {"resampled", resampled}, {"lambda_out", lambda_out}}, &r);
+    if (rc) return rc;
+    return gradient_sparse_call(S, r, prev_color, pixels, resampled, lambda_out, on_device, hip_stream);
+}
+
+int pt_temporal_gradient_sparse_host(const pt_gradient_params* g, const float* prev_color, const int32_t* pixels, const float* resampled,
+                                     float* lambda_out) {
+    ptg::Resolved r;
+    int rc = sparse_args("pt_temporal_gradient_sparse_host", g,
+                         {{"prev_color", prev_color}, {"pixels", pixels}, {"resampled", resampled}, {"lambda_out", lambda_out}}, &r);
+    if (rc) return rc;
+    try {
+        ptg::run_host_sparse(r, prev_color, pixels, resampled, lambda_out);
+    } catch (const std::exception& e) {
+        return fail(PT_ERR_DEVICE, std::string("pt_temporal_gradient_sparse_host: ") + e.what());
     }
     return PT_OK;
 }

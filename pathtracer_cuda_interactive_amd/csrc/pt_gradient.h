@@ -8,6 +8,9 @@
 // host twin and a numpy restatement give the same bits.
 //
 // Layout: one 32-B record per tile, (d.r, d.g, d.b, -, m.r, m.g, m.b, -), ping-ponged between the iterations.
+//
+// The sparse variant (pt_gradient_pixels, pt_temporal_gradient_sparse) re-traces one pixel per tile in place of a
+// row: tile_pixel chooses it, in wrapping uint32 arithmetic, reduce_sparse makes x_0 from it, and filter / lambda_of are shared.
 #pragma once
 
 #include <stdint.h>
@@ -70,6 +73,33 @@ PT_HD Tile reduce(const Resolved& r, const float* __restrict__ prev_color, const
     return Tile{br - ar, bg - ag, bb - ab, 0.0f, ar < br ? br : ar, ag < bg ? bg : ag, ab < bb ? bb : ab, 0.0f};
 }
 
+// The pixel of tile t = ty * tw + tx at `seed`: one PCG output step of the tile number on the seed's stream gives an offset in
+// the tile, clamped to the frame.  All of it wrapping uint32 arithmetic; the pixel index fits (width * height <= 2^30).
+PT_HD uint32_t tile_hash(uint32_t t, uint32_t seed) {
+    const uint32_t v = t * 747796405u + (seed * 2891336453u + 1u);
+    const uint32_t w = ((v >> ((v >> 28) + 4u)) ^ v) * 277803737u;
+    return (w >> 22) ^ w;
+}
+PT_HD int32_t tile_pixel(const Resolved& r, uint32_t seed, int tx, int ty) {
+    const uint32_t h = tile_hash((uint32_t)ty * (uint32_t)r.tw + (uint32_t)tx, seed);
+    const int ox = (int)((h & 0xffffu) % (uint32_t)r.stride), oy = (int)((h >> 16) % (uint32_t)r.stride);
+    const int x = r.stride * tx + ox < r.width - 1 ? r.stride * tx + ox : r.width - 1;
+    const int y = r.stride * ty + oy < r.height - 1 ? r.stride * ty + oy : r.height - 1;
+    return y * r.width + x;
+}
+
+// x_0 of tile (tx, ty) from its one listed pixel: prev_color at the entry against the tile's re-traced value.  An entry outside
+// the frame forms no address; the tile then compares the re-traced value with itself.
+PT_HD Tile reduce_sparse(const Resolved& r, const float* __restrict__ prev_color, const int32_t* __restrict__ pixels,
+                         const float* __restrict__ resampled, int tx, int ty) {
+    const size_t t = (size_t)ty * (size_t)r.tw + (size_t)tx;
+    const int32_t e = pixels[t];
+    const float* b = resampled + 3 * t;
+    const float* a = e >= 0 && e < r.width * r.height ? prev_color + 3 * (size_t)e : b;
+    const float ar = a[0], ag = a[1], ab = a[2], br = b[0], bg = b[1], bb = b[2];
+    return Tile{br - ar, bg - ag, bb - ab, 0.0f, ar < br ? br : ar, ag < bg ? bg : ag, ab < bb ? bb : ab, 0.0f};
+}
+
 // One iteration at tile (tx, ty): 25 taps at `spacing` on the tile grid, a tap outside the grid skipped before its address is formed
 PT_HD Tile filter(const Tile* __restrict__ x, int tx, int ty, int tw, int th, int spacing) {
     const float h[5] = {1.0f / 16.0f, 1.0f / 4.0f, 3.0f / 8.0f, 1.0f / 4.0f, 1.0f / 16.0f};
@@ -104,13 +134,16 @@ PT_HD float lambda_of(const Tile& t, float gain, float norm_floor) {
 // Device side (pt_gradient.hip).  xa / xb: tw * th records each, device memory owned by the caller (the scene handle); the
 // three frames: device pointers.  Enqueues 1 + iterations kernels on `stream`, no host sync.  Returns a hipError_t.
 int run_device(const Resolved& r, const float* prev_color, const float* resampled, float* lambda_out, void* xa, void* xb, void* hip_stream);
+// The sparse variant: pixels [th * tw] and resampled [th * tw, 3] in place of the rows.  The same number of kernels.
+int run_device_sparse(const Resolved& r, const float* prev_color, const int32_t* pixels, const float* resampled, float* lambda_out, void* xa,
+                      void* xb, void* hip_stream);
+// pixels_out [th * tw] = tile_pixel of every tile: one kernel on `stream`, no host sync.  Returns a hipError_t.
+int pixels_device(const Resolved& r, uint32_t seed, int32_t* pixels_out, void* hip_stream);
 
-// Host twin: the same functions over the tile grid, pass by pass.
-inline void run_host(const Resolved& r, const float* prev_color, const float* resampled, float* lambda_out) {
+// Host twins: the same functions over the tile grid, pass by pass.  filter_host: the iterations and the final step on x_0 = xa.
+inline void filter_host(const Resolved& r, std::vector<Tile>& xa, float* lambda_out) {
     const size_t ntiles = (size_t)r.tw * (size_t)r.th;
-    std::vector<Tile> xa(ntiles), xb(ntiles);
-    for (int ty = 0; ty < r.th; ty++)
-        for (int tx = 0; tx < r.tw; tx++) xa[(size_t)ty * r.tw + tx] = reduce(r, prev_color, resampled, tx, ty);
+    std::vector<Tile> xb(ntiles);
     Tile* xs[2] = {xa.data(), xb.data()};
     for (int k = 0; k < r.iterations; k++) {
         const Tile* src = xs[k & 1];
@@ -120,6 +153,22 @@ inline void run_host(const Resolved& r, const float* prev_color, const float* re
     }
     const Tile* last = xs[r.iterations & 1];
     for (size_t t = 0; t < ntiles; t++) lambda_out[t] = lambda_of(last[t], r.gain, r.norm_floor);
+}
+inline void run_host(const Resolved& r, const float* prev_color, const float* resampled, float* lambda_out) {
+    std::vector<Tile> xa((size_t)r.tw * (size_t)r.th);
+    for (int ty = 0; ty < r.th; ty++)
+        for (int tx = 0; tx < r.tw; tx++) xa[(size_t)ty * r.tw + tx] = reduce(r, prev_color, resampled, tx, ty);
+    filter_host(r, xa, lambda_out);
+}
+inline void run_host_sparse(const Resolved& r, const float* prev_color, const int32_t* pixels, const float* resampled, float* lambda_out) {
+    std::vector<Tile> xa((size_t)r.tw * (size_t)r.th);
+    for (int ty = 0; ty < r.th; ty++)
+        for (int tx = 0; tx < r.tw; tx++) xa[(size_t)ty * r.tw + tx] = reduce_sparse(r, prev_color, pixels, resampled, tx, ty);
+    filter_host(r, xa, lambda_out);
+}
+inline void pixels_host(const Resolved& r, uint32_t seed, int32_t* pixels_out) {
+    for (int ty = 0; ty < r.th; ty++)
+        for (int tx = 0; tx < r.tw; tx++) pixels_out[(size_t)ty * r.tw + tx] = tile_pixel(r, seed, tx, ty);
 }
 
 }  // namespace ptg

@@ -126,8 +126,8 @@ struct RenderDev {
     int32_t short_region;           // index of the band with fewer than rows_per_region rows, or -1
     FastDiv div_spp;                // / spp_pass
     int32_t row_major;              // work item order inside a band: 0 = sample, row, column   1 = row, sample, column
-    // Adaptive rounds after the first (pt_render_adaptive): `list` holds the packed pixel ids (local row * img_width + column)
-    // still to be sampled, and the launch sees it as a frame of num_rows = list length rows of width 1, so that bands,
+    // A pixel list (adaptive rounds after the first, pt_render_pixels): `list` holds the packed pixel ids (local row * img_width
+    // + column) to be sampled, and the launch sees it as a frame of num_rows = list length rows of width 1, so that bands,
     // chunking and item order work unchanged.  u and the PCG stream use the image's width, img_width.  Read only by the LIST
     // variants of the trace kernels (start_path<true>); plain frames leave list null and img_width == width.
     const uint32_t* list;

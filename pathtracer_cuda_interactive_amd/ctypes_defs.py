@@ -135,6 +135,17 @@ class PtGradientParams(C.Structure):
                 ("gain", C.c_float), ("norm_floor", C.c_float)]
 
 
+# Parameter lists of pt_render_pixels and the sparse gradient's entry points (pt_api.h), which device.lib() installs.
+SPARSE_ARGTYPES = {
+    "pt_render_pixels": [C.c_void_p, C.POINTER(PtRenderParams), C.c_void_p, C.c_int32, C.c_void_p, C.c_int, C.c_void_p],
+    "pt_gradient_pixels": [C.c_void_p, C.POINTER(PtGradientParams), C.c_uint32, C.c_void_p, C.c_int, C.c_void_p],
+    "pt_gradient_pixels_host": [C.POINTER(PtGradientParams), C.c_uint32, C.c_void_p],
+    "pt_temporal_gradient_sparse": [C.c_void_p, C.POINTER(PtGradientParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                    C.c_void_p],
+    "pt_temporal_gradient_sparse_host": [C.POINTER(PtGradientParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+}
+
+
 class PtCamera(C.Structure):
     _fields_ = [("lookfrom", c_float3), ("lookat", c_float3), ("up", c_float3), ("vfov", C.c_float),
                 ("width", C.c_int32), ("height", C.c_int32), ("spp", C.c_int32)]

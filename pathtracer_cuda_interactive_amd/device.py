@@ -10,7 +10,7 @@ import numpy as np
 
 from . import _build
 from .ctypes_defs import (PT_MOTION_GEOMETRY_CURRENT, PT_MOTION_GEOMETRY_PREVIOUS, PT_OK, PT_SHAPE_SPHERE, PT_TRAVERSAL_DEFAULT,
-                          PT_UPDATE_GEOMETRY, PT_UPDATE_SHADING, PtAdaptiveParams, PtBvhNode, PtCounters, PtDenoiseParams, PtError,
+                          PT_UPDATE_GEOMETRY, PT_UPDATE_SHADING, SPARSE_ARGTYPES, PtAdaptiveParams, PtBvhNode, PtCounters, PtDenoiseParams, PtError,
                           PtGradientParams, PtGuideBuffers, PtLight, PtMaterial, PtMesh, PtMotionParams, PtRenderParams, PtSceneDesc, PtShape,
                           PtTemporalIo, PtTemporalParams, PtVdenoiseParams)
 from .host import NODE_DTYPE  # noqa: F401  (one definition; callers also read it from here)
@@ -25,6 +25,7 @@ EXPORTS = [
     "pt_render_guides", "pt_temporal_accumulate", "pt_temporal_accumulate_host",
     "pt_temporal_accumulate_moments", "pt_temporal_accumulate_moments_host", "pt_denoise_variance", "pt_denoise_variance_host",
     "pt_temporal_gradient", "pt_temporal_gradient_host", "pt_temporal_accumulate_adaptive", "pt_temporal_accumulate_adaptive_host",
+    "pt_render_pixels", "pt_gradient_pixels", "pt_gradient_pixels_host", "pt_temporal_gradient_sparse", "pt_temporal_gradient_sparse_host",
 ]
 
 
@@ -59,6 +60,8 @@ def lib():
         L.pt_denoise_variance_host.argtypes = [C.POINTER(PtVdenoiseParams)] + [vp] * 8
         L.pt_temporal_gradient.argtypes = [vp, C.POINTER(PtGradientParams), vp, vp, vp, C.c_int, vp]
         L.pt_temporal_gradient_host.argtypes = [C.POINTER(PtGradientParams), vp, vp, vp]
+        for name, argtypes in SPARSE_ARGTYPES.items():
+            getattr(L, name).argtypes = argtypes
         L.pt_temporal_accumulate_adaptive.argtypes = [vp, C.POINTER(PtTemporalParams), C.c_float, C.POINTER(PtTemporalIo), vp, C.c_int32,
                                                       C.c_int, vp]
         L.pt_temporal_accumulate_adaptive_host.argtypes = [C.POINTER(PtTemporalParams), C.c_float, C.POINTER(PtTemporalIo), vp, C.c_int32]
@@ -289,6 +292,55 @@ class DeviceScene:
         _check(lib().pt_temporal_gradient(self._h, C.byref(g), C.c_void_p(prev_color_ptr), C.c_void_p(resampled_ptr),
                                           C.c_void_p(lambda_ptr), 1, C.c_void_p(stream or 0)))
 
+    def render_pixels(self, params, pixels, traversal=None):
+        """pt_render_pixels on a host list of pixel indices (j * width + i, any order, duplicates allowed): their colours as a new
+        [n, 3] float32 array, each the bits a full render(params) gives that pixel.  Blocking."""
+        p = params.copy()
+        if traversal is not None:
+            p.traversal = traversal
+        pixels = np.ascontiguousarray(pixels, dtype=np.int32).reshape(-1)
+        out = np.empty((pixels.size, 3), dtype=np.float32)
+        _check(lib().pt_render_pixels(self._h, C.byref(p), *_ptrs([pixels]), pixels.size, *_ptrs([out]), 0, None))
+        return out
+
+    def render_pixels_into(self, params, pixels_ptr, n, out_ptr, stream=None, traversal=None):
+        """pt_render_pixels on device memory (pixels_ptr: n int32, out_ptr: [n, 3] float32), enqueued on a HIP stream without a
+        host sync.  The list must stay valid until the stream has passed the call."""
+        p = params.copy()
+        if traversal is not None:
+            p.traversal = traversal
+        _check(lib().pt_render_pixels(self._h, C.byref(p), C.c_void_p(pixels_ptr or 0), int(n), C.c_void_p(out_ptr or 0), 1,
+                                      C.c_void_p(stream or 0)))
+
+    def gradient_pixels(self, width, height, seed, **kw):
+        """pt_gradient_pixels through the handle's staging memory: the list [TH * TW] int32 as a new host array (the bits of
+        gradient_pixels_host).  Keywords: the fields of pt_gradient_params."""
+        g = gradient_params(width, height, **kw)
+        _, TH, TW = gradient_grid(width, height, g.stride)
+        out = np.empty(TH * TW, dtype=np.int32)
+        _check(lib().pt_gradient_pixels(self._h, C.byref(g), int(seed) & 0xffffffff, *_ptrs([out]), 0, None))
+        return out
+
+    def gradient_pixels_into(self, width, height, seed, pixels_ptr, stream=None, **kw):
+        """pt_gradient_pixels into device memory ([TH * TW] int32, the grid gradient_grid gives), enqueued on a HIP stream
+        without a host sync."""
+        g = gradient_params(width, height, **kw)
+        _check(lib().pt_gradient_pixels(self._h, C.byref(g), int(seed) & 0xffffffff, C.c_void_p(pixels_ptr), 1, C.c_void_p(stream or 0)))
+
+    def temporal_gradient_sparse(self, prev_color, pixels, resampled, **kw):
+        """pt_temporal_gradient_sparse on host arrays (prev_color [H, W, 3]; pixels [TH * TW] int32 of gradient_pixels; resampled
+        [TH * TW, 3]: render_pixels of the previous parameters and that list on the current scene): lambda [TH, TW] as a new array."""
+        prev_color, pixels, resampled, g, shape = _gradient_sparse_args(prev_color, pixels, resampled, kw)
+        out = np.empty(shape, dtype=np.float32)
+        _check(lib().pt_temporal_gradient_sparse(self._h, C.byref(g), *_ptrs([prev_color, pixels, resampled, out]), 0, None))
+        return out
+
+    def temporal_gradient_sparse_into(self, width, height, prev_color_ptr, pixels_ptr, resampled_ptr, lambda_ptr, stream=None, **kw):
+        """pt_temporal_gradient_sparse on device memory, enqueued on a HIP stream without a host sync."""
+        g = gradient_params(width, height, **kw)
+        _check(lib().pt_temporal_gradient_sparse(self._h, C.byref(g), C.c_void_p(prev_color_ptr), C.c_void_p(pixels_ptr),
+                                                 C.c_void_p(resampled_ptr), C.c_void_p(lambda_ptr), 1, C.c_void_p(stream or 0)))
+
     def temporal_accumulate_adaptive(self, color, albedo, normal, motion, prev_depth, lam, history=None, stride=0, albedo_floor=0.0,
                                      **kw):
         """pt_temporal_accumulate_adaptive on host arrays: temporal_accumulate_moments with the map `lam` [TH, TW] of
@@ -501,6 +553,37 @@ def temporal_gradient_host(prev_color, resampled, **kw):
     prev_color, resampled, g, shape = _gradient_args(prev_color, resampled, kw)
     out = np.empty(shape, dtype=np.float32)
     _check(lib().pt_temporal_gradient_host(C.byref(g), *_ptrs([prev_color, resampled, out])))
+    return out
+
+
+def gradient_pixels_host(width, height, seed, **kw):
+    """pt_gradient_pixels_host: the pixel of every tile of the gradient grid at `seed` (no GPU needed), [TH * TW] int32."""
+    g = gradient_params(width, height, **kw)
+    _, TH, TW = gradient_grid(width, height, g.stride)
+    out = np.empty(TH * TW, dtype=np.int32)
+    _check(lib().pt_gradient_pixels_host(C.byref(g), int(seed) & 0xffffffff, *_ptrs([out])))
+    return out
+
+
+def _gradient_sparse_args(prev_color, pixels, resampled, kw):
+    prev_color, resampled = (np.ascontiguousarray(a, dtype=np.float32) for a in (prev_color, resampled))
+    pixels = np.ascontiguousarray(pixels, dtype=np.int32).reshape(-1)
+    if prev_color.ndim != 3 or prev_color.shape[2] != 3:
+        raise ValueError("temporal_gradient_sparse: prev_color must be [H, W, 3]")
+    H, W = prev_color.shape[:2]
+    g = gradient_params(W, H, **kw)
+    _, TH, TW = gradient_grid(W, H, g.stride)
+    if pixels.size != TH * TW or resampled.shape != (TH * TW, 3):
+        raise ValueError(f"temporal_gradient_sparse: pixels must be [{TH * TW}] and resampled [{TH * TW}, 3] (one pixel per tile)")
+    return prev_color, pixels, resampled, g, (TH, TW)
+
+
+def temporal_gradient_sparse_host(prev_color, pixels, resampled, **kw):
+    """pt_temporal_gradient_sparse_host: the rule of pt_temporal_gradient_sparse run by the host half of the library (no GPU
+    needed).  Returns lambda [TH, TW]."""
+    prev_color, pixels, resampled, g, shape = _gradient_sparse_args(prev_color, pixels, resampled, kw)
+    out = np.empty(shape, dtype=np.float32)
+    _check(lib().pt_temporal_gradient_sparse_host(C.byref(g), *_ptrs([prev_color, pixels, resampled, out])))
     return out
 
 

@@ -1,7 +1,7 @@
 """N frames of a .pts scene under a moving camera and, optionally, wobbling meshes, cleaned in image space.
 
   python tools/animate.py SCENE.pts [--frames 8] [--size 640x480] [--spp 2] [--translate DX,DY,DZ | --orbit DEG] [--wobble]
-                          [--denoise | --variance | --gradient] [--relight K:R,G,B] [--reference-spp N] [--out PREFIX] [--time]
+                          [--denoise | --variance | --gradient | --gradient-sparse] [--relight K:R,G,B] [--reference-spp N] [--out PREFIX] [--time]
 
 Per frame: pt_render at --spp, pt_render_guides against the previous frame's camera (and, with --wobble, the previous
 geometry: every mesh gets device.wobbled_desc's per-vertex wobble through DeviceScene.update), pt_temporal_accumulate, and with
@@ -14,6 +14,9 @@ its colour, moments and history length (stages "accumulate_moments" and "denoise
 --gradient (implies --variance): from the second frame on, pt_render of the previous frame's parameters on every
 third row of the current scene (stage "rows"), pt_temporal_gradient of the previous noisy frame against it (stage "gradient"),
 and pt_temporal_accumulate_adaptive with that map in place of pt_temporal_accumulate_moments (stage "accumulate_adaptive").
+--gradient-sparse (implies --gradient): the re-trace is one pixel per tile instead of a row.  From the second
+frame on, pt_gradient_pixels with the frame number as its seed (stage "pixels"), pt_render_pixels of the previous frame's
+parameters at that list on the current scene (stage "list"), and pt_temporal_gradient_sparse (stage "gradient").
 --relight K:R,G,B: from frame K on every light's radiance is scaled by (R, G, B) through DeviceScene.update(shading=True).
 --time: after the animation, each stage again on the last frame's inputs, warm, in windows of at least 0.5 s, with
 pt_render_aov and one pt_denoise iteration as yardsticks and the bytes pt_temporal_accumulate must move."""
@@ -103,11 +106,13 @@ def main():
     ap.add_argument("--denoise", action="store_true")
     ap.add_argument("--variance", action="store_true")
     ap.add_argument("--gradient", action="store_true")
+    ap.add_argument("--gradient-sparse", action="store_true")
     ap.add_argument("--relight", default="")
     ap.add_argument("--reference-spp", type=int, default=0)
     ap.add_argument("--out", default="")
     ap.add_argument("--time", action="store_true")
     a = ap.parse_args()
+    a.gradient = a.gradient or a.gradient_sparse
     a.variance = a.variance or a.gradient
     relight_at, relight_factor = None, None
     if a.relight:
@@ -133,6 +138,9 @@ def main():
             st["color"] = f3()
         _, th, tw = dev.gradient_grid(w, h)
         rows, lam = torch.empty((th, w, 3), device="cuda"), torch.zeros((th, tw), device="cuda")
+        if a.gradient_sparse:
+            # one pixel per tile: the list and its re-traced colours
+            pixels, listed = torch.empty(th * tw, dtype=torch.int32, device="cuda"), torch.empty((th * tw, 3), device="cuda")
     p0 = hs.render_params(w, h, a.spp)
     ds.render_aov_into(p0, 0, 0, sets[0]["depth"].data_ptr(), 0)
     z = sets[0]["depth"]
@@ -142,6 +150,8 @@ def main():
         stages = ["render", "guides", "accumulate_moments", "denoise_variance"]
     if a.gradient:
         stages = ["render", "rows", "gradient", "guides", "accumulate_adaptive", "denoise_variance"]
+    if a.gradient_sparse:
+        stages = ["render", "pixels", "list", "gradient", "guides", "accumulate_adaptive", "denoise_variance"]
     times = {s: [] for s in stages}
     errors = {s: [] for s in ("noisy", "accumulated", "denoised", "variance")}
     p_prev = None
@@ -162,7 +172,14 @@ def main():
         if a.gradient:
             color = cur["color"]
         times["render"].append(once(lambda: ds.render_into(p, color.data_ptr(), stream)))
-        if a.gradient:
+        if a.gradient_sparse:
+            times["pixels"].append(once(lambda: ds.gradient_pixels_into(w, h, k, pixels.data_ptr(), stream)) if k else 0.0)
+            times["list"].append(once(lambda: ds.render_pixels_into(p_prev, pixels.data_ptr(), th * tw, listed.data_ptr(), stream))
+                                 if k else 0.0)
+            times["gradient"].append(once(lambda: ds.temporal_gradient_sparse_into(w, h, old["color"].data_ptr(), pixels.data_ptr(),
+                                                                                   listed.data_ptr(), lam.data_ptr(), stream))
+                                     if k else 0.0)
+        elif a.gradient:
             times["rows"].append(once(lambda: ds.render_into(dev.gradient_rows_params(p_prev), rows.data_ptr(), stream)) if k else 0.0)
             times["gradient"].append(once(lambda: ds.temporal_gradient_into(w, h, old["color"].data_ptr(), rows.data_ptr(),
                                                                             lam.data_ptr(), stream)) if k else 0.0)
@@ -241,6 +258,12 @@ def main():
             t["pt_temporal_accumulate_moments"] = timed(lambda: ds.temporal_accumulate_moments_into(
                 w, h, color.data_ptr(), albedo.data_ptr(), cur["normal"].data_ptr(), motion.data_ptr(), prev_depth.data_ptr(), hist5,
                 scratch.data_ptr(), cur["length"].data_ptr(), mom.data_ptr(), stream, **TEMPORAL))
+            if a.gradient_sparse:
+                t["pt_gradient_pixels"] = timed(lambda: ds.gradient_pixels_into(w, h, a.frames - 1, pixels.data_ptr(), stream))
+                t["pt_render_pixels, one pixel per tile of the previous frame"] = timed(lambda: ds.render_pixels_into(
+                    p_prev, pixels.data_ptr(), th * tw, listed.data_ptr(), stream))
+                t["pt_temporal_gradient_sparse"] = timed(lambda: ds.temporal_gradient_sparse_into(
+                    w, h, old["color"].data_ptr(), pixels.data_ptr(), listed.data_ptr(), lam.data_ptr(), stream))
             if a.gradient:
                 t["pt_render, every 3rd row of the previous frame"] = timed(lambda: ds.render_into(dev.gradient_rows_params(p_prev),
                                                                                                    rows.data_ptr(), stream))

@@ -11,10 +11,12 @@
 #include <cstdlib>
 #include <cstring>
 #include <initializer_list>
+#include <iterator>
 #include <limits>
 #include <mutex>
 #include <queue>
 #include <string>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -267,9 +269,9 @@ struct pt_scene {
     int64_t opt_kernel = 2;          // 2 = decoupled traversal/shading (default), 1 = segment-synchronous wavefront kernel,
                                      // 3 = paths regrouped across the waves of a workgroup (pt_kernel_q.h; LDS-resident scenes, else as 2)
     int64_t opt_q_target = 0, opt_q_swap = 0, opt_q_low = 0;   // schedule knobs of kernel 3; 0 = automatic
-    int64_t opt_v2_thresh = 0, opt_v2_inner = 0, opt_v2_minw = 0;   // 0 = auto (see pick_kernel)
-    int64_t opt_reg_stack = 1;      // 1 = register traversal stack where it applies (launch_reg_stack), 0 = always the LDS stack
-    int64_t opt_leaf_sweep = 1;     // 1 = leaves found by the box sweep where it applies (launch_leaf_sweep), 0 = always the tree
+    int64_t opt_v2_thresh = 0, opt_v2_inner = 0, opt_v2_minw = 0;   // 0 = auto (see v2_schedule)
+    int64_t opt_reg_stack = 1;      // 1 = register traversal stack where it applies (choose_trace), 0 = always the LDS stack
+    int64_t opt_leaf_sweep = 1;     // 1 = leaves found by the box sweep where it applies (choose_trace), 0 = always the tree
     // the groups of equal leaf boxes of tree[1] (pt_leaf_sweep.h), made at scene creation where the tree was built on the host
     // and the scene has at most 64 primitives.  sweep_groups = 0: none (also after a geometry update: boxes that were equal need
     // not be any more); it may exceed what a launch admits, sweep.count then stays 0.
@@ -872,97 +874,20 @@ int validate_and_build(const pt_scene_desc* d, pt_scene* S) {
     return PT_OK;
 }
 
-// res: 0 scene in global memory, 1 scene staged in LDS, 2 staged in LDS with the 8 octant node tables,
-//      3 scene in global memory with the top of the tree cached in LDS
-// reg_stack: the kernel keeps its traversal stack in a register (pt_reg_stack.h), the block has no stack columns
-LdsPlan make_plan(const pt_scene* S, int res, bool stack16, int which = 0, bool reg_stack = false) {
-    LdsPlan lp{};
+// The tree a render traverses: the internal tree on the default kernel where scene creation kept one (see launch_render), the
+// caller's tree otherwise.  Pruned traversal (opt-in, tolerance semantics: DESIGN.md §6) takes the internal tree as well — left
+// child first like the exact one, so that its short stacks hold; bunny 7.55 -> 3.89 ms, no pixel moved.
+int which_tree(const pt_scene* S) {
+    return (S->have_fast && S->opt_fast_tree && S->opt_kernel >= 2) ? 1 : 0;
+}
+
+// Residency the next launch will use (see make_plan).
+int scene_residency(const pt_scene* S, int which = 0) {
     const pt_scene::Tree& T = S->tree[which];
-    uint32_t off = 0;
-    if (res == 3) {
-        // as many top nodes as fit next to the stacks within the block's LDS budget (default: without costing a resident block)
-        const uint32_t stack_bytes = (uint32_t)(kBlock / 64) * (uint32_t)T.stack_cap * 64u * 4u;
-        const uint32_t budget = S->opt_lds_budget_kb > 0 ? (uint32_t)S->opt_lds_budget_kb * 1024u : kTopLdsBudget;
-        const uint32_t room = budget > stack_bytes ? budget - stack_bytes : 0u;
-        lp.top_count = std::min<uint32_t>(T.top_avail, room / (uint32_t)sizeof(DNode));
-        lp.nodes_off = 0;
-        off = lp.top_count * (uint32_t)sizeof(DNode);
-    } else if (res != 0) {
-        lp.nodes_off = off;
-        off = align16(off + (res == 2 ? 8u * oct_table_pitch((uint32_t)T.num_nodes, kLdsNodeStride)
-                                      : (uint32_t)T.num_nodes * kLdsNodeStride));
-        lp.prims_off = off; off = align16(off + (uint32_t)S->dev.num_prims * sizeof(DPrim));
-        lp.normals_off = off; off = align16(off + (uint32_t)S->dev.num_prims * sizeof(DNormals));
-        lp.mats_off = off; off = align16(off + (uint32_t)S->dev.num_materials * sizeof(DMaterial));
-        lp.emis_off = off; off = align16(off + (uint32_t)std::max(S->dev.num_emission, 1) * sizeof(DEmission));
-    }
-    lp.stack_off = off;
-    if (!reg_stack) off += (uint32_t)(kBlock / 64) * (uint32_t)T.stack_cap * 64u * (stack16 ? 2u : 4u);
-    lp.total = align16(off);
-    return lp;
-}
-
-using TraceFn = void (*)(SceneDev, RenderDev, LdsPlan, float4*, uint32_t*, unsigned long long*);
-
-// Info "trace_variant": the template arguments of a trace kernel in one int64 (packing: include/pt_api.h).  The pick_*
-// functions hand it back next to the kernel, both made from the same template arguments (v1k / v2k / qk), so that the
-// value reported for a launch cannot disagree with the kernel launched.
-constexpr int64_t trace_variant(int family, int res, bool prune, bool stats, int spec, bool nee, bool list, bool postpone,
-                                int thresh, int inner, int minw, bool reg = false) {
-    return (int64_t)family | (int64_t)res << 4 | (int64_t)prune << 6 | (int64_t)stats << 7 | (int64_t)spec << 8 |
-           (int64_t)nee << 10 | (int64_t)list << 11 | (int64_t)postpone << 12 | (int64_t)reg << 13 | (int64_t)thresh << 16 |
-           (int64_t)(uint16_t)(int16_t)inner << 24 | (int64_t)minw << 40;
-}
-struct TracePick {
-    TraceFn fn;
-    int64_t variant;
-    int bank = 0;        // info "path_bank": the kernel hands out path starts from a register bank (pt_kernels.h: path_bank_on)
-    int reg = 0;         // info "reg_stack": the kernel keeps its traversal stack in a register (pt_reg_stack.h)
-};
-template <bool LDS_SCENE, bool PRUNE, bool STATS, bool LIST = false>
-TracePick v1k() {
-    return {trace_kernel<LDS_SCENE, PRUNE, STATS, LIST>, trace_variant(1, LDS_SCENE, PRUNE, STATS, 0, false, LIST, false, 0, 0, 0)};
-}
-template <int RES, bool PRUNE, bool STATS, int THRESH, int INNER, int MINW, int SPEC, bool NEE = false, bool LIST = false>
-TracePick v2k() {
-    static_assert(INNER >= -32768 && INNER <= 32767 && THRESH >= 0 && THRESH < 256 && MINW >= 0 && MINW < 16, "trace_variant fields");
-    return {trace_kernel_v2<RES, PRUNE, STATS, THRESH, INNER, MINW, SPEC, NEE, LIST>,
-            trace_variant(2, RES, PRUNE, STATS, SPEC, NEE, LIST, false, THRESH, INNER, MINW), path_bank_on(RES, SPEC, NEE, LIST, THRESH, INNER)};
-}
-template <int RES, bool PRUNE, bool STATS, int MINW>
-TracePick v2rk() {           // trace_kernel_v2_reg: the template arguments of its trace_v2, and the register-stack bit
-    return {trace_kernel_v2_reg<RES, PRUNE, STATS, MINW>, trace_variant(2, RES, PRUNE, STATS, 2, false, false, false, 40, 162, MINW, true),
-            path_bank_on(RES, 2, false, false, 40, 162), 1};
-}
-
-TracePick pick_kernel_v1(bool lds, bool prune, bool stats) {
-    if (lds) {
-        if (prune) return stats ? v1k<true, true, true>() : v1k<true, true, false>();
-        return stats ? v1k<true, false, true>() : v1k<true, false, false>();
-    }
-    if (prune) return stats ? v1k<false, true, true>() : v1k<false, true, false>();
-    return stats ? v1k<false, false, true>() : v1k<false, false, false>();
-}
-
-template <int RES, int THRESH, int INNER, int MINW, int SPEC>
-TracePick pick_v2_rt(bool prune, bool stats) {
-    if (prune) return stats ? v2k<RES, true, true, THRESH, INNER, MINW, SPEC>() : v2k<RES, true, false, THRESH, INNER, MINW, SPEC>();
-    return stats ? v2k<RES, false, true, THRESH, INNER, MINW, SPEC>() : v2k<RES, false, false, THRESH, INNER, MINW, SPEC>();
-}
-
-template <int RES, int THRESH, int INNER, int MINW>
-TracePick pick_v2_r(bool prune, bool stats, int spec) {
-    if (spec == 2) return pick_v2_rt<RES, THRESH, INNER, MINW, 2>(prune, stats);
-    if (spec == 1) return pick_v2_rt<RES, THRESH, INNER, MINW, 1>(prune, stats);
-    return pick_v2_rt<RES, THRESH, INNER, MINW, 0>(prune, stats);
-}
-
-template <int THRESH, int INNER, int MINW>
-TracePick pick_v2_ti(int res, bool prune, bool stats, int spec) {
-    if (res == 3) return pick_v2_r<3, THRESH, INNER, MINW>(prune, stats, spec);
-    if (res == 2) return pick_v2_r<2, THRESH, INNER, MINW>(prune, stats, spec);
-    if (res == 1) return pick_v2_r<1, THRESH, INNER, MINW>(prune, stats, spec);
-    return pick_v2_r<0, THRESH, INNER, MINW>(prune, stats, spec);
+    if (S->opt_force_global || S->scene_bytes > kLdsSceneLimit)
+        return (T.top_avail > 0 && S->opt_top_cache && S->opt_kernel >= 2 && !S->opt_force_global) ? 3 : 0;
+    if (S->opt_kernel >= 2 && S->opt_octants && T.have_oct) return 2;
+    return 1;
 }
 
 // (thresh, inner, min-waves-per-SIMD) variants compiled in; inner < 0 selects the "vote" burst of -inner steps, 1..9 a
@@ -975,85 +900,142 @@ TracePick pick_v2_ti(int res, bool prune, bool stats, int spec) {
 // is 5-8 % slower.  Re-checked on the internal tree (fewer inner visits per leaf test): 6 + 2 still wins on LDS-resident scenes
 // (cbox: 5+2 +2.4 %, 4+2 +4.6 %, 3+2 +5.4 %, two rounds of 2+1 +13 %; thresholds 24 / 32 / 48 / 56: +1.7 / 0.0 / +1.2 / +7.5 %; profiles/r02_tune_round44_lds_bursts_rejected.log,
 // r02_tune_round46_thresh_rejected.log).
-TracePick pick_kernel_v2(int res, bool prune, bool stats, int spec, int thresh, int inner, int minw) {
-#define PT_V2(T, I, W) if (thresh == T && inner == I && minw == W) return pick_v2_ti<T, I, W>(res, prune, stats, spec);
-    PT_V2(40, -6, 6) PT_V2(32, 4, 6) PT_V2(40, 4, 6) PT_V2(40, 3, 6) PT_V2(40, 162, 6)
-    PT_V2(32, 1004, 6) PT_V2(32, 1231, 6)
-    PT_V2(32, 1231, 5) PT_V2(40, 162, 5)        // 96 VGPRs, 5 waves per SIMD: for the instantiations that spill under the 80-VGPR cap
-#undef PT_V2
-    return {nullptr, 0};
-}
-
-// The register-stack instantiations (pt_kernels.h: trace_kernel_v2_reg; which launches take them: launch_reg_stack): the default schedule of
-// LDS-resident scenes of triangles with diffuse materials, both register caps.  Each keeps ScratchSize 0 within its cap
-// (profiles/r10_reg_stack.log has the table).
-template <int RES, int MINW>
-TracePick pick_reg_rw(bool prune, bool stats) {
-    if (prune) return stats ? v2rk<RES, true, true, MINW>() : v2rk<RES, true, false, MINW>();
-    return stats ? v2rk<RES, false, true, MINW>() : v2rk<RES, false, false, MINW>();
-}
-TracePick pick_kernel_reg(int res, bool prune, bool stats, int minw) {
-    if (res == 2) return minw == 5 ? pick_reg_rw<2, 5>(prune, stats) : pick_reg_rw<2, 6>(prune, stats);
-    return minw == 5 ? pick_reg_rw<1, 5>(prune, stats) : pick_reg_rw<1, 6>(prune, stats);
-}
-
-// Kernels with next-event estimation (PT_RENDER_NEE): exact traversal, the default schedule of the residency, generic
-// scene content or triangles-with-diffuse-materials only.
-template <int RES, int THRESH, int INNER>
-TracePick pick_nee_r(bool stats, int spec) {
-    if (spec == 2) return stats ? v2k<RES, false, true, THRESH, INNER, 6, 2, true>() : v2k<RES, false, false, THRESH, INNER, 6, 2, true>();
-    return stats ? v2k<RES, false, true, THRESH, INNER, 6, 0, true>() : v2k<RES, false, false, THRESH, INNER, 6, 0, true>();
-}
-TracePick pick_kernel_nee(int res, bool stats, int spec) {
-    if (res == 3) return pick_nee_r<3, 32, 4>(stats, spec);
-    if (res == 2) return pick_nee_r<2, 40, 162>(stats, spec);
-    if (res == 1) return pick_nee_r<1, 40, 162>(stats, spec);
-    return pick_nee_r<0, 32, 4>(stats, spec);
-}
-
-// trace_kernel_q (option "kernel" = 3): LDS-resident scenes, exact traversal, no next-event estimation.
-using TraceFnQ = void (*)(SceneDev, RenderDev, LdsPlan, QParams, float4*, uint32_t*, unsigned long long*);
-struct TracePickQ {
-    TraceFnQ fn;
-    int64_t variant;
+struct V2Schedule {
+    int thresh, inner, minw;
 };
-template <int RES, bool STATS, int SPEC, bool POSTPONE>
-TracePickQ qk() {
-    return {trace_kernel_q<RES, STATS, SPEC, POSTPONE>, trace_variant(3, RES, false, STATS, SPEC, false, false, POSTPONE, 0, 0, 0)};
-}
-template <int RES, bool POSTPONE>
-TracePickQ pick_q_r(bool stats, int spec) {
-    if (spec == 2) return stats ? qk<RES, true, 2, POSTPONE>() : qk<RES, false, 2, POSTPONE>();
-    if (spec == 1) return stats ? qk<RES, true, 1, POSTPONE>() : qk<RES, false, 1, POSTPONE>();
-    return stats ? qk<RES, true, 0, POSTPONE>() : qk<RES, false, 0, POSTPONE>();
-}
-// internal_tree: scenes in global memory set leaves aside (order-free leaf tests need the internal tree's tie handling)
-TracePickQ pick_kernel_q(const pt_scene* S, int res, bool internal_tree) {
-    const int spec = !(S->tri_only && S->opt_specialize) ? 0 : (S->diffuse_only ? 2 : 1);
-    const bool stats = S->opt_stats != 0;
-    if (res == 2) return pick_q_r<2, false>(stats, spec);
-    if (res == 1) return pick_q_r<1, false>(stats, spec);
-    if (res == 3) return internal_tree ? pick_q_r<3, true>(stats, spec) : pick_q_r<3, false>(stats, spec);
-    return internal_tree ? pick_q_r<0, true>(stats, spec) : pick_q_r<0, false>(stats, spec);
+constexpr V2Schedule kV2Schedules[] = {
+    {40, -6, 6}, {32, 4, 6}, {40, 4, 6}, {40, 3, 6}, {40, 162, 6}, {32, 1004, 6}, {32, 1231, 6},
+    {32, 1231, 5}, {40, 162, 5},        // 96 VGPRs, 5 waves per SIMD: for the instantiations that spill under the 80-VGPR cap
+};
+
+// A schedule of trace_kernel_v2 with its zeros, 0 = automatic, resolved for a residency; set_aside: on the internal tree.
+// LDS-resident: 6 inner + 2 leaf steps; global memory: 4 + 1 on the caller's tree; on the internal tree two rounds of
+// 3 + 1 with leaves set aside (v2_inner 1000 + burst).  Setting leaves aside: bunny -2.2 %, dragon stand-in -3.4 %
+// against the plain 4 + 1 (LDS-resident scenes lose 9 % with it: profiles/r02_tune_round43_postponed_leaves.log); two
+// rounds of 3 + 1 instead of one of 4 + 1: teapot -8.5 %, bunny -1.2 %, buddha stand-in -1.5 %, dragon stand-in -1.8 %
+// (r02_tune_round48_global_thresh.log, r02_tune_round49_global_burst.log; thresholds 24 / 40 / 48 lose, so do three rounds of
+// 3 + 1 and two of 2 + 1, and every set-aside shape on LDS-resident scenes: r02_tune_round50_more_bursts_rejected.log; 7 / 8 waves per
+// SIMD by register cap, with the blocks to match: +11..16 % / +28..41 % from the spills, r02_tune_round51_more_waves_rejected.log).
+constexpr V2Schedule v2_schedule(V2Schedule s, bool lds, bool set_aside) {
+    if (s.thresh == 0) s.thresh = lds ? 40 : 32;
+    if (s.inner == 0) s.inner = lds ? 162 : (set_aside ? 1231 : 4);
+    if (s.minw == 0) s.minw = 6;
+    return s;
 }
 
-// LDS plan of trace_kernel_q: the staged scene as for v2, 16-bit traversal stacks for the kQT traversal waves only, then the
-// control words and the two rings (contiguous: the kernel clears them in one sweep).  Also settles the schedule knobs.
-QParams make_plan_q(const pt_scene* S, LdsPlan& lp, int which, int res) {
+// Everything about a trace launch that is settled before a kernel is looked up.  launch_render and the info keys that
+// describe the next launch read the same one (choose_trace).
+struct TraceChoice {
+    int which;                   // the tree traversed (which_tree)
+    int res;                     // 0 scene in global memory, 1 scene staged in LDS, 2 staged in LDS with the 8 octant node tables,
+                                 // 3 scene in global memory with the top of the tree cached in LDS
+    int family;                  // 1 trace_kernel, 2 trace_kernel_v2 (_reg, _sweep), 3 trace_kernel_q
+    bool prune, stats, nee, list, postpone;
+    int spec;                    // 0 generic scene content, 1 triangles only, 2 triangles with diffuse materials only
+    V2Schedule sched;            // family 2
+    bool reg_stack;              // the kernel keeps its traversal stack in a register (pt_reg_stack.h), the block has no stack columns
+    bool sweep;                  // trace_kernel_v2_sweep stands in for the register-stack entry
+    int block_threads;
+    int feed_waves;              // waves per block that draw from the work feed
+    int redo_lanes;              // lanes per block that rerun segments in reference order (one global-memory stack column each)
+    bool lds_scene() const { return res == 1 || res == 2; }
+};
+
+int choose_trace(const pt_scene* S, int traversal, bool nee, bool listed, TraceChoice* out) {
+    TraceChoice c{};
+    // Exact traversal runs on the internal tree where scene creation kept one.  What depends on the visit order is handled the
+    // reference's way: two valid hits with equal t (the first one VISITED wins, scene.h:270) are ordered by one box test in
+    // the caller's tree (pt_trace.h: ref_visits_first); rays with a zero direction component (1/d infinite: the monotonicity
+    // argument of validate_and_build does not cover 0 * inf) are traced on the caller's tree in reference order.
+    c.which = which_tree(S);
+    c.res = scene_residency(S, c.which);
+    const bool exact = traversal == PT_TRAVERSAL_EXACT;
+    if (nee && (S->opt_kernel < 2 || !exact))
+        return fail(PT_ERR_UNSUPPORTED, "PT_RENDER_NEE runs on the default kernel with exact traversal only");
+    // kernel 3 (paths regrouped across the waves of a workgroup) serves exact traversal without next-event estimation or a pixel
+    // list; those run on kernel 2
+    c.family = S->opt_kernel == 1 ? 1 : (S->opt_kernel == 3 && !nee && exact && !listed) ? 3 : 2;
+    c.prune = !exact; c.stats = S->opt_stats != 0; c.nee = nee; c.list = listed;
+    // scenes in global memory set leaves aside on the internal tree (order-free leaf tests need its tie handling)
+    c.postpone = c.family == 3 && !c.lds_scene() && c.which == 1;
+    c.spec = !(S->tri_only && S->opt_specialize) ? 0 : (S->diffuse_only ? 2 : 1);
+    if (nee && c.spec == 1) c.spec = 0;     // with NEE: generic scene content or triangles-with-diffuse-materials only
+    // The LIST and NEE kernels are compiled for the automatic schedule of every residency only — the v2_* knobs change no bit,
+    // so these launches ignore them — and NEE sets no leaves aside.
+    if (c.family == 2)
+        c.sched = v2_schedule((nee || listed) ? V2Schedule{0, 0, 6} : V2Schedule{(int)S->opt_v2_thresh, (int)S->opt_v2_inner, (int)S->opt_v2_minw},
+                              c.lds_scene(), c.which == 1 && !nee);
+    // The traversal stack in a register: option "reg_stack" allows it, the launch runs trace_kernel_v2 without next-event
+    // estimation or a pixel list on a scene of triangles with diffuse materials (the instantiations compiled with it:
+    // find_trace), and reg_stack_on holds for its residency, schedule and tree.  The schedule must be the automatic one:
+    // options "v2_thresh" / "v2_inner" name an instantiation of trace_kernel_v2, and a caller who sets them gets that one
+    // (the tuning tools and the test of every compiled instantiation select kernels that way).  Decided before the LDS plan
+    // is made: such a block has no stack columns.
+    const pt_scene::Tree& T = S->tree[c.which];
+    c.reg_stack = S->opt_reg_stack && c.family == 2 && !nee && !listed && c.spec == 2 && !S->opt_v2_thresh && !S->opt_v2_inner &&
+                  (c.sched.minw == 5 || c.sched.minw == 6) &&
+                  reg_stack_on(c.res, c.sched.thresh, c.sched.inner, c.which == 1, T.stack_cap - 1, T.num_nodes, S->dev.num_prims);
+    // Leaves found by the box sweep (pt_leaf_sweep.h): option "leaf_sweep" allows it, the launch is one of
+    // trace_kernel_v2_reg<2, false, false, MINW> (register stack, octant tables, exact, not counting), and the handle holds a group
+    // table that fits: made at scene creation, dropped by a geometry update.  The kernel stands in for that table entry: same
+    // LDS plan, and it reports that entry's "trace_variant", "reg_stack" and "path_bank"; info "leaf_sweep" alone tells them apart.
+    // The sweep's own tables (pt_sweep_layout.h) go where that plan has the octant node tables: a launch whose tables do not fit
+    // there takes the tree (a binary tree over 3 primitives or more always leaves the room).
+    c.sweep = S->opt_leaf_sweep && leaf_sweep_on(c.reg_stack, exact, c.stats, c.res, S->dev.num_prims, (int)S->sweep.count) &&
+              S->sweep_tab.p && sweep_layout_fits(S->sweep.count, (uint32_t)S->dev.num_prims, (uint32_t)T.num_nodes, kLdsNodeStride);
+    c.block_threads = c.family == 3 ? kQBlock : kBlock;
+    c.feed_waves = c.family == 3 ? kQS : kBlock / 64;
+    c.redo_lanes = c.family == 3 ? kQS * 64 : kBlock;            // kernel 3: its S-waves rerun
+    *out = c;
+    return PT_OK;
+}
+
+// LDS plan of trace_kernel and trace_kernel_v2 (the latter keeps 16-bit stacks for LDS scenes, none with a register stack).
+LdsPlan make_plan(const pt_scene* S, const TraceChoice& c) {
+    LdsPlan lp{};
+    const pt_scene::Tree& T = S->tree[c.which];
+    uint32_t off = 0;
+    if (c.res == 3) {
+        // as many top nodes as fit next to the stacks within the block's LDS budget (default: without costing a resident block)
+        const uint32_t stack_bytes = (uint32_t)(kBlock / 64) * (uint32_t)T.stack_cap * 64u * 4u;
+        const uint32_t budget = S->opt_lds_budget_kb > 0 ? (uint32_t)S->opt_lds_budget_kb * 1024u : kTopLdsBudget;
+        const uint32_t room = budget > stack_bytes ? budget - stack_bytes : 0u;
+        lp.top_count = std::min<uint32_t>(T.top_avail, room / (uint32_t)sizeof(DNode));
+        lp.nodes_off = 0;
+        off = lp.top_count * (uint32_t)sizeof(DNode);
+    } else if (c.res != 0) {
+        lp.nodes_off = off;
+        off = align16(off + (c.res == 2 ? 8u * oct_table_pitch((uint32_t)T.num_nodes, kLdsNodeStride)
+                                        : (uint32_t)T.num_nodes * kLdsNodeStride));
+        lp.prims_off = off; off = align16(off + (uint32_t)S->dev.num_prims * sizeof(DPrim));
+        lp.normals_off = off; off = align16(off + (uint32_t)S->dev.num_prims * sizeof(DNormals));
+        lp.mats_off = off; off = align16(off + (uint32_t)S->dev.num_materials * sizeof(DMaterial));
+        lp.emis_off = off; off = align16(off + (uint32_t)std::max(S->dev.num_emission, 1) * sizeof(DEmission));
+    }
+    lp.stack_off = off;
+    const bool stack16 = c.lds_scene() && c.family >= 2;
+    if (!c.reg_stack) off += (uint32_t)(kBlock / 64) * (uint32_t)T.stack_cap * 64u * (stack16 ? 2u : 4u);
+    lp.total = align16(off);
+    return lp;
+}
+
+// LDS plan of trace_kernel_q, from make_plan's: the staged scene as for v2, 16-bit traversal stacks for the kQT traversal waves
+// only, then the control words and the two rings (contiguous: the kernel clears them in one sweep).  Also settles the schedule knobs.
+QParams make_plan_q(const pt_scene* S, const TraceChoice& c, LdsPlan& lp) {
     QParams q{};
-    const bool lds_scene = res == 1 || res == 2;
-    const uint32_t stack_bytes = (uint32_t)kQT * (uint32_t)S->tree[which].stack_cap * 64u * (lds_scene ? 2u : 4u);
+    const pt_scene::Tree& T = S->tree[c.which];
+    const uint32_t stack_bytes = (uint32_t)kQT * (uint32_t)T.stack_cap * 64u * (c.lds_scene() ? 2u : 4u);
     // scenes in global memory carry 32-bit stacks as deep as the tree's Strahler number: they run with rings of half the size, and
     // the top of the tree takes what two workgroups per CU leave (160 KB / 2, minus stacks and rings)
     uint32_t ring = kQRing;
-    if (!lds_scene) ring = std::max<uint32_t>(64u, kQRing / 2);
+    if (!c.lds_scene()) ring = std::max<uint32_t>(64u, kQRing / 2);
     q.ring_log2 = 0;
     while ((1u << q.ring_log2) < ring) q.ring_log2++;
     const uint32_t ring_bytes = kQCtlBytes + 2u * ring * kQEntryBytes;
-    if (res == 3) {
+    if (c.res == 3) {
         const uint32_t budget = S->opt_lds_budget_kb > 0 ? (uint32_t)S->opt_lds_budget_kb * 1024u : 80u * 1024u;
         const uint32_t used = stack_bytes + ring_bytes + 64u;
-        lp.top_count = std::min<uint32_t>(S->tree[which].top_avail, budget > used ? (budget - used) / (uint32_t)sizeof(DNode) : 0u);
+        lp.top_count = std::min<uint32_t>(T.top_avail, budget > used ? (budget - used) / (uint32_t)sizeof(DNode) : 0u);
         lp.nodes_off = 0;
         lp.stack_off = lp.top_count * (uint32_t)sizeof(DNode);
     }
@@ -1073,132 +1055,131 @@ QParams make_plan_q(const pt_scene* S, LdsPlan& lp, int which, int res) {
     return q;
 }
 
-// Residency the next launch will use (see make_plan).
-// The tree a render traverses: the internal tree on the default kernel where scene creation kept one (see launch_render), the
-// caller's tree otherwise.  Pruned traversal (opt-in, tolerance semantics: DESIGN.md §6) takes the internal tree as well — left
-// child first like the exact one, so that its short stacks hold; bunny 7.55 -> 3.89 ms, no pixel moved.
-int which_tree(const pt_scene* S) {
-    return (S->have_fast && S->opt_fast_tree && S->opt_kernel >= 2) ? 1 : 0;
+// The LDS plan of a launch and, for kernel 3, its schedule parameters.
+int plan_trace(const pt_scene* S, const TraceChoice& c, LdsPlan* lp, QParams* qp) {
+    *lp = make_plan(S, c);
+    if (lp->total > S->lds_per_block_max) return fail(PT_ERR_DEVICE, "LDS plan exceeds the per-block limit");
+    if (c.family != 3) return PT_OK;
+    *qp = make_plan_q(S, c, *lp);
+    if (lp->total > S->lds_per_block_max) return fail(PT_ERR_DEVICE, "LDS plan exceeds the per-block limit");
+    return PT_OK;
 }
 
-int scene_residency(const pt_scene* S, int which = 0) {
-    const pt_scene::Tree& T = S->tree[which];
-    if (S->opt_force_global || S->scene_bytes > kLdsSceneLimit)
-        return (T.top_avail > 0 && S->opt_top_cache && S->opt_kernel >= 2 && !S->opt_force_global) ? 3 : 0;
-    if (S->opt_kernel >= 2 && S->opt_octants && T.have_oct) return 2;
-    return 1;
+// Info "trace_variant": the template arguments of a trace kernel in one int64 (packing: include/pt_api.h).  find_trace hands
+// it back next to the kernel, both made from the same template arguments (v1k / v2k / v2rk / qk), so that the value reported
+// for a launch cannot disagree with the kernel launched.
+constexpr int64_t trace_variant(int family, int res, bool prune, bool stats, int spec, bool nee, bool list, bool postpone,
+                                int thresh, int inner, int minw, bool reg = false) {
+    return (int64_t)family | (int64_t)res << 4 | (int64_t)prune << 6 | (int64_t)stats << 7 | (int64_t)spec << 8 |
+           (int64_t)nee << 10 | (int64_t)list << 11 | (int64_t)postpone << 12 | (int64_t)reg << 13 | (int64_t)thresh << 16 |
+           (int64_t)(uint16_t)(int16_t)inner << 24 | (int64_t)minw << 40;
 }
-
-// The schedule of trace_kernel_v2 after the "v2_*" options, 0 = automatic, have been resolved for a residency and tree:
-// pick_kernel's launch and launch_reg_stack's question about it read the same one.
-// LDS-resident: 6 inner + 2 leaf steps; global memory: 4 + 1 on the caller's tree; on the internal tree two rounds of
-// 3 + 1 with leaves set aside (v2_inner 1000 + burst).  Setting leaves aside: bunny -2.2 %, dragon stand-in -3.4 %
-// against the plain 4 + 1 (LDS-resident scenes lose 9 % with it: profiles/r02_tune_round43_postponed_leaves.log); two
-// rounds of 3 + 1 instead of one of 4 + 1: teapot -8.5 %, bunny -1.2 %, buddha stand-in -1.5 %, dragon stand-in -1.8 %
-// (r02_tune_round48_global_thresh.log, r02_tune_round49_global_burst.log; thresholds 24 / 40 / 48 lose, so do three rounds of
-// 3 + 1 and two of 2 + 1, and every set-aside shape on LDS-resident scenes: r02_tune_round50_more_bursts_rejected.log; 7 / 8 waves per
-// SIMD by register cap, with the blocks to match: +11..16 % / +28..41 % from the spills, r02_tune_round51_more_waves_rejected.log).
-struct V2Schedule {
-    int thresh, inner, minw;
-};
-V2Schedule v2_schedule(const pt_scene* S, int res, bool internal_tree) {
-    const bool lds = res == 1 || res == 2;
-    V2Schedule s{(int)S->opt_v2_thresh, (int)S->opt_v2_inner, (int)S->opt_v2_minw};
-    if (s.thresh == 0) s.thresh = lds ? 40 : 32;
-    if (s.inner == 0) s.inner = lds ? 162 : (internal_tree ? 1231 : 4);
-    if (s.minw == 0) s.minw = 6;
-    return s;
-}
-
-// Does this launch keep its traversal stack in a register?  Option "reg_stack" allows it, the launch runs trace_kernel_v2
-// without next-event estimation or a pixel list on a scene of triangles with diffuse materials (the instantiations compiled
-// with it: pick_kernel_reg), and reg_stack_on holds for its residency, schedule and tree.  The schedule must be the automatic
-// one: options "v2_thresh" / "v2_inner" name an instantiation of trace_kernel_v2, and a caller who sets them gets that one
-// (the tuning tools and the test of every compiled instantiation select kernels that way).  Decided before the LDS plan is
-// made: such a block has no stack columns.
-bool launch_reg_stack(const pt_scene* S, int res, int which, bool nee, bool listed, bool use_q) {
-    if (!S->opt_reg_stack || S->opt_kernel < 2 || use_q || nee || listed) return false;
-    if (!(S->tri_only && S->diffuse_only && S->opt_specialize)) return false;
-    if (S->opt_v2_thresh || S->opt_v2_inner) return false;
-    const V2Schedule sc = v2_schedule(S, res, which == 1);
-    if (sc.minw != 5 && sc.minw != 6) return false;          // the register caps pick_kernel_reg is compiled for
-    const pt_scene::Tree& T = S->tree[which];
-    return reg_stack_on(res, sc.thresh, sc.inner, which == 1, T.stack_cap - 1, T.num_nodes, S->dev.num_prims);
-}
-
-// Does this launch find its leaves by the box sweep (pt_leaf_sweep.h)?  Option "leaf_sweep" allows it, the launch is one of
-// trace_kernel_v2_reg<2, false, false, MINW> (register stack, octant tables, exact, not counting), and the handle holds a group
-// table that fits: made at scene creation, dropped by a geometry update.  The kernel stands in for that table entry: same
-// LDS plan, and it reports that entry's "trace_variant", "reg_stack" and "path_bank"; info "leaf_sweep" alone tells them apart.
-// The sweep's own tables (pt_sweep_layout.h) go where that plan has the octant node tables: a launch whose tables do not fit
-// there takes the tree (a binary tree over 3 primitives or more always leaves the room).
+// The three argument lists of the trace kernels; TraceChoice says which one an entry's kernel takes (launch_trace).
+using TraceFn = void (*)(SceneDev, RenderDev, LdsPlan, float4*, uint32_t*, unsigned long long*);
+using TraceFnQ = void (*)(SceneDev, RenderDev, LdsPlan, QParams, float4*, uint32_t*, unsigned long long*);
 using SweepFn = void (*)(SceneDev, RenderDev, LdsPlan, float4*, uint32_t*, unsigned long long*, SweepLayoutDev);
-bool launch_leaf_sweep(const pt_scene* S, int res, int which, bool reg_stack, bool exact) {
-    return S->opt_leaf_sweep && leaf_sweep_on(reg_stack, exact, S->opt_stats != 0, res, S->dev.num_prims, (int)S->sweep.count) &&
-           S->sweep_tab.p && sweep_layout_fits(S->sweep.count, (uint32_t)S->dev.num_prims, (uint32_t)S->tree[which].num_nodes, kLdsNodeStride);
+struct TraceEntry {
+    const void* fn = nullptr;
+    int64_t variant = 0;
+    int bank = 0;        // info "path_bank": the kernel hands out path starts from a register bank (pt_kernels.h: path_bank_on)
+    int reg = 0;         // info "reg_stack": the kernel keeps its traversal stack in a register (pt_reg_stack.h)
+};
+template <bool LDS_SCENE, bool PRUNE, bool STATS, bool LIST>
+TraceEntry v1k() {
+    return {reinterpret_cast<const void*>(&trace_kernel<LDS_SCENE, PRUNE, STATS, LIST>),
+            trace_variant(1, LDS_SCENE, PRUNE, STATS, 0, false, LIST, false, 0, 0, 0)};
 }
-SweepFn pick_kernel_sweep(int minw) {
-    return minw == 5 ? trace_kernel_v2_sweep<5> : trace_kernel_v2_sweep<6>;
+template <int RES, bool PRUNE, bool STATS, int THRESH, int INNER, int MINW, int SPEC, bool NEE, bool LIST>
+TraceEntry v2k() {
+    static_assert(INNER >= -32768 && INNER <= 32767 && THRESH >= 0 && THRESH < 256 && MINW >= 0 && MINW < 16, "trace_variant fields");
+    return {reinterpret_cast<const void*>(&trace_kernel_v2<RES, PRUNE, STATS, THRESH, INNER, MINW, SPEC, NEE, LIST>),
+            trace_variant(2, RES, PRUNE, STATS, SPEC, NEE, LIST, false, THRESH, INNER, MINW), path_bank_on(RES, SPEC, NEE, LIST, THRESH, INNER)};
+}
+template <int RES, bool PRUNE, bool STATS, int MINW>
+TraceEntry v2rk() {          // trace_kernel_v2_reg: the template arguments of its trace_v2, and the register-stack bit
+    return {reinterpret_cast<const void*>(&trace_kernel_v2_reg<RES, PRUNE, STATS, MINW>),
+            trace_variant(2, RES, PRUNE, STATS, 2, false, false, false, 40, 162, MINW, true), path_bank_on(RES, 2, false, false, 40, 162), 1};
+}
+template <int RES, bool STATS, int SPEC, bool POSTPONE>
+TraceEntry qk() {
+    return {reinterpret_cast<const void*>(&trace_kernel_q<RES, STATS, SPEC, POSTPONE>),
+            trace_variant(3, RES, false, STATS, SPEC, false, false, POSTPONE, 0, 0, 0)};
 }
 
-TracePick pick_kernel(const pt_scene* S, int res, bool prune, bool stats, bool internal_tree, bool reg_stack) {
-    if (S->opt_kernel >= 2) {
-        const V2Schedule sc = v2_schedule(S, res, internal_tree);
-        const int t = sc.thresh, i = sc.inner, w = sc.minw;
-        const bool tri = S->tri_only && S->opt_specialize;
-        if (i >= 1000 && !internal_tree) return {nullptr, 0};   // order-free leaf tests need the internal tree's tie handling
-        const int spec = !tri ? 0 : (S->diffuse_only ? 2 : 1);
-        if (reg_stack) return pick_kernel_reg(res, prune, stats, w);     // launch_reg_stack: spec 2, thresh 40, burst 162
-        return pick_kernel_v2(res, prune, stats, spec, t, i, w);
-    }
-    return pick_kernel_v1(res == 1 || res == 2, prune, stats);
+// Which instantiations of the trace kernels are compiled: find_trace names a kernel only where its predicate holds, and
+// tests/golden/trace_kernels.txt lists the result.
+// trace_kernel_v2 — with NEE: exact traversal, generic scene content or triangles with diffuse materials, the automatic
+// schedule of the residency without leaves set aside; with a pixel list: the automatic schedules of the residency; otherwise
+// every schedule of kV2Schedules.
+constexpr bool v2_compiled(int res, bool prune, V2Schedule s, int spec, bool nee, bool list) {
+    const bool lds = res == 1 || res == 2;
+    const bool automatic = s.minw == 6 && s.thresh == (lds ? 40 : 32) && (lds ? s.inner == 162 : s.inner == 4 || (s.inner == 1231 && !nee));
+    if (nee) return !prune && spec != 1 && automatic;
+    return !list || automatic;
 }
+// trace_kernel_q: LDS-resident scenes set no leaves aside.
+constexpr bool q_compiled(int res, bool postpone) { return !(postpone && (res == 1 || res == 2)); }
 
-// Adaptive rounds after the first (RenderDev::list): the LIST variants of the trace kernels, compiled for the automatic schedule
-// of every residency only — the v2_* knobs change no bit, so these rounds ignore them, and option "kernel" = 3 runs them on 2.
-// NEE is a template argument here so that only the schedules and scene specialisations pick_kernel_nee uses are compiled with it.
-template <int RES, int THRESH, int INNER, int SPEC, bool NEE>
-TracePick pick_list_rs(bool prune, bool stats) {
-    if constexpr (NEE) {
-        return stats ? v2k<RES, false, true, THRESH, INNER, 6, SPEC, true, true>()
-                     : v2k<RES, false, false, THRESH, INNER, 6, SPEC, true, true>();
-    } else {
-        if (prune) return stats ? v2k<RES, true, true, THRESH, INNER, 6, SPEC, false, true>()
-                                : v2k<RES, true, false, THRESH, INNER, 6, SPEC, false, true>();
-        return stats ? v2k<RES, false, true, THRESH, INNER, 6, SPEC, false, true>()
-                     : v2k<RES, false, false, THRESH, INNER, 6, SPEC, false, true>();
-    }
+// f(std::integral_constant<., V>) for the V among Vs that equals v: a runtime value becomes a template argument.  No such V: no kernel.
+template <auto... Vs, class T, class F>
+TraceEntry among(T v, F f) {
+    TraceEntry r{};
+    (void)((v == (T)Vs ? (r = f(std::integral_constant<decltype(Vs), Vs>{}), true) : false) || ...);
+    return r;
 }
-template <int RES, int THRESH, int INNER, bool NEE>
-TracePick pick_list_r(bool prune, bool stats, int spec) {
-    if (spec == 2) return pick_list_rs<RES, THRESH, INNER, 2, NEE>(prune, stats);
-    if constexpr (!NEE) {
-        if (spec == 1) return pick_list_rs<RES, THRESH, INNER, 1, NEE>(prune, stats);
-    }
-    return pick_list_rs<RES, THRESH, INNER, 0, NEE>(prune, stats);
+#define PT_CONST(x) decltype(x)::value
+
+// The kernel of a choice, or no kernel where none is compiled for it (options "v2_thresh" / "v2_inner" / "v2_minw").
+// with_sweep = false: the table entry the sweep kernel stands in for.
+TraceEntry find_trace(const TraceChoice& c, bool with_sweep = true) {
+    if (c.family == 1)
+        return among<false, true>(c.lds_scene(), [&](auto L) { return among<false, true>(c.prune, [&](auto P) {
+               return among<false, true>(c.stats, [&](auto S) { return among<false, true>(c.list, [&](auto LI) {
+                   return v1k<PT_CONST(L), PT_CONST(P), PT_CONST(S), PT_CONST(LI)>(); }); }); }); });
+    if (c.family == 3)
+        return among<0, 1, 2, 3>(c.res, [&](auto R) { return among<false, true>(c.stats, [&](auto S) {
+               return among<0, 1, 2>(c.spec, [&](auto SP) { return among<false, true>(c.postpone, [&](auto PO) {
+                   if constexpr (q_compiled(PT_CONST(R), PT_CONST(PO))) return qk<PT_CONST(R), PT_CONST(S), PT_CONST(SP), PT_CONST(PO)>();
+                   else return TraceEntry{}; }); }); }); });
+    // trace_kernel_v2_reg (choose_trace: spec 2, thresh 40, burst 162): the default schedule of LDS-resident scenes of triangles
+    // with diffuse materials, both register caps.  Each keeps ScratchSize 0 within its cap (profiles/r10_reg_stack.log has the table).
+    if (c.reg_stack)
+        return among<1, 2>(c.res, [&](auto R) { return among<5, 6>(c.sched.minw, [&](auto W) {
+               return among<false, true>(c.prune, [&](auto P) { return among<false, true>(c.stats, [&](auto S) {
+                   TraceEntry e = v2rk<PT_CONST(R), PT_CONST(P), PT_CONST(S), PT_CONST(W)>();
+                   if (c.sweep && with_sweep) e.fn = reinterpret_cast<const void*>(&trace_kernel_v2_sweep<PT_CONST(W)>);   // keeps the entry's variant
+                   return e; }); }); }); });
+    if (c.sched.inner >= 1000 && c.which != 1) return {};      // order-free leaf tests need the internal tree's tie handling
+    static_assert(std::size(kV2Schedules) == 9, "the index list below enumerates kV2Schedules");
+    int si = -1;
+    for (int k = 0; k < (int)std::size(kV2Schedules); k++)
+        if (kV2Schedules[k].thresh == c.sched.thresh && kV2Schedules[k].inner == c.sched.inner && kV2Schedules[k].minw == c.sched.minw) si = k;
+    return among<0, 1, 2, 3, 4, 5, 6, 7, 8>(si, [&](auto SI) { return among<0, 1, 2, 3>(c.res, [&](auto R) {
+           return among<false, true>(c.nee, [&](auto N) { return among<false, true>(c.list, [&](auto LI) {
+           static constexpr V2Schedule s = kV2Schedules[PT_CONST(SI)];
+           // (most NEE and LIST schedules end here: the lambdas below are not instantiated for them, which the build time notices)
+           if constexpr (!v2_compiled(PT_CONST(R), false, s, 0, PT_CONST(N), PT_CONST(LI))) return TraceEntry{};
+           else return among<0, 1, 2>(c.spec, [&](auto SP) { return among<false, true>(c.prune, [&](auto P) {
+           return among<false, true>(c.stats, [&](auto S) {
+               if constexpr (v2_compiled(PT_CONST(R), PT_CONST(P), s, PT_CONST(SP), PT_CONST(N), PT_CONST(LI)))
+                   return v2k<PT_CONST(R), PT_CONST(P), PT_CONST(S), s.thresh, s.inner, s.minw, PT_CONST(SP), PT_CONST(N), PT_CONST(LI)>();
+               else return TraceEntry{}; }); }); }); }); }); }); });
 }
-TracePick pick_kernel_list(const pt_scene* S, int res, bool prune, bool stats, bool internal_tree, bool nee) {
-    if (S->opt_kernel == 1) {
-        if (res == 1 || res == 2) {
-            if (prune) return stats ? v1k<true, true, true, true>() : v1k<true, true, false, true>();
-            return stats ? v1k<true, false, true, true>() : v1k<true, false, false, true>();
-        }
-        if (prune) return stats ? v1k<false, true, true, true>() : v1k<false, true, false, true>();
-        return stats ? v1k<false, false, true, true>() : v1k<false, false, false, true>();
-    }
-    const bool tri = S->tri_only && S->opt_specialize;
-    const int spec = !tri ? 0 : (S->diffuse_only ? 2 : 1);
-    // the automatic schedules of pick_kernel / pick_kernel_nee
-    if (nee) {
-        if (res == 3) return pick_list_r<3, 32, 4, true>(false, stats, spec);
-        if (res == 2) return pick_list_r<2, 40, 162, true>(false, stats, spec);
-        if (res == 1) return pick_list_r<1, 40, 162, true>(false, stats, spec);
-        return pick_list_r<0, 32, 4, true>(false, stats, spec);
-    }
-    if (res == 2) return pick_list_r<2, 40, 162, false>(prune, stats, spec);
-    if (res == 1) return pick_list_r<1, 40, 162, false>(prune, stats, spec);
-    if (res == 3) return internal_tree ? pick_list_r<3, 32, 1231, false>(prune, stats, spec) : pick_list_r<3, 32, 4, false>(prune, stats, spec);
-    return internal_tree ? pick_list_r<0, 32, 1231, false>(prune, stats, spec) : pick_list_r<0, 32, 4, false>(prune, stats, spec);
+#undef PT_CONST
+
+// The one typed launch of a trace kernel: the entry's kernel takes the argument list of the choice's family.
+void launch_trace(const pt_scene* S, const TraceChoice& c, const TraceEntry& e, int grid, hipStream_t stream, const RenderDev& rd,
+                  const LdsPlan& lp, const QParams& qp, float4* samples) {
+    void* const fn = const_cast<void*>(e.fn);
+    if (c.family == 3)
+        hipLaunchKernelGGL(reinterpret_cast<TraceFnQ>(fn), dim3(grid), dim3(c.block_threads), lp.total, stream, S->dev, rd, lp, qp,
+                           samples, S->work_counter(), S->counters());
+    else if (c.sweep)
+        hipLaunchKernelGGL(reinterpret_cast<SweepFn>(fn), dim3(grid), dim3(c.block_threads), lp.total, stream, S->dev, rd, lp,
+                           samples, S->work_counter(), S->counters(), SweepLayoutDev{S->sweep_tab.p, S->sweep.count, 0u});
+    else
+        hipLaunchKernelGGL(reinterpret_cast<TraceFn>(fn), dim3(grid), dim3(c.block_threads), lp.total, stream, S->dev, rd, lp,
+                           samples, S->work_counter(), S->counters());
 }
 
 // Sums the kCounterSlots per-workgroup counter slots of the last frame (the caller has synchronised the stream).
@@ -1215,10 +1196,6 @@ int read_slot_sums(const pt_scene* S, unsigned long long* out) {
 int launch_grid(int num_cus, int blocks_per_cu, uint64_t work_items, int block_threads = kBlock) {
     const uint64_t blocks_needed = (work_items + (uint64_t)block_threads - 1) / (uint64_t)block_threads;
     return (int)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)num_cus * (uint64_t)blocks_per_cu, blocks_needed));
-}
-// Lanes (= global-memory stack columns of the reference-order reruns) of that launch.
-size_t redo_stack_lanes(int num_cus, int blocks_per_cu, uint64_t work_items) {
-    return (size_t)launch_grid(num_cus, blocks_per_cu, work_items) * kBlock;
 }
 
 struct RowSel {
@@ -1253,10 +1230,8 @@ struct PixelList {
     uint32_t n;
 };
 
-// mode: 0 = pt_render (fb = mean), 2 = pt_render_accumulate (accum (+)= sum); ad: a round of pt_render_adaptive (mode 0);
-// pl: the pixels to trace in place of the selected rows (out_dev is then [n, 3]; n == 0: an empty frame, out_dev may be null)
-int launch_render(pt_scene* S, const pt_render_params* p, float* out_dev, int mode, hipStream_t stream,
-                  const AdaptiveRound* ad = nullptr, const PixelList* pl = nullptr) {
+// The checks on a render call's arguments that come before its frame is opened, and its row selection.
+int check_render_args(const pt_scene* S, const pt_render_params* p, const float* out_dev, const PixelList* pl, RowSel* rows) {
     if (!S || !p || (!out_dev && !(pl && pl->n == 0))) return fail(PT_ERR_INVALID_ARG, "null argument");
     if (p->width <= 0 || p->height <= 0 || p->spp <= 0) return fail(PT_ERR_INVALID_ARG, "width, height and spp must be positive");
     if (p->sample_offset < 0 || p->stream_stride < 0) return fail(PT_ERR_INVALID_ARG, "negative sample_offset / stream_stride");
@@ -1268,27 +1243,35 @@ int launch_render(pt_scene* S, const pt_render_params* p, float* out_dev, int mo
         return fail(PT_ERR_INVALID_ARG, p->stream_stride > 0
                         ? "sample_offset + spp exceeds stream_stride: PCG streams of neighbouring pixels would overlap"
                         : "sample_offset > 0 needs an explicit stream_stride >= total sample count (default stride = spp)");
-    RowSel rows;
-    int rc = select_rows(p, &rows);
-    if (rc) return rc;
-    DeviceGuard guard;
-    { int grc = guard.enter(S->device); if (grc) return grc; }
-    // this call's frame slot (see pt_scene::FrameSlot)
-    const int in_flight = (int)std::min<int64_t>(kMaxFramesInFlight, std::max<int64_t>(1, S->opt_frames_in_flight));
-    const bool timing = S->opt_timing_frames > 0;        // 0: no HIP events around the kernels (four records less per frame)
+    return select_rows(p, rows);
+}
+
+// What opening a frame settles: the call's frame slot (see pt_scene::FrameSlot) and its record in the timing ring.
+struct OpenFrame {
+    int in_flight;
+    bool timing;                 // false: no HIP events around the kernels (four records less per frame)
+    bool prev_busy;              // the previous call's frame is still on the GPU
+    pt_scene::FrameSlot* slot;
+    pt_scene::FrameRec* rec;
+    size_t pass_base;            // passes of earlier adaptive rounds of this frame
+};
+// cont: a later adaptive round, which continues the frame of round 0
+int open_frame(pt_scene* S, hipStream_t stream, bool cont, OpenFrame* f) {
+    f->in_flight = (int)std::min<int64_t>(kMaxFramesInFlight, std::max<int64_t>(1, S->opt_frames_in_flight));
+    f->timing = S->opt_timing_frames > 0;
     // Is the previous call's frame still on the GPU?  If not there is nothing to overlap with, and this frame runs on the
     // caller's stream as with one slot: a caller that synchronises after every frame (a display loop) does not pay for two
     // event waits across streams per frame.
-    const bool cont = ad && ad->round > 0;               // a later adaptive round: continues the frame of round 0
-    bool prev_busy = false;
-    if (!cont && in_flight > 1 && S->frame_seq > 0 && S->cur().used) {
-        prev_busy = hipEventQuery(S->cur().free_ev) == hipErrorNotReady;
+    f->prev_busy = false;
+    if (!cont && f->in_flight > 1 && S->frame_seq > 0 && S->cur().used) {
+        f->prev_busy = hipEventQuery(S->cur().free_ev) == hipErrorNotReady;
         (void)hipGetLastError();
     }
-    if (!cont) S->cur_slot = (int)(S->frame_seq % (uint64_t)in_flight);
-    pt_scene::FrameSlot& slot = S->cur();
-    if ((rc = slot.ctl.ensure(kWorkWords + kNumCounters))) return rc;
-    if (!slot.free_ev) HIP_TRY(hipEventCreateWithFlags(&slot.free_ev, hipEventDisableTiming));
+    if (!cont) S->cur_slot = (int)(S->frame_seq % (uint64_t)f->in_flight);
+    f->slot = &S->cur();
+    int rc = f->slot->ctl.ensure(kWorkWords + kNumCounters);
+    if (rc) return rc;
+    if (!f->slot->free_ev) HIP_TRY(hipEventCreateWithFlags(&f->slot->free_ev, hipEventDisableTiming));
     S->last_stream = stream;
     S->have_timing = false;
     if (!cont) {
@@ -1299,26 +1282,29 @@ int launch_render(pt_scene* S, const pt_render_params* p, float* out_dev, int mo
         S->frames[S->frame_seq % S->frames.size()].passes = 0;
         S->frame_seq++;
     }
-    pt_scene::FrameRec& frec = S->frames[(S->frame_seq - 1) % S->frames.size()];
-    const size_t pass_base = frec.passes;               // passes of earlier adaptive rounds of this frame
-    if (rows.count == 0 || (pl && pl->n == 0)) {           // nothing to trace: the frame's counters read zero
-        S->info_trace_variant = 0;
-        S->info_path_bank = 0;
-        S->info_reg_stack = 0;
-        S->info_leaf_sweep = 0;
-        if (slot.used && slot.free_stream != stream) HIP_TRY(hipStreamWaitEvent(stream, slot.free_ev, 0));
-        HIP_TRY(hipMemsetAsync(slot.ctl.p, 0, (kWorkWords + kTimelineBase) * sizeof(unsigned long long), stream));
-        HIP_TRY(hipEventRecord(slot.free_ev, stream));
-        slot.used = true; slot.free_stream = stream;
-        return PT_OK;
-    }
+    f->rec = &S->frames[(S->frame_seq - 1) % S->frames.size()];
+    f->pass_base = f->rec->passes;
+    return PT_OK;
+}
 
-    // a pixel list is a frame of n rows of width 1 (RenderDev::list)
-    const bool listed = pl != nullptr;
-    const int vrows = listed ? (int)pl->n : rows.count, vwidth = listed ? 1 : p->width;
-    const uint64_t npix = (uint64_t)vrows * (uint64_t)vwidth;
+// A frame with nothing to trace: its counters read zero.
+int empty_frame(pt_scene* S, pt_scene::FrameSlot& slot, hipStream_t stream) {
+    S->info_trace_variant = 0;
+    S->info_path_bank = 0;
+    S->info_reg_stack = 0;
+    S->info_leaf_sweep = 0;
+    if (slot.used && slot.free_stream != stream) HIP_TRY(hipStreamWaitEvent(stream, slot.free_ev, 0));
+    HIP_TRY(hipMemsetAsync(slot.ctl.p, 0, (kWorkWords + kTimelineBase) * sizeof(unsigned long long), stream));
+    HIP_TRY(hipEventRecord(slot.free_ev, stream));
+    slot.used = true; slot.free_stream = stream;
+    return PT_OK;
+}
+
+// Samples per pass — bounded by the scratch budget and by 2^30 work items per launch — and the passes that makes; the sample
+// buffer of the slot (and, for several passes of a plain render, the accumulator) allocated to match.
+int plan_passes(pt_scene* S, const pt_render_params* p, int mode, bool adaptive, pt_scene::FrameSlot& slot, uint64_t npix,
+                uint64_t* spp_pass_out, int* n_pass_out) {
     if (npix > (1ull << 30)) return fail(PT_ERR_INVALID_ARG, "more than 2^30 pixels per call");
-    // samples per pass: bounded by the scratch budget and by 2^30 work items per launch
     uint64_t scratch = S->opt_scratch_bytes > 0 ? (uint64_t)S->opt_scratch_bytes : kDefaultScratchBytes;
     if (S->opt_scratch_bytes <= 0 && std::min<uint64_t>(scratch, npix * (uint64_t)p->spp * sizeof(float4)) > slot.samples.n * sizeof(float4)) {
         // the buffer must grow under the default budget: never to more than a quarter of what is free on the device right
@@ -1332,6 +1318,7 @@ int launch_render(pt_scene* S, const pt_render_params* p, float* out_dev, int mo
     if (mode == 2 && spp_pass < (uint64_t)p->spp)
         return fail(PT_ERR_UNSUPPORTED, "pt_render_accumulate: spp of one call must fit the scratch budget (single pass)");
     // allocation failure (another handle took the memory meanwhile): halve the samples per pass and retry
+    int rc;
     while ((rc = slot.samples.ensure(npix * spp_pass))) {
         if (spp_pass == 1 || mode == 2) return rc;
         (void)hipGetLastError();
@@ -1340,58 +1327,28 @@ int launch_render(pt_scene* S, const pt_render_params* p, float* out_dev, int mo
     const int n_pass = (int)(((uint64_t)p->spp + spp_pass - 1) / spp_pass);
     if (mode == 2 && n_pass > 1)
         return fail(PT_ERR_UNSUPPORTED, "pt_render_accumulate: spp of one call must fit the scratch budget (single pass)");
-    if (n_pass > 1 && !ad && (rc = S->accum.ensure(npix * 3))) return rc;
+    if (n_pass > 1 && !adaptive && (rc = S->accum.ensure(npix * 3))) return rc;
+    *spp_pass_out = spp_pass;
+    *n_pass_out = n_pass;
+    return PT_OK;
+}
 
-    const int traversal = p->traversal == PT_TRAVERSAL_DEFAULT ? PT_TRAVERSAL_EXACT : p->traversal;
-    if (traversal != PT_TRAVERSAL_EXACT && traversal != PT_TRAVERSAL_PRUNED) return fail(PT_ERR_INVALID_ARG, "unknown traversal mode");
-    // Exact traversal runs on the internal tree where scene creation kept one.  What depends on the visit order is handled the
-    // reference's way: two valid hits with equal t (the first one VISITED wins, scene.h:270) are ordered by one box test in
-    // the caller's tree (pt_trace.h: ref_visits_first); rays with a zero direction component (1/d infinite: the monotonicity
-    // argument of validate_and_build does not cover 0 * inf) are traced on the caller's tree in reference order.
-    const int which = which_tree(S);
-    const int res = scene_residency(S, which);
-    const bool lds_scene = res == 1 || res == 2;
-    if (p->flags & ~PT_RENDER_NEE) return fail(PT_ERR_INVALID_ARG, "unknown bits in pt_render_params.flags");
-    const bool nee = (p->flags & PT_RENDER_NEE) != 0;
-    if (nee && (S->opt_kernel < 2 || traversal != PT_TRAVERSAL_EXACT))
-        return fail(PT_ERR_UNSUPPORTED, "PT_RENDER_NEE runs on the default kernel with exact traversal only");
-    // kernel 3 (paths regrouped across the waves of a workgroup) serves exact traversal without next-event estimation; those run
-    // on kernel 2
-    const bool use_q = S->opt_kernel == 3 && !nee && traversal == PT_TRAVERSAL_EXACT && !listed;
-    const bool reg_stack = launch_reg_stack(S, res, which, nee, listed, use_q);
-    LdsPlan lp = make_plan(S, res, lds_scene && S->opt_kernel >= 2, which, reg_stack);   // trace_kernel_v2 keeps 16-bit stacks for LDS scenes
-    if (lp.total > S->lds_per_block_max) return fail(PT_ERR_DEVICE, "LDS plan exceeds the per-block limit");
-    QParams qp{};
-    TraceFnQ fnq = nullptr;
-    TraceFn fn = nullptr;
-    SweepFn fns = nullptr;           // set: this launch runs trace_kernel_v2_sweep in place of fn
-    int64_t variant = 0;
-    int path_bank = 0, reg_stack_used = 0;
-    if (use_q) {
-        qp = make_plan_q(S, lp, which, res);
-        if (lp.total > S->lds_per_block_max) return fail(PT_ERR_DEVICE, "LDS plan exceeds the per-block limit");
-        const TracePickQ pq = pick_kernel_q(S, res, which == 1);
-        fnq = pq.fn; variant = pq.variant;
-    } else {
-        const TracePick pk = listed ? pick_kernel_list(S, res, traversal == PT_TRAVERSAL_PRUNED, S->opt_stats != 0, which == 1, nee)
-                           : nee ? pick_kernel_nee(res, S->opt_stats != 0, (S->tri_only && S->diffuse_only && S->opt_specialize) ? 2 : 0)
-                                 : pick_kernel(S, res, traversal == PT_TRAVERSAL_PRUNED, S->opt_stats != 0, which == 1, reg_stack);
-        fn = pk.fn; variant = pk.variant; path_bank = pk.bank; reg_stack_used = pk.reg;
-        if (!fn) return fail(PT_ERR_INVALID_ARG, "no kernel variant compiled for these v2_thresh / v2_inner options");
-        // the sweep kernel in place of the register-stack entry just picked, whose variant and plan it keeps
-        if (!listed && !nee && launch_leaf_sweep(S, res, which, reg_stack, traversal == PT_TRAVERSAL_EXACT))
-            fns = pick_kernel_sweep(v2_schedule(S, res, which == 1).minw);
-    }
-    const void* fn_any = use_q ? reinterpret_cast<const void*>(fnq) : fns ? reinterpret_cast<const void*>(fns) : reinterpret_cast<const void*>(fn);
-    const int block_threads = use_q ? kQBlock : kBlock;
-    if (S->cfg_fn != fn_any || S->cfg_lds != lp.total) {
-        if (lp.total > 64 * 1024)
-            HIP_TRY(hipFuncSetAttribute(fn_any, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lp.total));
+// Resident blocks per CU of a kernel with its LDS plan: the launch configuration of the last kernel used is kept (occupancy
+// query and attribute call are not free per frame).
+int launch_occupancy(pt_scene* S, const void* fn, int block_threads, uint32_t lds, int* occ) {
+    if (S->cfg_fn != fn || S->cfg_lds != lds) {
+        if (lds > 64 * 1024)
+            HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         int q = 0;
-        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&q, fn_any, block_threads, lp.total));
-        S->cfg_fn = fn_any; S->cfg_lds = lp.total; S->cfg_occ = std::max(q, 1);
+        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&q, fn, block_threads, lds));
+        S->cfg_fn = fn; S->cfg_lds = lds; S->cfg_occ = std::max(q, 1);
     }
-    const int occ = S->cfg_occ;
+    *occ = S->cfg_occ;
+    return PT_OK;
+}
+
+// Blocks per CU a launch takes of the `occ` the occupancy query allows.
+int launch_blocks_per_cu(const pt_scene* S, bool lds_scene, int occ, bool own_stream, int in_flight) {
     // scenes read from global memory: 6 blocks per CU (what 80 VGPRs allow) with a 26 KB stack + top-of-tree budget each.
     // With the internal tree's short stacks (its Strahler number, not its depth) the sixth block no longer costs cached nodes
     // worth having: bunny +0.6 %, buddha stand-in -1.1 %, dragon stand-in -7.6 % against 5 blocks of 31 KB
@@ -1403,47 +1360,160 @@ int launch_render(pt_scene* S, const pt_render_params* p, float* out_dev, int mo
     // With three slots a frame takes half of each CU — two frames are resident side by side, half a frame apart, the third
     // enters where the first leaves — with two slots all but one block per CU (cbox 2.55 ms per frame with full grids,
     // 2.50 with 5 + 1 of 6, 2.49 with 3 + 3 and three slots; bunny 4.64 / 4.53 / 4.39; profiles/r03_frames_in_flight.log).
-    // (a pixel list stays on the caller's stream: its trace kernel reads the caller's memory)
-    const bool own_stream = !ad && !listed && in_flight > 1 && n_pass == 1 && prev_busy;
     if (own_stream && S->opt_blocks_per_cu <= 0) bpc = std::max(1, in_flight >= 3 ? bpc / 2 : bpc - 1);
-    S->info_kernel = use_q ? 3 : S->opt_kernel == 1 ? 1 : 2;
-    S->info_trace_variant = variant;
-    S->info_path_bank = path_bank;
-    S->info_reg_stack = reg_stack_used;
-    S->info_leaf_sweep = fns ? 1 : 0;
+    return bpc;
+}
+
+// The slot's own stream and the event that marks the point of the call on the caller's stream, made on first use.
+int slot_stream(pt_scene::FrameSlot& slot) {
+    if (!slot.stream) {
+        // A stream of the lowest priority: the runtime maps streams onto a few hardware queues PER PRIORITY (4 by default),
+        // and two streams on one hardware queue run in order.  Among the application's own normal-priority streams the two
+        // slot streams ended up sharing a queue with each other or with the caller's as often as not (one more stream in
+        // the process: 2.70 ms per cbox frame with two slots against 2.69 with one; on queues of their own 2.53 —
+        // profiles/r03_frames_in_flight.log).  Low rather than high: a frame waits for the caller's other GPU work (the
+        // RCCL gather of the rank's rows, N > 1), not the other way round.  PT_SLOT_STREAM_PRIORITY=normal|high: A/B runs.
+        const char* pr = std::getenv("PT_SLOT_STREAM_PRIORITY");
+        const std::string want = pr ? pr : "low";
+        int least = 0, greatest = 0;
+        if (want != "normal" && hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && least != greatest)
+            HIP_TRY(hipStreamCreateWithPriority(&slot.stream, hipStreamNonBlocking, want == "high" ? greatest : least));
+        else
+            HIP_TRY(hipStreamCreateWithFlags(&slot.stream, hipStreamNonBlocking));
+    }
+    if (!slot.in_ev) HIP_TRY(hipEventCreateWithFlags(&slot.in_ev, hipEventDisableTiming));
+    return PT_OK;
+}
+
+// The render arguments of a pass of sn samples from sample s0 on; feed_waves: the waves of the launch that draw from the work
+// feed.  A pixel list is a frame of n rows of width 1 (RenderDev::list).
+RenderDev pass_render_dev(const pt_scene* S, const pt_render_params* p, const RowSel& rows, const PixelList* pl, int s0, int sn,
+                          uint64_t feed_waves) {
+    const int vrows = pl ? (int)pl->n : rows.count, vwidth = pl ? 1 : p->width;
+    const uint64_t npix = (uint64_t)vrows * (uint64_t)vwidth;
+    RenderDev rd{};
+    std::memcpy(rd.cam_origin, p->cam_origin, 12);
+    std::memcpy(rd.cam_top_left, p->cam_top_left, 12);
+    std::memcpy(rd.cam_horizontal, p->cam_horizontal, 12);
+    std::memcpy(rd.cam_vertical, p->cam_vertical, 12);
+    rd.width = vwidth; rd.height = p->height;
+    rd.row_begin = rows.begin; rd.row_step = rows.step; rd.num_rows = vrows;
+    rd.list = pl ? pl->list : nullptr;
+    rd.img_width = p->width;
+    rd.div_img_width = make_fastdiv((uint32_t)p->width);
+    rd.spp_pass = sn;
+    rd.sample_base = p->sample_offset + s0;
+    rd.stream_stride = p->stream_stride > 0 ? p->stream_stride : p->spp;
+    rd.seed = p->seed;
+    rd.max_depth = p->max_depth > 0 ? p->max_depth : 50;
+    rd.rr_depth = p->rr_depth >= 0 ? p->rr_depth : 5;
+    rd.npix = (uint32_t)npix;
+    rd.total_work = (uint32_t)(npix * (uint64_t)sn);
+    rd.num_regions = S->opt_xcd_regions > 0 ? (int)std::min<int64_t>(S->opt_xcd_regions, 8) : 8;
+    rd.rows_per_region = (vrows + rd.num_regions - 1) / rd.num_regions;
+    rd.div_width = make_fastdiv((uint32_t)vwidth);
+    rd.div_spp = make_fastdiv((uint32_t)sn);
+    rd.row_major = S->opt_item_order == 1 ? 1 : 0;
+    rd.div_npix_full = make_fastdiv((uint32_t)rd.rows_per_region * (uint32_t)vwidth);
+    {   // the band that holds the remainder rows (all bands after it are empty)
+        const int full = vrows / rd.rows_per_region, rest = vrows - full * rd.rows_per_region;
+        rd.short_region = rest ? full : -1;
+        rd.div_npix_last = make_fastdiv((uint32_t)std::max(rest, 1) * (uint32_t)vwidth);
+    }
+    // chunk: work items a wave reserves per atomic.  Big launches (a wave traces >= 2048 items): 128 — the waves of a
+    // launch run dry within two paths' time of each other instead of four (cbox -1.9 %, bunny -0.9 % against 256; 64
+    // buys nothing more and saturates the counters on cheap scenes: profiles/r02_tune_round36_*.log); mid-size
+    // launches 256; small launches (interactive 1-2 spp frames) down to 64 so that the items are spread over all
+    // resident waves instead of the first total/256 of them
+    const uint64_t per_wave = rd.total_work / feed_waves;
+    rd.chunk = per_wave >= 2048 ? 128u
+             : per_wave >= 4 * kMaxChunk ? kMaxChunk : (uint32_t)std::max<uint64_t>(64, std::min<uint64_t>(kMaxChunk, (per_wave / 64) * 64));
+    if (S->opt_chunk > 0) rd.chunk = (uint32_t)std::min<int64_t>(kMaxChunk, std::max<int64_t>(64, (S->opt_chunk / 64) * 64));
+    return rd;
+}
+
+// The four events of pass ev_pass of a frame's timing record, created where the record does not hold them yet.
+int pass_events(pt_scene::FrameRec& rec, size_t ev_pass) {
+    if (rec.ev.size() > ev_pass) return PT_OK;
+    pt_scene::PassEvents fresh{};
+    hipEvent_t* const ev[4] = {&fresh.t0, &fresh.t1, &fresh.r0, &fresh.r1};
+    for (int k = 0; k < 4; k++) {
+        const hipError_t ee = hipEventCreate(ev[k]);
+        if (ee == hipSuccess) continue;
+        while (k-- > 0) (void)hipEventDestroy(*ev[k]);
+        return fail(PT_ERR_DEVICE, std::string("hipEventCreate: ") + hipGetErrorString(ee));
+    }
+    rec.ev.push_back(fresh);
+    return PT_OK;
+}
+
+// What resolve_kernel does with a pass: rmode 2 adds the pass's partial sum (progressive: every pass adds its own; first only
+// if sample_offset == 0 and pass 0), 0 writes the mean after the last pass, 1 accumulates a pass before the last.
+struct ResolveMode {
+    int rmode, rfirst;
+    float scale;
+};
+ResolveMode resolve_mode(int mode, const pt_render_params* p, bool first, bool last) {
+    if (mode == 2) return {2, (first && p->sample_offset == 0) ? 1 : 0, 1.0f};
+    if (last) return {0, first ? 1 : 0, 1.0f / (float)p->spp};
+    return {1, first ? 1 : 0, 1.0f};
+}
+
+// mode: 0 = pt_render (fb = mean), 2 = pt_render_accumulate (accum (+)= sum); ad: a round of pt_render_adaptive (mode 0);
+// pl: the pixels to trace in place of the selected rows (out_dev is then [n, 3]; n == 0: an empty frame, out_dev may be null)
+int launch_render(pt_scene* S, const pt_render_params* p, float* out_dev, int mode, hipStream_t stream,
+                  const AdaptiveRound* ad = nullptr, const PixelList* pl = nullptr) {
+    RowSel rows;
+    int rc = check_render_args(S, p, out_dev, pl, &rows);
+    if (rc) return rc;
+    DeviceGuard guard;
+    { int grc = guard.enter(S->device); if (grc) return grc; }
+    const bool cont = ad && ad->round > 0;
+    OpenFrame f;
+    if ((rc = open_frame(S, stream, cont, &f))) return rc;
+    pt_scene::FrameSlot& slot = *f.slot;
+    if (rows.count == 0 || (pl && pl->n == 0)) return empty_frame(S, slot, stream);
+
+    const bool listed = pl != nullptr;
+    const uint64_t npix = listed ? (uint64_t)pl->n : (uint64_t)rows.count * (uint64_t)p->width;
+    uint64_t spp_pass;
+    int n_pass;
+    if ((rc = plan_passes(S, p, mode, ad != nullptr, slot, npix, &spp_pass, &n_pass))) return rc;
+
+    const int traversal = p->traversal == PT_TRAVERSAL_DEFAULT ? PT_TRAVERSAL_EXACT : p->traversal;
+    if (traversal != PT_TRAVERSAL_EXACT && traversal != PT_TRAVERSAL_PRUNED) return fail(PT_ERR_INVALID_ARG, "unknown traversal mode");
+    if (p->flags & ~PT_RENDER_NEE) return fail(PT_ERR_INVALID_ARG, "unknown bits in pt_render_params.flags");
+    TraceChoice c;
+    LdsPlan lp;
+    QParams qp{};
+    if ((rc = choose_trace(S, traversal, (p->flags & PT_RENDER_NEE) != 0, listed, &c)) || (rc = plan_trace(S, c, &lp, &qp))) return rc;
+    const TraceEntry e = find_trace(c);
+    if (!e.fn) return fail(PT_ERR_INVALID_ARG, "no kernel variant compiled for these v2_thresh / v2_inner options");
+    int occ;
+    if ((rc = launch_occupancy(S, e.fn, c.block_threads, lp.total, &occ))) return rc;
+    // (a pixel list stays on the caller's stream: its trace kernel reads the caller's memory)
+    const bool own_stream = !ad && !listed && f.in_flight > 1 && n_pass == 1 && f.prev_busy;
+    const int bpc = launch_blocks_per_cu(S, c.lds_scene(), occ, own_stream, f.in_flight);
+    S->info_kernel = c.family;
+    S->info_trace_variant = e.variant;
+    S->info_path_bank = e.bank;
+    S->info_reg_stack = e.reg;
+    S->info_leaf_sweep = c.sweep ? 1 : 0;
     S->info_occupancy = occ;
     S->info_blocks_per_cu = bpc;
     S->info_lds_bytes = lp.total;
-    S->info_lds_scene = lds_scene;
+    S->info_lds_scene = c.lds_scene();
 
-    if (which == 1) {
-        // one global-memory stack column per lane of the LARGEST grid this call launches (pass 0 traces the most samples) for
-        // the reruns (rare: latency does not matter).  Sized from the grid, not from an assumed blocks-per-CU: `blocks_per_cu`
-        // is a caller's option and the kernel indexes the buffer by blockIdx (pt_kernels.h: redo_stk).
-        const size_t lanes = use_q ? (size_t)launch_grid(S->num_cus, bpc, npix * spp_pass, kQBlock) * kQS * 64    // S-waves rerun
-                                   : redo_stack_lanes(S->num_cus, bpc, npix * spp_pass);
-        if ((rc = slot.redo_stack.ensure(lanes * (size_t)S->tree[0].stack_cap))) return rc;
-    }
-    select_tree(S, which, which == 1);
-    float* accum = mode == 2 ? out_dev : S->accum.p;
+    // one global-memory stack column per lane of a grid that reruns segments in reference order (rare: latency does not matter).
+    // Sized from the grid, not from an assumed blocks-per-CU: `blocks_per_cu` is a caller's option and the kernel indexes the
+    // buffer by blockIdx (pt_kernels.h: redo_stk).
+    const auto redo_words = [&](int grid) { return (size_t)grid * (size_t)c.redo_lanes * (size_t)S->tree[0].stack_cap; };
+    // the LARGEST grid this call launches: pass 0 traces the most samples
+    if (c.which == 1 && (rc = slot.redo_stack.ensure(redo_words(launch_grid(S->num_cus, bpc, npix * spp_pass, c.block_threads))))) return rc;
+    select_tree(S, c.which, c.which == 1);
     hipStream_t tstream = stream;
     if (own_stream) {
-        if (!slot.stream) {
-            // A stream of the lowest priority: the runtime maps streams onto a few hardware queues PER PRIORITY (4 by default),
-            // and two streams on one hardware queue run in order.  Among the application's own normal-priority streams the two
-            // slot streams ended up sharing a queue with each other or with the caller's as often as not (one more stream in
-            // the process: 2.70 ms per cbox frame with two slots against 2.69 with one; on queues of their own 2.53 —
-            // profiles/r03_frames_in_flight.log).  Low rather than high: a frame waits for the caller's other GPU work (the
-            // RCCL gather of the rank's rows, N > 1), not the other way round.  PT_SLOT_STREAM_PRIORITY=normal|high: A/B runs.
-            const char* pr = std::getenv("PT_SLOT_STREAM_PRIORITY");
-            const std::string want = pr ? pr : "low";
-            int least = 0, greatest = 0;
-            if (want != "normal" && hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && least != greatest)
-                HIP_TRY(hipStreamCreateWithPriority(&slot.stream, hipStreamNonBlocking, want == "high" ? greatest : least));
-            else
-                HIP_TRY(hipStreamCreateWithFlags(&slot.stream, hipStreamNonBlocking));
-        }
-        if (!slot.in_ev) HIP_TRY(hipEventCreateWithFlags(&slot.in_ev, hipEventDisableTiming));
+        if ((rc = slot_stream(slot))) return rc;
         tstream = slot.stream;
         HIP_TRY(hipEventRecord(slot.in_ev, stream));
     }
@@ -1454,121 +1524,70 @@ int launch_render(pt_scene* S, const pt_render_params* p, float* out_dev, int mo
     for (int pass = 0; pass < n_pass; pass++) {
         const int s0 = pass * (int)spp_pass;
         const int sn = std::min<int>((int)spp_pass, p->spp - s0);
-        RenderDev rd{};
-        std::memcpy(rd.cam_origin, p->cam_origin, 12);
-        std::memcpy(rd.cam_top_left, p->cam_top_left, 12);
-        std::memcpy(rd.cam_horizontal, p->cam_horizontal, 12);
-        std::memcpy(rd.cam_vertical, p->cam_vertical, 12);
-        rd.width = vwidth; rd.height = p->height;
-        rd.row_begin = rows.begin; rd.row_step = rows.step; rd.num_rows = vrows;
-        rd.list = listed ? pl->list : nullptr;
-        rd.img_width = p->width;
-        rd.div_img_width = make_fastdiv((uint32_t)p->width);
-        rd.spp_pass = sn;
-        rd.sample_base = p->sample_offset + s0;
-        rd.stream_stride = p->stream_stride > 0 ? p->stream_stride : p->spp;
-        rd.seed = p->seed;
-        rd.max_depth = p->max_depth > 0 ? p->max_depth : 50;
-        rd.rr_depth = p->rr_depth >= 0 ? p->rr_depth : 5;
-        rd.npix = (uint32_t)npix;
-        rd.total_work = (uint32_t)(npix * (uint64_t)sn);
-        rd.num_regions = S->opt_xcd_regions > 0 ? (int)std::min<int64_t>(S->opt_xcd_regions, 8) : 8;
-        rd.rows_per_region = (vrows + rd.num_regions - 1) / rd.num_regions;
-        rd.div_width = make_fastdiv((uint32_t)vwidth);
-        rd.div_spp = make_fastdiv((uint32_t)sn);
-        rd.row_major = S->opt_item_order == 1 ? 1 : 0;
-        rd.div_npix_full = make_fastdiv((uint32_t)rd.rows_per_region * (uint32_t)vwidth);
-        {   // the band that holds the remainder rows (all bands after it are empty)
-            const int full = vrows / rd.rows_per_region, rest = vrows - full * rd.rows_per_region;
-            rd.short_region = rest ? full : -1;
-            rd.div_npix_last = make_fastdiv((uint32_t)std::max(rest, 1) * (uint32_t)vwidth);
-        }
-
-        const int grid = launch_grid(S->num_cus, bpc, rd.total_work, block_threads);
-        if (which == 1 && (size_t)grid * (use_q ? kQS * 64 : kBlock) * (size_t)S->tree[0].stack_cap > slot.redo_stack.n)
+        const int grid = launch_grid(S->num_cus, bpc, npix * (uint64_t)sn, c.block_threads);
+        if (c.which == 1 && redo_words(grid) > slot.redo_stack.n)
             return fail(PT_ERR_DEVICE, "internal error: rerun stacks smaller than the grid");
         S->info_grid = grid;
-        // chunk: work items a wave reserves per atomic.  Big launches (a wave traces >= 2048 items): 128 — the waves of a
-        // launch run dry within two paths' time of each other instead of four (cbox -1.9 %, bunny -0.9 % against 256; 64
-        // buys nothing more and saturates the counters on cheap scenes: profiles/r02_tune_round36_*.log); mid-size
-        // launches 256; small launches (interactive 1-2 spp frames) down to 64 so that the items are spread over all
-        // resident waves instead of the first total/256 of them
-        const uint64_t per_wave = rd.total_work / ((uint64_t)grid * (use_q ? kQS : kBlock / 64));     // waves that draw from the feed
-        rd.chunk = per_wave >= 2048 ? 128u
-                 : per_wave >= 4 * kMaxChunk ? kMaxChunk : (uint32_t)std::max<uint64_t>(64, std::min<uint64_t>(kMaxChunk, (per_wave / 64) * 64));
-        if (S->opt_chunk > 0) rd.chunk = (uint32_t)std::min<int64_t>(kMaxChunk, std::max<int64_t>(64, (S->opt_chunk / 64) * 64));
+        const RenderDev rd = pass_render_dev(S, p, rows, pl, s0, sn, (uint64_t)grid * (uint64_t)c.feed_waves);
 
-        const size_t ev_pass = pass_base + (size_t)pass;
-        if (timing && frec.ev.size() <= ev_pass) {
-            pt_scene::PassEvents fresh{};
-            hipError_t ee = hipEventCreate(&fresh.t0);
-            if (ee == hipSuccess && (ee = hipEventCreate(&fresh.t1)) != hipSuccess) (void)hipEventDestroy(fresh.t0);
-            if (ee == hipSuccess && (ee = hipEventCreate(&fresh.r0)) != hipSuccess) { (void)hipEventDestroy(fresh.t0); (void)hipEventDestroy(fresh.t1); }
-            if (ee == hipSuccess && (ee = hipEventCreate(&fresh.r1)) != hipSuccess) { (void)hipEventDestroy(fresh.t0); (void)hipEventDestroy(fresh.t1); (void)hipEventDestroy(fresh.r0); }
-            if (ee != hipSuccess) return fail(PT_ERR_DEVICE, std::string("hipEventCreate: ") + hipGetErrorString(ee));
-            frec.ev.push_back(fresh);
-        }
-        const pt_scene::PassEvents pe = timing ? frec.ev[ev_pass] : pt_scene::PassEvents{};
+        const size_t ev_pass = f.pass_base + (size_t)pass;
+        if (f.timing && (rc = pass_events(*f.rec, ev_pass))) return rc;
+        const pt_scene::PassEvents pe = f.timing ? f.rec->ev[ev_pass] : pt_scene::PassEvents{};
         if (pass > 0) HIP_TRY(hipMemsetAsync(slot.ctl.p, 0, kWorkBytes, tstream));
-        if (timing) HIP_TRY(hipEventRecord(pe.t0, tstream));
-        if (use_q)
-            hipLaunchKernelGGL(fnq, dim3(grid), dim3(kQBlock), lp.total, tstream, S->dev, rd, lp, qp, slot.samples.p,
-                               S->work_counter(), S->counters());
-        else if (fns)
-            hipLaunchKernelGGL(fns, dim3(grid), dim3(kBlock), lp.total, tstream, S->dev, rd, lp, slot.samples.p,
-                               S->work_counter(), S->counters(), SweepLayoutDev{S->sweep_tab.p, S->sweep.count, 0u});
-        else
-            hipLaunchKernelGGL(fn, dim3(grid), dim3(kBlock), lp.total, tstream, S->dev, rd, lp, slot.samples.p,
-                               S->work_counter(), S->counters());
+        if (f.timing) HIP_TRY(hipEventRecord(pe.t0, tstream));
+        launch_trace(S, c, e, grid, tstream, rd, lp, qp, slot.samples.p);
         HIP_TRY(hipGetLastError());
-        if (timing) HIP_TRY(hipEventRecord(pe.t1, tstream));
+        if (f.timing) HIP_TRY(hipEventRecord(pe.t1, tstream));
         if (own_stream) HIP_TRY(hipStreamWaitEvent(tstream, slot.in_ev, 0));   // the resolve writes the caller's buffer
-        if (timing) HIP_TRY(hipEventRecord(pe.r0, tstream));
+        if (f.timing) HIP_TRY(hipEventRecord(pe.r0, tstream));
 
         const bool first = pass == 0, last = pass == n_pass - 1;
-        int rmode;
-        float scale = 1.0f;
-        int rfirst;
-        if (mode == 2) {
-            // progressive: every pass adds its own partial sum; first only if sample_offset==0 and pass 0
-            rmode = 2;
-            rfirst = (first && p->sample_offset == 0) ? 1 : 0;
-        } else if (last) {
-            rmode = 0; rfirst = first ? 1 : 0; scale = 1.0f / (float)p->spp;
-        } else {
-            rmode = 1; rfirst = first ? 1 : 0;
-        }
+        const unsigned rblocks = (unsigned)((npix + 255) / 256);
         if (ad) {
             AdaptiveArgs aa = ad->args;
             aa.n = (uint32_t)npix;
             aa.spp_pass = sn;
             aa.first = ad->round == 0 && first;
             aa.check = last;
-            hipLaunchKernelGGL(adaptive_resolve_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, tstream, slot.samples.p, aa);
+            hipLaunchKernelGGL(adaptive_resolve_kernel, dim3(rblocks), dim3(256), 0, tstream, slot.samples.p, aa);
         } else {
-            hipLaunchKernelGGL(resolve_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, tstream, slot.samples.p, accum,
-                               out_dev, (uint32_t)npix, sn, rmode, rfirst, scale);
+            const ResolveMode r = resolve_mode(mode, p, first, last);
+            hipLaunchKernelGGL(resolve_kernel, dim3(rblocks), dim3(256), 0, tstream, slot.samples.p, mode == 2 ? out_dev : S->accum.p,
+                               out_dev, (uint32_t)npix, sn, r.rmode, r.rfirst, r.scale);
         }
         HIP_TRY(hipGetLastError());
-        if (timing) HIP_TRY(hipEventRecord(pe.r1, tstream));
+        if (f.timing) HIP_TRY(hipEventRecord(pe.r1, tstream));
         HIP_TRY(hipEventRecord(slot.free_ev, tstream));
         slot.used = true; slot.free_stream = tstream;
         if (own_stream) HIP_TRY(hipStreamWaitEvent(stream, slot.free_ev, 0));
         S->info_passes++;
-        if (timing) frec.passes = ev_pass + 1;
+        if (f.timing) f.rec->passes = ev_pass + 1;
     }
-    S->have_timing = timing;
+    S->have_timing = f.timing;
     return PT_OK;
 }
 
+// The frame's counters, summed over the counter slots, once its stream has drained; zeros where the handle has no control block
+// yet.  Enters the handle's device under the caller's guard.
+int synced_slot_sums(pt_scene* S, DeviceGuard& guard, unsigned long long* c) {
+    { int grc = guard.enter(S->device); if (grc) return grc; }
+    HIP_TRY(hipStreamSynchronize(S->last_stream));
+    std::fill(c, c + kSlotStride, 0ull);
+    return S->cur().ctl.p ? read_slot_sums(S, c) : PT_OK;
+}
+
 // trace_kernel_q bounds every wait on its rings; a wait that ran into its bound leaves a mark in counter slot 15 and an
-// invalid frame behind.  (The stream has been synchronised.)
+// invalid frame behind.  c: the frame's slot sums.
+int schedule_error(const pt_scene* S, const unsigned long long* c) {
+    if (S->info_kernel != 3 || !c[15]) return PT_OK;
+    return fail(PT_ERR_DEVICE, "trace_kernel_q: schedule error, frame invalid (bits " + std::to_string(c[15]) + ": 1 bounded wait ran out, 2 ring entry corrupted, 4 impossible path state)");
+}
+// (The stream has been synchronised.)
 int check_schedule_error(const pt_scene* S) {
     if (S->info_kernel != 3 || !S->cur().ctl.p) return PT_OK;
     unsigned long long c[kSlotStride];
     int rc = read_slot_sums(S, c);
-    if (rc) return rc;
-    return c[15] ? fail(PT_ERR_DEVICE, "trace_kernel_q: schedule error, frame invalid (bits " + std::to_string(c[15]) + ": 1 bounded wait ran out, 2 ring entry corrupted, 4 impossible path state)") : PT_OK;
+    return rc ? rc : schedule_error(S, c);
 }
 
 // HIP-event times of one recorded render call, summed over its sample passes (the events must have completed).
@@ -2411,14 +2430,11 @@ int pt_get_counters(pt_scene* S, pt_counters* out) {
     if (!S || !out) return fail(PT_ERR_INVALID_ARG, "null argument");
     std::memset(out, 0, sizeof *out);
     DeviceGuard guard;
-    { int grc = guard.enter(S->device); if (grc) return grc; }
-    HIP_TRY(hipStreamSynchronize(S->last_stream));
-    if (!S->cur().ctl.p) return PT_OK;
     unsigned long long c[kSlotStride];
-    int rc = read_slot_sums(S, c);
-    if (rc) return rc;
+    int rc = synced_slot_sums(S, guard, c);
+    if (rc || !S->cur().ctl.p) return rc;
     out->paths = c[0]; out->segments = c[1]; out->node_visits = c[2]; out->leaf_tests = c[3];
-    if (S->info_kernel == 3 && c[15]) return fail(PT_ERR_DEVICE, "trace_kernel_q: schedule error, frame invalid (bits " + std::to_string(c[15]) + ": 1 bounded wait ran out, 2 ring entry corrupted, 4 impossible path state)");
+    if ((rc = schedule_error(S, c))) return rc;
     if (S->have_timing && S->last_frame()) {
         int rc2 = frame_times(*S->last_frame(), &out->kernel_ms, &out->resolve_ms);
         if (rc2) return rc2;
@@ -2485,34 +2501,36 @@ int pt_scene_set_option(pt_scene* S, const char* key, int64_t value) {
 int pt_scene_get_info(pt_scene* S, const char* key, int64_t* value) {
     if (!S || !key || !value) return fail(PT_ERR_INVALID_ARG, "null argument");
     const std::string k(key);
+    // what the next plain render decides (exact unless the key says pruned; without NEE or a pixel list, so it cannot fail)
+    TraceChoice next;
+    (void)choose_trace(S, k == "vgprs_pruned" ? PT_TRAVERSAL_PRUNED : PT_TRAVERSAL_EXACT, false, false, &next);
+    DeviceGuard guard;
+    unsigned long long c[kSlotStride];
     if (k == "grid") *value = S->info_grid;
     else if (k == "lds_bytes") *value = S->info_lds_bytes;
     else if (k == "lds_scene") *value = S->info_lds_scene;
-    else if (k == "residency") *value = scene_residency(S, which_tree(S));
+    else if (k == "residency") *value = next.res;
     else if (k == "passes") *value = S->info_passes;
     else if (k == "adaptive_rounds") *value = S->info_adaptive_rounds;
     else if (k == "occupancy") *value = S->info_occupancy;                // what the occupancy query allows
     else if (k == "blocks_per_cu") *value = S->info_blocks_per_cu;        // what the last launch used
     else if (k == "redo_segments") {                                     // STATS: segments rerun in reference order by the last render
-        DeviceGuard guard;
-        { int grc = guard.enter(S->device); if (grc) return grc; }
-        HIP_TRY(hipStreamSynchronize(S->last_stream));
-        unsigned long long c[kSlotStride] = {0};
-        if (S->cur().ctl.p) { int rc = read_slot_sums(S, c); if (rc) return rc; }
+        int rc = synced_slot_sums(S, guard, c);
+        if (rc) return rc;
         *value = (int64_t)c[12];
     }
     else if (k == "num_cus") *value = S->num_cus;
     else if (k == "bvh_depth") *value = S->tree[0].depth;
-    else if (k == "stack_entries") *value = S->tree[which_tree(S)].stack_cap;   // per lane, sentinel included
+    else if (k == "stack_entries") *value = S->tree[next.which].stack_cap;   // per lane, sentinel included
     else if (k == "fast_tree") *value = S->have_fast ? 1 : 0;             // an internal tree exists (the caller's tree is nested)
     else if (k == "debug_reruns") *value = S->info_debug_reruns;          // rays the last pt_debug_intersect reran in reference order
     else if (k == "fast_tree_cost_permille") *value = S->fast_cost_permille;   // summed inner-box area, internal tree / caller's tree x 1000 (0: none built)
     else if (k == "fast_tree_is_callers") *value = (S->have_fast && S->fast_is_callers_topology) ? 1 : 0;
-    else if (k == "fast_tree_on") *value = which_tree(S);    // ... and the next exact render traverses it
+    else if (k == "fast_tree_on") *value = next.which;       // ... and the next exact render traverses it
     else if (k == "fast_tree_depth") *value = S->have_fast ? S->tree[1].depth : 0;
     else if (k == "scene_bytes") *value = S->scene_bytes;
     else if (k == "num_inner_nodes") *value = S->tree[0].num_nodes;
-    else if (k == "top_nodes") { const int w = which_tree(S); *value = make_plan(S, scene_residency(S, w), false, w).top_count; }
+    else if (k == "top_nodes") *value = make_plan(S, next).top_count;     // make_plan's count even on kernel 3, whose make_plan_q caches another
     else if (k == "device") *value = S->device;
     else if (k == "sweep_on_device") *value = S->sweep_on_device;         // the internal tree was built on the GPU (pt_sweep_build.hip)
     else if (k.rfind("create_us", 0) == 0 && k.size() == 10 && k[9] >= '0' && k[9] <= '6') *value = S->create_us[k[9] - '0'];
@@ -2536,43 +2554,31 @@ int pt_scene_get_info(pt_scene* S, const char* key, int64_t* value) {
     else if (k.rfind("qdiag", 0) == 0 && k.size() >= 6 && k.size() <= 7 && k.find_first_not_of("0123456789", 5) == std::string::npos &&
              std::stoi(k.substr(5)) < 11) {
         // schedule diagnostics of the last STATS render of trace_kernel_q: counter slots [4..14], see pt_kernel_q.h
-        DeviceGuard guard;
-        { int grc = guard.enter(S->device); if (grc) return grc; }
-        HIP_TRY(hipStreamSynchronize(S->last_stream));
-        unsigned long long c[kSlotStride] = {0};
-        if (S->cur().ctl.p) { int rc = read_slot_sums(S, c); if (rc) return rc; }
+        int rc = synced_slot_sums(S, guard, c);
+        if (rc) return rc;
         *value = (int64_t)c[4 + std::stoi(k.substr(5))];
     }
     else if (k.rfind("diag", 0) == 0 && k.size() >= 5 && k.size() <= 7 && k.find_first_not_of("0123456789", 4) == std::string::npos &&
              std::stoi(k.substr(4)) < 8 + kNumCounters - kTimelineBase) {
         // schedule diagnostics / launch timeline of the last STATS render (trace_kernel_v2): see pt_kernels.h
-        DeviceGuard guard;
-        { int grc = guard.enter(S->device); if (grc) return grc; }
-        HIP_TRY(hipStreamSynchronize(S->last_stream));
         unsigned long long v = 0;
         const int idx = std::stoi(k.substr(4));
-        if (S->cur().ctl.p && idx < 8) {                  // schedule diagnostics: summed over the counter slots
-            unsigned long long c[kSlotStride];
-            int rc = read_slot_sums(S, c);
+        if (idx < 8) {                                    // schedule diagnostics: summed over the counter slots
+            int rc = synced_slot_sums(S, guard, c);
             if (rc) return rc;
             v = c[4 + idx];
-        } else if (S->cur().ctl.p) {                      // launch timeline / histograms
-            HIP_TRY(hipMemcpy(&v, S->counters() + kTimelineBase + (idx - 8), sizeof v, hipMemcpyDeviceToHost));
+        } else {                                          // launch timeline / histograms
+            { int grc = guard.enter(S->device); if (grc) return grc; }
+            HIP_TRY(hipStreamSynchronize(S->last_stream));
+            if (S->cur().ctl.p) HIP_TRY(hipMemcpy(&v, S->counters() + kTimelineBase + (idx - 8), sizeof v, hipMemcpyDeviceToHost));
         }
         *value = (int64_t)v;
     }
     else if (k == "vgprs" || k == "vgprs_pruned") {
+        // of the next render without NEE or a pixel list; a launch that would take the sweep kernel reports the entry it stands in for
         hipFuncAttributes fa;
-        const int w = which_tree(S);
-        const int res = scene_residency(S, w);
-        const void* f;
-        if (S->opt_kernel == 3 && k == "vgprs") {
-            f = reinterpret_cast<const void*>(pick_kernel_q(S, res, w == 1).fn);
-        } else {
-            TraceFn fn = pick_kernel(S, res, k == "vgprs_pruned", S->opt_stats != 0, w == 1, launch_reg_stack(S, res, w, false, false, false)).fn;
-            if (!fn) return fail(PT_ERR_INVALID_ARG, "no such kernel variant");
-            f = reinterpret_cast<const void*>(fn);
-        }
+        const void* f = find_trace(next, false).fn;
+        if (!f) return fail(PT_ERR_INVALID_ARG, "no such kernel variant");
         HIP_TRY(hipFuncGetAttributes(&fa, f));
         *value = fa.numRegs;
     } else return fail(PT_ERR_INVALID_ARG, "unknown info key " + k);

@@ -1,9 +1,11 @@
 """Every trace-kernel instantiation compiled into libpt_hip.so, launched once and checked against the CPU oracle.
 
 The compiled set is read from the library's gfx950 code object (tests/trace_variants.py).  A planner maps each instantiation
-to the scene, options, traversal and entry point that make the pick functions of csrc/pt_api.hip launch it; info
-"trace_variant" confirms that they did.  The CPU test fails when an instantiation exists that the planner cannot reach."""
+to the scene, options, traversal and entry point that make choose_trace / find_trace of csrc/pt_api.hip launch it; info
+"trace_variant" confirms that they did.  The CPU tests fail when an instantiation exists that the planner cannot reach, or
+when the compiled set is not the one listed in tests/golden/trace_kernels.txt."""
 import ctypes as C
+import os
 from collections import Counter
 
 import numpy as np
@@ -20,7 +22,7 @@ TINY, BIG = 32, 320        # primitives: 8 octant tables of 31 inner nodes fit 2
 
 OPTION_DEFAULTS = {"kernel": 2, "force_global": 0, "octants": 1, "top_cache": 1, "fast_tree": 1, "specialize": 1, "stats": 0,
                    "v2_thresh": 0, "v2_inner": 0, "v2_minw": 0}
-# the automatic (v2_thresh, v2_inner) of kernel 2 by residency and tree (pick_kernel), and of NEE kernels (pick_kernel_nee)
+# the automatic (v2_thresh, v2_inner) of kernel 2 by residency and tree, and of NEE kernels (choose_trace / v2_schedule)
 AUTO_SCHEDULE = {0: {"internal": (32, 1231), "callers": (32, 4)}, 3: {"internal": (32, 1231), "callers": (32, 4)},
                  1: {"internal": (40, 162), "callers": (40, 162)}, 2: {"internal": (40, 162), "callers": (40, 162)}}
 NEE_SCHEDULE = {0: (32, 4), 3: (32, 4), 1: (40, 162), 2: (40, 162)}
@@ -122,6 +124,29 @@ def test_every_compiled_trace_kernel_is_reachable():
     fam = Counter(v.family for v in variants)
     print(f"{len(variants)} trace-kernel instantiations compiled: trace_kernel {fam[1]}, trace_kernel_v2 {fam[2]}, "
           f"trace_kernel_q {fam[3]}")
+
+
+# tests/golden/trace_kernels.txt: the sorted mangled names of every kernel of the gfx950 code objects whose name contains
+# "trace_kernel".  The matrix above and below iterates over what is compiled, so only this list notices an instantiation that
+# the dispatcher of csrc/pt_api.hip stopped naming (or names in addition).  A pull request that adds or removes a kernel on
+# purpose regenerates it from its own build:
+#   python -c "import sys; sys.path.insert(0, 'tests'); from trace_variants import code_object_symbols as s;
+#              from pathtracer_cuda_interactive_amd import _build as b;
+#              print('\n'.join(sorted(n for co in s(b.HIP_LIB) for n in co if 'trace_kernel' in n)))" > tests/golden/trace_kernels.txt
+def test_compiled_trace_kernels_are_the_listed_set():
+    from trace_variants import code_object_symbols
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "trace_kernels.txt")) as f:
+        listed = f.read().split()
+    assert listed == sorted(set(listed)), "tests/golden/trace_kernels.txt is not a sorted list of distinct names"
+    built = [n for co in code_object_symbols(_build.HIP_LIB) for n in co if "trace_kernel" in n]
+    missing, extra = sorted(set(listed) - set(built)), sorted(set(built) - set(listed))
+    print(f"{len(built)} trace kernels built, {len(listed)} listed; missing {len(missing)}, extra {len(extra)}")
+    for name in missing:
+        print("missing:", name)
+    for name in extra:
+        print("extra:", name)
+    assert not missing and not extra, f"{len(missing)} listed kernels are not built, {len(extra)} built kernels are not listed"
+    assert len(built) == len(listed), "a trace kernel is compiled into more than one code object"
 
 
 # ---- GPU --------------------------------------------------------------------------------------------------------------
@@ -283,6 +308,30 @@ def test_every_compiled_trace_kernel_matches_the_oracle(oracle):
     print(f"trace-kernel matrix: {len(set(compiled) & ran)}/{len(compiled)} compiled instantiations ran")
     assert not failures, f"{len(failures)} instantiations failed:\n" + "\n".join(failures)
     assert not missing, "never launched:\n" + "\n".join(map(str, missing))
+
+
+@pytest.mark.gpu
+def test_a_schedule_without_a_kernel_fails_and_leaves_the_handle_as_it_was():
+    """v2_thresh names an instantiation; 41 names none: the render fails with PT_ERR_INVALID_ARG, and once the option is back
+    at 0 the handle renders the same bits with the same kernel as before the failure."""
+    from pathtracer_cuda_interactive_amd import PT_ERR_INVALID_ARG, PtError
+    from pathtracer_cuda_interactive_amd import device as dev
+    hs, d = _make_scene("tiny", "diffuse")
+    p = hs.render_params(W, H, SPP, seed=97)
+    ds = dev.DeviceScene(d)
+    try:
+        before, variant = ds.render(p), ds.info("trace_variant")
+        assert Variant.decode(variant).family == 2
+        ds.set_option("v2_thresh", 41)
+        with pytest.raises(PtError) as e:
+            ds.render(p)
+        assert e.value.status == PT_ERR_INVALID_ARG
+        assert "no kernel variant compiled for these v2_thresh / v2_inner options" in str(e.value)
+        ds.set_option("v2_thresh", 0)
+        assert_bit_equal(ds.render(p), before, "the frame after the failed render")
+        assert ds.info("trace_variant") == variant
+    finally:
+        ds.close()
 
 
 def _with_spp(p, spp, traversal=None):

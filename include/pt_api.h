@@ -215,6 +215,52 @@ int pt_scene_destroy(pt_scene* scene);
 enum { PT_UPDATE_GEOMETRY = 1, PT_UPDATE_SHADING = 2 };
 int pt_scene_update(pt_scene* scene, const pt_scene_desc* desc, int flags);
 
+/* Rigid animation by one matrix per group of shapes, on the device — an EXTENSION, like pt_scene_update: off unless called, never
+ * part of a parity or roofline number.  The handle holds its geometry as primitive records already; a caller whose objects only
+ * move uploads 84 bytes per object instead of every vertex.
+ *   pt_scene_set_groups  group_of_shape[num_shapes], every value in [-1, num_groups); -1 = the shape never moves, its record is
+ *                        copied bit for bit.  0 <= num_groups <= 2^20.  Uploads the ids (4 bytes per shape), replaces an earlier
+ *                        assignment and does not touch the geometry.  An id out of range: PT_ERR_INVALID_ARG, pt_last_error()
+ *                        names group_of_shape[k]; the earlier assignment stays.
+ *   pt_scene_transform   transforms[num_groups]; num_groups must be the assignment's, and there must be one (PT_ERR_INVALID_ARG).
+ *                        Transforms are ABSOLUTE: they apply to the REST geometry — the records that were live after
+ *                        pt_scene_create or after the last successful pt_scene_update(PT_UPDATE_GEOMETRY) —, which the handle
+ *                        copies device-to-device into buffers of its own on the first transform after either of those (96 bytes
+ *                        per shape, freed with the scene; a geometry update drops the copy).  Repeated calls never accumulate
+ *                        rounding.
+ * The rule (csrc/pt_transform.h), fp32, operations in the order written, no contraction, cross and dot as at pt_render_guides:
+ *   rows r0 = (m0,m1,m2), r1 = (m4,m5,m6), r2 = (m8,m9,m10).
+ *   point   x' = ((m0 x + m1 y) + m2 z) + m3, rows 1 and 2 alike.
+ *   normal  c0 = cross(r1,r2), c1 = cross(r2,r0), c2 = cross(r0,r1); det = dot(r0,c0); det < 0 negates all nine entries;
+ *           n'.x = (c0.x nx + c0.y ny) + c0.z nz, the other components alike.  Not renormalised: shading normalises after
+ *           interpolation.  Made once per group on the host; 21 floats per group go to the device.
+ *           det == 0, a NaN det or any m[i] that is not finite: PT_ERR_INVALID_ARG naming transforms[g], before anything changes.
+ *           A cofactor that overflowed (a uniform scale beyond about 1e19): PT_ERR_UNSUPPORTED naming transforms[g], likewise.
+ *   sphere  the centre as a point; r' = r * sqrt((m0 m0 + m4 m4) + m8 m8), sqrt correctly rounded.  The linear part is expected
+ *           to be a similarity; the library does not check that.
+ *   triangle  the nine corner coordinates and the nine normal components of its record; material, light and padding are copied.
+ *   A RESULT that is not finite is caught as in pt_scene_update: PT_ERR_UNSUPPORTED, the handle unchanged.
+ * Blocking, on the default stream, with pt_scene_update's two synchronises.  A call that fails leaves the handle exactly as it
+ * was: the new records and leaf boxes are made and checked in the staging buffers pt_scene_update uses.  On success the record
+ * buffers rotate as they do there (staging -> current -> previous): "prev_geometry" becomes 1 and PT_MOTION_GEOMETRY_PREVIOUS
+ * sees the records from before this call.  Everything pt_scene_update documents about the result holds: topology kept, exact
+ * boxes, the box sweep of small scenes dropped for the tree, the 256-level limit, the plan build on the first call.  The handle
+ * then renders, bit for bit and through every entry point, what pt_scene_update(PT_UPDATE_GEOMETRY) renders when given the desc
+ * that the two host functions below produce from the rest desc.
+ *   pt_scene_get_info: "groups" = groups of the assignment (0: none); "rest_geometry" = 1 while a copy of the rest records is
+ *   held; "transforms" = successful pt_scene_transform calls so far; "transform_us0".."transform_us3" = wall microseconds of the
+ *   last one: total, records (table upload and the kernel's enqueue), refit, and the one-time copy of the rest records plus the
+ *   plan build (0 when neither was due).
+ * pt_transform_geometry_host / pt_transform_sphere_host: the same source compiled for the HOST; they need no GPU and no scene.
+ * positions, normals, positions_out, normals_out: [n, 3] each; normals and normals_out may both be NULL; an output may be its
+ * input.  A transform the rule refuses: the status pt_scene_transform gives it; a NULL argument otherwise: PT_ERR_INVALID_ARG. */
+typedef struct pt_transform { float m[12]; } pt_transform;   /* row-major 3x4: x' = m[0]x + m[1]y + m[2]z + m[3], ... */   /* 48 bytes */
+int pt_scene_set_groups(pt_scene* scene, const int32_t* group_of_shape, int32_t num_groups);
+int pt_scene_transform(pt_scene* scene, const pt_transform* transforms, int32_t num_groups);
+int pt_transform_geometry_host(const pt_transform* t, int32_t n, const float* positions, const float* normals,
+                               float* positions_out, float* normals_out);
+int pt_transform_sphere_host(const pt_transform* t, const float* center, float radius, float* center_out, float* radius_out);
+
 /* Blocking render.  `fb` receives rows x width x 3 floats, rows = the rows
  * selected by (row_begin,row_end,row_stride), packed in increasing row order;
  * fb[(r*W+i)*3+c], linear radiance, row 0 = top (main.cu:35,50).

@@ -26,6 +26,8 @@
 #include "pt_sweep_build.h"
 #include "pt_scene_prep.h"
 #include "pt_scene_refit.h"
+#include "pt_scene_transform.h"
+#include "pt_transform.h"
 #include "pt_denoise.h"
 #include "pt_gradient.h"
 #include "pt_temporal.h"
@@ -188,6 +190,16 @@ struct pt_scene {
     DevBuf<unsigned int> st_status;
     ptf::Plan refit_plan[2];
     int64_t updates = 0, update_us[4] = {0, 0, 0, 0};   // [0] total [1] records + uploads [2] refit + octant tables [3] plan build
+    // pt_scene_transform: the group of every shape and the table of group entries (pt_transform.h); the REST records, a copy of
+    // prims / normals made on the first transform after pt_scene_create or a geometry update, which every transform starts from
+    DevBuf<int32_t> group_of;
+    DevBuf<float> group_tab;
+    int32_t num_groups = 0;
+    bool have_groups = false;
+    DevBuf<DPrim> rest_prims;
+    DevBuf<DNormals> rest_normals;
+    bool have_rest = false;
+    int64_t transforms = 0, transform_us[4] = {0, 0, 0, 0};   // [0] total [1] records [2] refit [3] snapshot + plan build
     bool tri_only = false;           // the scene holds no sphere
     bool diffuse_only = false;       // every material is DIFFUSE
     // scratch
@@ -1606,6 +1618,65 @@ int frame_times(const pt_scene::FrameRec& f, double* kernel_ms, double* resolve_
 }
 
 
+// The staging buffers of a geometry change: new records and vertex normals, the buffer the live records retire into, the status word.
+int ensure_staging(pt_scene* S) {
+    const size_t N = (size_t)S->dev.num_prims;
+    int rc;
+    if ((rc = S->st_prims.ensure(N)) || (rc = S->prev_prims.ensure(N)) || (rc = S->st_normals.ensure(N)) || (rc = S->st_status.ensure(1)))
+        return rc;
+    return PT_OK;
+}
+
+// What pt_scene_update and pt_scene_transform do once new records stand in st_prims / st_normals: the refit plans where none
+// exist yet, leaf boxes and the status read-back, both trees refitted, and only then the handle changes — the three record
+// buffers rotate (staging -> current -> previous) and the box sweep is dropped.  `who` heads the messages.  *us_plan: wall
+// microseconds of the plan build (left alone where none was due); *us_refit: of everything after it.
+int adopt_staged(pt_scene* S, const char* who, bool tri_only, int64_t* us_plan, int64_t* us_refit) {
+    using clk = std::chrono::steady_clock;
+    auto us_since = [](clk::time_point t0) { return (int64_t)std::chrono::duration_cast<std::chrono::microseconds>(clk::now() - t0).count(); };
+    const int N = S->dev.num_prims;
+    int rc;
+    clk::time_point t_stage = clk::now();
+    const int n_trees = N > 1 ? (S->have_fast ? 2 : 1) : 0;   // one shape: a dummy node, the root is never box-tested
+    bool whole = true, planned = false;
+    for (int t = 0; t < n_trees; t++) {
+        ptf::Plan& pl = S->refit_plan[t];
+        if (!pl.built) {
+            if ((rc = ptf::plan_build(S->tree[t].nodes.p, S->tree[t].num_nodes, N, &pl))) return rc;
+            planned = true;
+        }
+        whole = whole && pl.whole_tree;
+        // octant tables are made by the single-workgroup launch alone; they exist only for trees far smaller than its reach
+        if (S->tree[t].have_oct && !pl.whole_tree) return fail(PT_ERR_UNSUPPORTED, std::string(who) + ": octant tables on a tree of wide levels");
+    }
+    if (planned) { *us_plan = std::max<int64_t>(us_since(t_stage), 1); t_stage = clk::now(); }
+    HIP_TRY(hipMemsetAsync(S->st_status.p, 0, sizeof(unsigned int), nullptr));
+    unsigned int bad = 0;
+    if (!whole || n_trees == 0) {
+        // the leaf boxes, checked before any node array is written (a tree done by one launch checks for itself)
+        if ((rc = S->st_boxes.ensure((size_t)N * 6)) || (rc = ptf::leaf_boxes(S->st_prims.p, N, S->st_boxes.p, S->st_status.p))) return rc;
+        HIP_TRY(hipMemcpy(&bad, S->st_status.p, sizeof bad, hipMemcpyDeviceToHost));
+    }
+    for (int t = 0; t < n_trees && !bad; t++) {
+        pt_scene::Tree& T = S->tree[t];
+        if ((rc = ptf::refit_tree(S->refit_plan[t], T.nodes.p, T.have_oct ? T.nodes_oct.p : nullptr, T.num_nodes, S->st_prims.p,
+                                  whole ? nullptr : S->st_boxes.p, N, S->st_status.p)))
+            return rc;
+    }
+    if (whole && n_trees) HIP_TRY(hipMemcpy(&bad, S->st_status.p, sizeof bad, hipMemcpyDeviceToHost));
+    if (bad) return fail(PT_ERR_UNSUPPORTED, std::string(who) + ": a new coordinate, radius or leaf box is not finite");
+    std::swap(S->prev_prims.p, S->st_prims.p); std::swap(S->prev_prims.n, S->st_prims.n);   // the new records, for a moment
+    std::swap(S->prims.p, S->prev_prims.p); std::swap(S->prims.n, S->prev_prims.n);         // current -> previous, new -> current
+    S->have_prev = true;
+    std::swap(S->normals.p, S->st_normals.p); std::swap(S->normals.n, S->st_normals.n);
+    S->dev.prims = S->prims.p; S->dev.normals = S->normals.p;
+    S->tri_only = tri_only;
+    S->sweep_groups = 0; S->sweep.count = 0;     // leaf boxes that were equal need not be any more: back to the tree
+    S->sweep_tab.release();                      // (no frame is in flight: the update synchronised before it wrote)
+    *us_refit = us_since(t_stage);
+    return PT_OK;
+}
+
 // pt_scene_update (include/pt_api.h).  Order of events: everything that can be refused is made and checked first — argument
 // counts and the desc on the host, primitive records and leaf boxes in staging memory on the device — and only then does the
 // handle change: node arrays written, record buffers traded, shading tables overwritten.
@@ -1638,52 +1709,15 @@ int update_scene(pt_scene* S, const pt_scene_desc* d, int flags) {
     const clk::time_point t_all = clk::now();
     int64_t us_records = 0, us_refit = 0, us_plan = 0;
     if (geometry) {
-        clk::time_point t_stage = clk::now();
+        const clk::time_point t_stage = clk::now();
         pt_scene_desc dg = *d;                                // material ids are checked against the handle's table
         dg.num_materials = S->dev.num_materials;
         int has_sphere = 0;
-        if ((rc = S->st_prims.ensure((size_t)N)) || (rc = S->prev_prims.ensure((size_t)N)) || (rc = S->st_normals.ensure((size_t)N)) ||
-            (rc = S->st_status.ensure(1)))
-            return rc;
+        if ((rc = ensure_staging(S))) return rc;
         if ((rc = ptp::prims_device(&dg, S->st_prims.p, S->st_normals.p, &has_sphere))) return rc;
-        us_records = us_since(t_stage); t_stage = clk::now();
-        const int n_trees = N > 1 ? (S->have_fast ? 2 : 1) : 0;   // one shape: a dummy node, the root is never box-tested
-        bool whole = true, planned = false;
-        for (int t = 0; t < n_trees; t++) {
-            ptf::Plan& pl = S->refit_plan[t];
-            if (!pl.built) {
-                if ((rc = ptf::plan_build(S->tree[t].nodes.p, S->tree[t].num_nodes, N, &pl))) return rc;
-                planned = true;
-            }
-            whole = whole && pl.whole_tree;
-            // octant tables are made by the single-workgroup launch alone; they exist only for trees far smaller than its reach
-            if (S->tree[t].have_oct && !pl.whole_tree) return fail(PT_ERR_UNSUPPORTED, "pt_scene_update: octant tables on a tree of wide levels");
-        }
-        if (planned) { us_plan = std::max<int64_t>(us_since(t_stage), 1); t_stage = clk::now(); }
-        HIP_TRY(hipMemsetAsync(S->st_status.p, 0, sizeof(unsigned int), nullptr));
-        unsigned int bad = 0;
-        if (!whole || n_trees == 0) {
-            // the leaf boxes, checked before any node array is written (a tree done by one launch checks for itself)
-            if ((rc = S->st_boxes.ensure((size_t)N * 6)) || (rc = ptf::leaf_boxes(S->st_prims.p, N, S->st_boxes.p, S->st_status.p))) return rc;
-            HIP_TRY(hipMemcpy(&bad, S->st_status.p, sizeof bad, hipMemcpyDeviceToHost));
-        }
-        for (int t = 0; t < n_trees && !bad; t++) {
-            pt_scene::Tree& T = S->tree[t];
-            if ((rc = ptf::refit_tree(S->refit_plan[t], T.nodes.p, T.have_oct ? T.nodes_oct.p : nullptr, T.num_nodes, S->st_prims.p,
-                                      whole ? nullptr : S->st_boxes.p, N, S->st_status.p)))
-                return rc;
-        }
-        if (whole && n_trees) HIP_TRY(hipMemcpy(&bad, S->st_status.p, sizeof bad, hipMemcpyDeviceToHost));
-        if (bad) return fail(PT_ERR_UNSUPPORTED, "pt_scene_update: a new coordinate, radius or leaf box is not finite");
-        std::swap(S->prev_prims.p, S->st_prims.p); std::swap(S->prev_prims.n, S->st_prims.n);   // the new records, for a moment
-        std::swap(S->prims.p, S->prev_prims.p); std::swap(S->prims.n, S->prev_prims.n);         // current -> previous, new -> current
-        S->have_prev = true;
-        std::swap(S->normals.p, S->st_normals.p); std::swap(S->normals.n, S->st_normals.n);
-        S->dev.prims = S->prims.p; S->dev.normals = S->normals.p;
-        S->tri_only = !has_sphere;
-        S->sweep_groups = 0; S->sweep.count = 0;     // leaf boxes that were equal need not be any more: back to the tree
-        S->sweep_tab.release();                      // (no frame is in flight: the update synchronised before it wrote)
-        us_refit = us_since(t_stage);
+        us_records = us_since(t_stage);
+        if ((rc = adopt_staged(S, "pt_scene_update", !has_sphere, &us_plan, &us_refit))) return rc;
+        S->have_rest = false;                        // the next pt_scene_transform starts from these records
     }
     if (shading) {
         const clk::time_point t_stage = clk::now();
@@ -1699,6 +1733,53 @@ int update_scene(pt_scene* S, const pt_scene_desc* d, int flags) {
     select_tree(S, 0);
     S->updates++;
     S->update_us[0] = us_since(t_all); S->update_us[1] = us_records; S->update_us[2] = us_refit; S->update_us[3] = us_plan;
+    return PT_OK;
+}
+
+// pt_scene_transform (include/pt_api.h).  pt_scene_update's order of events with another producer of the staged records: the
+// matrices are checked and their entries made on the host, the rest records are snapshot where none are held, one kernel writes
+// the staged records from them (pt_scene_transform.hip), and adopt_staged does the rest.
+int transform_scene(pt_scene* S, const pt_transform* transforms, int32_t num_groups) {
+    using clk = std::chrono::steady_clock;
+    auto us_since = [](clk::time_point t0) { return (int64_t)std::chrono::duration_cast<std::chrono::microseconds>(clk::now() - t0).count(); };
+    if (!S->have_groups) return fail(PT_ERR_INVALID_ARG, "pt_scene_transform: the scene has no group assignment (pt_scene_set_groups)");
+    if (num_groups != S->num_groups) return fail(PT_ERR_INVALID_ARG, "pt_scene_transform: num_groups differs from pt_scene_set_groups'");
+    if (num_groups > 0 && !transforms) return fail(PT_ERR_INVALID_ARG, "pt_scene_transform: null transforms");
+    std::vector<ptx::Entry> tab((size_t)std::max(num_groups, 1));
+    for (int32_t g = 0; g < num_groups; g++)
+        if (const int bad = ptx::prepare(&transforms[g], &tab[(size_t)g]))
+            return fail(ptx::refusal_status(bad), "pt_scene_transform: transforms[" + std::to_string(g) + "]: " + ptx::refusal(bad));
+    const int N = S->dev.num_prims;
+    DeviceGuard guard;
+    { int grc = guard.enter(S->device); if (grc) return grc; }
+    // frames of this handle that are still in flight, on the caller's streams and on the slots' own, read the scene
+    HIP_TRY(hipDeviceSynchronize());
+    const clk::time_point t_all = clk::now();
+    int64_t us_records = 0, us_refit = 0, us_once = 0;
+    int rc;
+    if ((rc = ensure_staging(S)) || (rc = S->group_tab.ensure(tab.size() * ptx::kEntryFloats))) return rc;
+    const bool snapshot = !S->have_rest;
+    if (snapshot) {
+        const clk::time_point t_stage = clk::now();
+        if ((rc = S->rest_prims.ensure((size_t)N)) || (rc = S->rest_normals.ensure((size_t)N))) return rc;
+        HIP_TRY(hipMemcpyAsync(S->rest_prims.p, S->prims.p, (size_t)N * sizeof(DPrim), hipMemcpyDeviceToDevice, nullptr));
+        HIP_TRY(hipMemcpyAsync(S->rest_normals.p, S->normals.p, (size_t)N * sizeof(DNormals), hipMemcpyDeviceToDevice, nullptr));
+        HIP_TRY(hipStreamSynchronize(nullptr));           // paid once: timed on its own
+        us_once = std::max<int64_t>(us_since(t_stage), 1);
+    }
+    const clk::time_point t_stage = clk::now();
+    HIP_TRY(hipMemcpy(S->group_tab.p, tab.data(), tab.size() * sizeof(ptx::Entry), hipMemcpyHostToDevice));
+    if ((rc = ptx::transform_records(S->rest_prims.p, S->rest_normals.p, S->group_of.p, S->group_tab.p, N, S->st_prims.p, S->st_normals.p)))
+        return rc;
+    us_records = us_since(t_stage);
+    int64_t us_plan = 0;
+    if ((rc = adopt_staged(S, "pt_scene_transform", S->tri_only, &us_plan, &us_refit))) return rc;
+    // the handle's own streams do not synchronise with the default stream the kernels above ran on
+    HIP_TRY(hipDeviceSynchronize());
+    S->have_rest = true;                                 // (a refused call leaves the flag as it was: the next one copies again)
+    select_tree(S, 0);
+    S->transforms++;
+    S->transform_us[0] = us_since(t_all); S->transform_us[1] = us_records; S->transform_us[2] = us_refit; S->transform_us[3] = us_once + us_plan;
     return PT_OK;
 }
 
@@ -2089,6 +2170,7 @@ int pt_scene_destroy(pt_scene* S) {
     S->vd_guide.release(); S->vd_x[0].release(); S->vd_x[1].release(); S->vd_host.release();
     S->gr_x[0].release(); S->gr_x[1].release(); S->gr_host.release(); S->px_list.release();
     S->st_prims.release(); S->prev_prims.release(); S->st_normals.release(); S->st_boxes.release(); S->st_status.release();
+    S->group_of.release(); S->group_tab.release(); S->rest_prims.release(); S->rest_normals.release();
     for (auto& pl : S->refit_plan) ptf::plan_release(&pl);
     S->drop_events();
     delete S;
@@ -2101,6 +2183,57 @@ int pt_scene_update(pt_scene* S, const pt_scene_desc* desc, int flags) {
     if (flags == 0 || (flags & ~(PT_UPDATE_GEOMETRY | PT_UPDATE_SHADING)))
         return fail(PT_ERR_INVALID_ARG, "pt_scene_update: flags must be PT_UPDATE_GEOMETRY, PT_UPDATE_SHADING or both");
     return update_scene(S, desc, flags);
+}
+
+int pt_scene_set_groups(pt_scene* S, const int32_t* group_of_shape, int32_t num_groups) {
+    if (!S) return fail(PT_ERR_INVALID_ARG, "pt_scene_set_groups: null scene");
+    if (!group_of_shape) return fail(PT_ERR_INVALID_ARG, "pt_scene_set_groups: null group_of_shape");
+    if (num_groups < 0 || num_groups > (1 << 20)) return fail(PT_ERR_INVALID_ARG, "pt_scene_set_groups: num_groups must be in [0, 2^20]");
+    const int N = S->dev.num_prims;
+    for (int k = 0; k < N; k++)
+        if (group_of_shape[k] < -1 || group_of_shape[k] >= num_groups)
+            return fail(PT_ERR_INVALID_ARG, "pt_scene_set_groups: group_of_shape[" + std::to_string(k) + "] is not in [-1, num_groups)");
+    DeviceGuard guard;
+    { int grc = guard.enter(S->device); if (grc) return grc; }
+    int rc = S->group_of.ensure((size_t)N);
+    if (rc) return rc;
+    S->have_groups = false;                              // a copy that fails leaves no assignment, not half of one
+    HIP_TRY(hipMemcpy(S->group_of.p, group_of_shape, (size_t)N * sizeof(int32_t), hipMemcpyHostToDevice));
+    S->num_groups = num_groups;
+    S->have_groups = true;
+    return PT_OK;
+}
+
+int pt_scene_transform(pt_scene* S, const pt_transform* transforms, int32_t num_groups) {
+    if (!S) return fail(PT_ERR_INVALID_ARG, "pt_scene_transform: null scene");
+    return transform_scene(S, transforms, num_groups);
+}
+
+int pt_transform_geometry_host(const pt_transform* t, int32_t n, const float* positions, const float* normals, float* positions_out,
+                               float* normals_out) {
+    if (!t || n < 0 || !positions || !positions_out || (normals == nullptr) != (normals_out == nullptr))
+        return fail(PT_ERR_INVALID_ARG, "pt_transform_geometry_host: null transform or array, or normals without normals_out");
+    ptx::Entry e;
+    if (const int bad = ptx::prepare(t, &e)) return fail(ptx::refusal_status(bad), "pt_transform_geometry_host: transform: " + ptx::refusal(bad));
+    for (int32_t k = 0; k < n; k++) {
+        const ptm::V3 p = ptx::point(e.m, ptm::mk(positions[3 * (size_t)k], positions[3 * (size_t)k + 1], positions[3 * (size_t)k + 2]));
+        positions_out[3 * (size_t)k] = p.x; positions_out[3 * (size_t)k + 1] = p.y; positions_out[3 * (size_t)k + 2] = p.z;
+        if (normals) {
+            const ptm::V3 q = ptx::normal(e.c, ptm::mk(normals[3 * (size_t)k], normals[3 * (size_t)k + 1], normals[3 * (size_t)k + 2]));
+            normals_out[3 * (size_t)k] = q.x; normals_out[3 * (size_t)k + 1] = q.y; normals_out[3 * (size_t)k + 2] = q.z;
+        }
+    }
+    return PT_OK;
+}
+
+int pt_transform_sphere_host(const pt_transform* t, const float* center, float radius, float* center_out, float* radius_out) {
+    if (!t || !center || !center_out || !radius_out) return fail(PT_ERR_INVALID_ARG, "pt_transform_sphere_host: null argument");
+    ptx::Entry e;
+    if (const int bad = ptx::prepare(t, &e)) return fail(ptx::refusal_status(bad), "pt_transform_sphere_host: transform: " + ptx::refusal(bad));
+    const ptm::V3 p = ptx::point(e.m, ptm::mk(center[0], center[1], center[2]));
+    center_out[0] = p.x; center_out[1] = p.y; center_out[2] = p.z;
+    *radius_out = ptx::radius(e.m, radius);
+    return PT_OK;
 }
 
 int pt_render_async(pt_scene* S, const pt_render_params* p, float* fb_dev, void* hip_stream) {
@@ -2537,6 +2670,10 @@ int pt_scene_get_info(pt_scene* S, const char* key, int64_t* value) {
     else if (k == "prev_geometry") *value = S->have_prev ? 1 : 0;         // records from before the last geometry update are kept (pt_render_guides)
     else if (k == "updates") *value = S->updates;                         // successful pt_scene_update calls so far
     else if (k.rfind("update_us", 0) == 0 && k.size() == 10 && k[9] >= '0' && k[9] <= '3') *value = S->update_us[k[9] - '0'];
+    else if (k == "groups") *value = S->have_groups ? S->num_groups : 0;  // groups of the assignment pt_scene_set_groups made (0: none)
+    else if (k == "rest_geometry") *value = S->have_rest ? 1 : 0;         // a snapshot of the rest records is held (pt_scene_transform)
+    else if (k == "transforms") *value = S->transforms;                   // successful pt_scene_transform calls so far
+    else if (k.rfind("transform_us", 0) == 0 && k.size() == 13 && k[12] >= '0' && k[12] <= '3') *value = S->transform_us[k[12] - '0'];
     else if (k == "refit_shape0" || k == "refit_shape1") {
         // how a geometry update refits tree 0 (the caller's) / 1 (the internal one): 0 no plan (no such tree, a one-shape scene, or
         // no geometry update yet), 1 one launch, 2 scatter + a launch per wide level + the narrow top, 3 scatter + the narrow top alone

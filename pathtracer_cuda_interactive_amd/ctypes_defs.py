@@ -98,6 +98,11 @@ class PtDenoiseParams(C.Structure):
 PT_MOTION_GEOMETRY_CURRENT, PT_MOTION_GEOMETRY_PREVIOUS = 0, 1                # pt_motion_params.geometry
 
 
+class PtTransform(C.Structure):
+    """pt_transform (pt_api.h): a row-major 3x4 matrix, one per group of shapes (pt_scene_transform)."""
+    _fields_ = [("m", C.c_float * 12)]
+
+
 class PtMotionParams(C.Structure):
     """pt_motion_params (pt_api.h): the previous frame's camera and which record set holds its geometry (pt_render_guides)."""
     _fields_ = [("prev_cam_origin", c_float3), ("prev_cam_top_left", c_float3), ("prev_cam_horizontal", c_float3),

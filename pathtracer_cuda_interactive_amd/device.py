@@ -12,7 +12,7 @@ from . import _build
 from .ctypes_defs import (PT_MOTION_GEOMETRY_CURRENT, PT_MOTION_GEOMETRY_PREVIOUS, PT_OK, PT_SHAPE_SPHERE, PT_TRAVERSAL_DEFAULT,
                           PT_UPDATE_GEOMETRY, PT_UPDATE_SHADING, SPARSE_ARGTYPES, PtAdaptiveParams, PtBvhNode, PtCounters, PtDenoiseParams, PtError,
                           PtGradientParams, PtGuideBuffers, PtLight, PtMaterial, PtMesh, PtMotionParams, PtRenderParams, PtSceneDesc, PtShape,
-                          PtTemporalIo, PtTemporalParams, PtVdenoiseParams)
+                          PtTemporalIo, PtTemporalParams, PtTransform, PtVdenoiseParams)
 from .host import NODE_DTYPE  # noqa: F401  (one definition; callers also read it from here)
 
 _lib = None
@@ -26,6 +26,7 @@ EXPORTS = [
     "pt_temporal_accumulate_moments", "pt_temporal_accumulate_moments_host", "pt_denoise_variance", "pt_denoise_variance_host",
     "pt_temporal_gradient", "pt_temporal_gradient_host", "pt_temporal_accumulate_adaptive", "pt_temporal_accumulate_adaptive_host",
     "pt_render_pixels", "pt_gradient_pixels", "pt_gradient_pixels_host", "pt_temporal_gradient_sparse", "pt_temporal_gradient_sparse_host",
+    "pt_scene_set_groups", "pt_scene_transform", "pt_transform_geometry_host", "pt_transform_sphere_host",
 ]
 
 
@@ -44,6 +45,10 @@ def lib():
         L.pt_scene_create.argtypes = [C.POINTER(PtSceneDesc), C.POINTER(vp)]
         L.pt_scene_destroy.argtypes = [vp]
         L.pt_scene_update.argtypes = [vp, C.POINTER(PtSceneDesc), C.c_int]
+        L.pt_scene_set_groups.argtypes = [vp, ip, C.c_int32]
+        L.pt_scene_transform.argtypes = [vp, C.POINTER(PtTransform), C.c_int32]
+        L.pt_transform_geometry_host.argtypes = [C.POINTER(PtTransform), C.c_int32, vp, vp, vp, vp]
+        L.pt_transform_sphere_host.argtypes = [C.POINTER(PtTransform), fp, C.c_float, fp, fp]
         L.pt_render.argtypes = [vp, C.POINTER(PtRenderParams), vp, C.c_int]
         L.pt_render_async.argtypes = [vp, C.POINTER(PtRenderParams), vp, vp]
         L.pt_render_accumulate.argtypes = [vp, C.POINTER(PtRenderParams), vp, vp]
@@ -114,6 +119,17 @@ class DeviceScene:
         shape count the handle was created with (see edited_desc); its nodes are ignored."""
         flags = (PT_UPDATE_GEOMETRY if geometry else 0) | (PT_UPDATE_SHADING if shading else 0)
         _check(lib().pt_scene_update(self._h, C.byref(desc), flags))
+
+    def set_groups(self, ids, num_groups):
+        """pt_scene_set_groups: the group of every shape (ids [num_shapes] int32, -1 = never moves) for transform."""
+        ids = np.ascontiguousarray(ids, dtype=np.int32).reshape(-1)
+        _check(lib().pt_scene_set_groups(self._h, ids.ctypes.data_as(C.POINTER(C.c_int32)), int(num_groups)))
+
+    def transform(self, matrices):
+        """pt_scene_transform: the rest geometry under one row-major 3x4 matrix per group (matrices [num_groups, 3, 4]); the
+        records are made on the device and both trees refitted.  Absolute, not cumulative.  Blocking."""
+        M = _matrices(matrices)
+        _check(lib().pt_scene_transform(self._h, M.ctypes.data_as(C.POINTER(PtTransform)), M.shape[0]))
 
     def set_option(self, key, value):
         _check(lib().pt_scene_set_option(self._h, key.encode(), int(value)))
@@ -755,6 +771,114 @@ def edited_desc(desc, meshes=None, spheres=None, materials=None, lights=None, ba
         d2.background[:] = [float(x) for x in background]
     d2._keep = keep
     return d2
+
+
+def _matrices(matrices):
+    M = np.ascontiguousarray(matrices, dtype=np.float32)
+    if M.ndim == 2 and M.shape == (3, 4):
+        M = M[None]
+    if M.ndim != 3 or M.shape[1:] != (3, 4):
+        raise ValueError("matrices must be [num_groups, 3, 4]")
+    return M
+
+
+SHAPE_DTYPE = np.dtype([("type", "<i4"), ("material_id", "<i4"), ("area_light_id", "<i4"), ("center", "<f4", 3), ("radius", "<f4"),
+                        ("face_index", "<i4"), ("mesh_index", "<i4")])
+
+
+def shape_table(desc):
+    """desc's shapes as a structured numpy array (a copy)."""
+    assert SHAPE_DTYPE.itemsize == C.sizeof(PtShape)
+    raw = C.string_at(C.addressof(desc.shapes.contents), desc.num_shapes * C.sizeof(PtShape))
+    return np.frombuffer(raw, dtype=SHAPE_DTYPE).copy()
+
+
+def groups_by_object(desc):
+    """One group per object of `desc`: a triangle's group is its mesh_index, sphere k (the k-th sphere in shape order) gets
+    num_meshes + k.  Returns (ids [num_shapes] int32, num_groups)."""
+    sh = shape_table(desc)
+    sphere = sh["type"] == PT_SHAPE_SPHERE
+    ids = sh["mesh_index"].astype(np.int32)
+    ids[sphere] = desc.num_meshes + np.arange(int(sphere.sum()), dtype=np.int32)
+    return ids, desc.num_meshes + int(sphere.sum())
+
+
+def rigid_matrix(axis, degrees, centre=(0.0, 0.0, 0.0), scale=1.0, translate=(0.0, 0.0, 0.0)):
+    """A row-major 3x4 float32 matrix: rotation by `degrees` about the unit vector along `axis` through `centre`, a uniform
+    `scale` about the same point, then a translation."""
+    a = np.asarray(axis, dtype=np.float64)
+    a = a / np.linalg.norm(a)
+    t = np.radians(degrees)
+    K = np.array([[0, -a[2], a[1]], [a[2], 0, -a[0]], [-a[1], a[0], 0]])
+    R = (np.eye(3) + np.sin(t) * K + (1 - np.cos(t)) * (K @ K)) * scale
+    c = np.asarray(centre, dtype=np.float64)
+    M = np.empty((3, 4))
+    M[:, :3] = R
+    M[:, 3] = c - R @ c + np.asarray(translate, dtype=np.float64)
+    return M.astype(np.float32)
+
+
+def transform_geometry_host(matrix, positions, normals=None):
+    """pt_transform_geometry_host: positions [n, 3] (and normals [n, 3]) under one 3x4 matrix, by the host half of the library
+    (no GPU needed).  Returns (positions', normals' or None) as new arrays."""
+    M = _matrices(matrix)[0]
+    P = np.ascontiguousarray(positions, dtype=np.float32).reshape(-1, 3)
+    Nn = None if normals is None else np.ascontiguousarray(normals, dtype=np.float32).reshape(-1, 3)
+    if Nn is not None and Nn.shape != P.shape:
+        raise ValueError("normals must match positions")
+    Po = np.empty_like(P)
+    No = None if Nn is None else np.empty_like(Nn)
+    _check(lib().pt_transform_geometry_host(M.ctypes.data_as(C.POINTER(PtTransform)), P.shape[0], *_ptrs([P, Nn, Po, No])))
+    return Po, No
+
+
+def transform_sphere_host(matrix, center, radius):
+    """pt_transform_sphere_host: (centre' [3] float32, radius' as np.float32) of a sphere under one 3x4 matrix (no GPU needed)."""
+    M = _matrices(matrix)[0]
+    c = np.ascontiguousarray(center, dtype=np.float32).reshape(3)
+    co, ro = np.empty(3, dtype=np.float32), np.empty(1, dtype=np.float32)
+    _check(lib().pt_transform_sphere_host(M.ctypes.data_as(C.POINTER(PtTransform)), _fp(c), float(np.float32(radius)), _fp(co), _fp(ro)))
+    return co, ro[0]
+
+
+def transform_desc_host(desc, ids, matrices):
+    """The desc DeviceScene.transform(matrices) stands for, made on the host: a copy of `desc` (edited_desc) in which every shape
+    with a group id >= 0 is under its group's matrix, through pt_transform_geometry_host / pt_transform_sphere_host.  Transforms
+    apply to `desc` — the rest pose — and never compose: transform_desc_host(desc, ids, M2) does not depend on an M1 applied
+    before.  A mesh whose faces all share one group keeps its vertex table; one whose faces are spread over several groups
+    gets a table of three vertices per face (a vertex shared by two groups has two images).  The node pool is desc's."""
+    from .standins import mesh_arrays
+    M = _matrices(matrices)
+    ids = np.ascontiguousarray(ids, dtype=np.int32).reshape(-1)
+    if ids.size != desc.num_shapes or (ids.size and (ids.min() < -1 or ids.max() >= M.shape[0])):
+        raise ValueError("ids must hold one value in [-1, num_groups) per shape")
+    sh = shape_table(desc)
+    tri = sh["type"] != PT_SHAPE_SPHERE
+    mesh_list = []
+    for m in range(desc.num_meshes):
+        P, I, Nn = mesh_arrays(desc, m)
+        mine = np.nonzero(tri & (sh["mesh_index"] == m))[0]
+        fg = np.full(I.shape[0], -1, dtype=np.int32)
+        fg[sh["face_index"][mine]] = ids[mine]
+        if (fg[sh["face_index"][mine]] != ids[mine]).any():
+            raise ValueError(f"mesh {m}: a face is used by shapes of different groups")
+        used = np.unique(ids[mine])
+        if used.size == 1 and used[0] >= 0:
+            P, Nn = transform_geometry_host(M[used[0]], P, Nn)
+        elif used.size > 1:
+            P, Nn = P[I].reshape(-1, 3), Nn[I].reshape(-1, 3)
+            I = np.arange(P.shape[0], dtype=np.int32).reshape(-1, 3)
+            order = np.argsort(fg, kind="stable")
+            groups, first = np.unique(fg[order], return_index=True)
+            for g, lo, hi in zip(groups, first, list(first[1:]) + [order.size]):
+                if g >= 0:
+                    v = (3 * order[lo:hi, None] + np.arange(3)).reshape(-1)
+                    P[v], Nn[v] = transform_geometry_host(M[g], P[v], Nn[v])
+        mesh_list.append((P, I, Nn, desc.meshes[m].material_id, desc.meshes[m].area_light_id))
+    spheres = {}
+    for i in np.nonzero(~tri & (ids >= 0))[0]:
+        spheres[int(i)] = transform_sphere_host(M[ids[i]], sh["center"][i], sh["radius"][i])
+    return edited_desc(desc, mesh_list=mesh_list, spheres=spheres)
 
 
 def wobbled_desc(desc, step, meshes=None, amp=0.01):

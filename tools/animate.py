@@ -2,6 +2,7 @@
 
   python tools/animate.py SCENE.pts [--frames 8] [--size 640x480] [--spp 2] [--translate DX,DY,DZ | --orbit DEG] [--wobble]
                           [--denoise | --variance | --gradient | --gradient-sparse] [--relight K:R,G,B] [--reference-spp N] [--out PREFIX] [--time]
+                          [--spin G:AXIS:DEG_PER_FRAME ...]
 
 Per frame: pt_render at --spp, pt_render_guides against the previous frame's camera (and, with --wobble, the previous
 geometry: every mesh gets device.wobbled_desc's per-vertex wobble through DeviceScene.update), pt_temporal_accumulate, and with
@@ -17,6 +18,9 @@ and pt_temporal_accumulate_adaptive with that map in place of pt_temporal_accumu
 --gradient-sparse (implies --gradient): the re-trace is one pixel per tile instead of a row.  From the second
 frame on, pt_gradient_pixels with the frame number as its seed (stage "pixels"), pt_render_pixels of the previous frame's
 parameters at that list on the current scene (stage "list"), and pt_temporal_gradient_sparse (stage "gradient").
+--spin G:AXIS:DEG_PER_FRAME (repeatable): object G — mesh G, or sphere G - num_meshes, device.groups_by_object's
+numbering — turns about the x, y or z axis through its centroid by that many degrees per frame through DeviceScene.transform: the
+matrices go to the device, no vertex is touched on the host, and the guides follow the previous transform's records.  Not with --wobble.
 --relight K:R,G,B: from frame K on every light's radiance is scaled by (R, G, B) through DeviceScene.update(shading=True).
 --time: after the animation, each stage again on the last frame's inputs, warm, in windows of at least 0.5 s, with
 pt_render_aov and one pt_denoise iteration as yardsticks and the bytes pt_temporal_accumulate must move."""
@@ -94,6 +98,28 @@ def relit_desc(desc, factor):
     return dev.edited_desc(desc, lights=lights)
 
 
+def spin_setup(d0, specs, scenes):
+    """Parses --spin, gives the spun objects the groups 0, 1, ... on every handle of `scenes` (all other shapes: -1) and returns
+    frame -> matrices [groups, 3, 4]."""
+    from pathtracer_cuda_interactive_amd.standins import mesh_arrays
+    ids, G = dev.groups_by_object(d0)
+    sh = dev.shape_table(d0)
+    spins = []
+    for spec in specs:
+        g, axis, deg = spec.split(":")
+        g, axis = int(g), {"x": (1, 0, 0), "y": (0, 1, 0), "z": (0, 0, 1)}[axis.lower()]
+        if not 0 <= g < G:
+            raise SystemExit(f"--spin {spec}: the scene has objects 0..{G - 1}")
+        centre = mesh_arrays(d0, g)[0].astype(np.float64).mean(axis=0) if g < d0.num_meshes else sh["center"][ids == g][0]
+        spins.append((g, axis, float(deg), centre))
+    group_of = np.full(d0.num_shapes, -1, np.int32)
+    for k, (g, _, _, _) in enumerate(spins):
+        group_of[ids == g] = k
+    for s in scenes:
+        s.set_groups(group_of, len(spins))
+    return lambda frame: np.stack([dev.rigid_matrix(axis, deg * frame, centre=c) for _, axis, deg, c in spins])
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("scene")
@@ -108,6 +134,7 @@ def main():
     ap.add_argument("--gradient", action="store_true")
     ap.add_argument("--gradient-sparse", action="store_true")
     ap.add_argument("--relight", default="")
+    ap.add_argument("--spin", action="append", default=[])
     ap.add_argument("--reference-spp", type=int, default=0)
     ap.add_argument("--out", default="")
     ap.add_argument("--time", action="store_true")
@@ -122,6 +149,11 @@ def main():
     d0 = hs.finalize(PT_BVH_SORT_REFERENCE)
     ds = dev.DeviceScene(d0)
     ref = dev.DeviceScene(d0) if a.reference_spp else None
+    spin_matrices = None
+    if a.spin:
+        if a.wobble:
+            ap.error("--spin and --wobble both move the geometry: give one")
+        spin_matrices = spin_setup(d0, a.spin, [s for s in (ds, ref) if s is not None])
     stream = torch.cuda.current_stream().cuda_stream
     f3 = lambda: torch.empty((h, w, 3), device="cuda")           # noqa: E731
     f1 = lambda: torch.empty((h, w), device="cuda")              # noqa: E731
@@ -169,6 +201,9 @@ def main():
                 desc_k = relit_desc(desc_k, relight_factor)
             ds.update(desc_k, geometry=moved, shading=relit)
             update_ms = ds.info("update_us0") / 1e3
+        if spin_matrices is not None and k:
+            ds.transform(spin_matrices(k))
+            update_ms = ds.info("transform_us0") / 1e3
         if a.gradient:
             color = cur["color"]
         times["render"].append(once(lambda: ds.render_into(p, color.data_ptr(), stream)))
@@ -216,6 +251,8 @@ def main():
         line = f"frame {k:3d}: " + "  ".join(f"{s} {times[s][-1]:7.3f} ms" for s in stages)
         if desc_k is not None:
             line += f"  (update {update_ms:.3f} ms)"
+        elif spin_matrices is not None and k:
+            line += f"  (transform {update_ms:.3f} ms)"
         if a.gradient and k:
             line += f"  lambda: mean {float(lam.mean()):.3f}, {float((lam > 0).float().mean()):.3f} of the tiles positive"
         valid = prev_depth > 0
@@ -224,6 +261,8 @@ def main():
         if ref is not None:
             if desc_k is not None:
                 ref.update(desc_k, geometry=moved, shading=relit)
+            if spin_matrices is not None and k:
+                ref.transform(spin_matrices(k))
             q = p.copy()
             q.spp, q.seed = a.reference_spp, 7
             truth = ref.render(q)

@@ -434,6 +434,17 @@ typedef struct pt_guide_buffers { /* any pointer may be NULL; on_device != 0: al
 } pt_guide_buffers;
 int pt_render_guides(pt_scene* scene, const pt_render_params* p, const pt_motion_params* m, const pt_guide_buffers* out,
                      int on_device);
+/* pt_render_guides for a frame that is enqueued and left alone: the same arguments, rules, row selection and NULL-output rule,
+ * the same bits in every buffer, on DEVICE pointers only, enqueued on hip_stream (NULL = the default stream) without a host
+ * sync; what the caller observes is written in stream order.  m == NULL: pt_render_aov's four buffers (motion and prev_depth
+ * are not written).  NULL p or out, a bad geometry value, a bad frame or row selection: PT_ERR_INVALID_ARG as there.
+ * It reads scene memory only, takes no frame slot and leaves pt_get_counters, pt_get_frame_times and info "trace_variant" as
+ * they were.  The kernel: option "query_guides" 0 (default) = automatic, 1 = the lane-refilling query kernel of pt_trace_rays
+ * (below), 2 = pt_render_guides' own one-shot kernel on hip_stream.  Automatic is the one-shot kernel — camera rays are coherent,
+ * and the refilling kernel measured slower on them at every scene and size tried — unless "query_blocks" is set, which asks for
+ * the refilling kernel; info "query_guides" reports what the last call ran on (1 refilling, 0 one-shot).  DESIGN.md §24. */
+int pt_render_guides_async(pt_scene* scene, const pt_render_params* p, const pt_motion_params* m, const pt_guide_buffers* out,
+                           void* hip_stream);
 
 /* Carries a colour history along those motion vectors: an exponential average whose length grows by one per frame up to
  * max_history where the reprojected history agrees with this frame in depth and normal, and restarts elsewhere. */
@@ -632,6 +643,30 @@ int pt_temporal_accumulate_adaptive(pt_scene* scene, const pt_temporal_params* t
 int pt_temporal_accumulate_adaptive_host(const pt_temporal_params* t, float albedo_floor, const pt_temporal_io* io,
                                          const float* lambda, int32_t stride);
 
+/* What do these rays hit: picking, occlusion and visibility probes, baking, a caller's own light sampling.  DESIGN.md §24.
+ *   rays: n x {org[3], dir[3], tnear, tfar} (pt_debug_intersect's layout).  traversal: PT_TRAVERSAL_* as in pt_debug_intersect,
+ *   PT_TRAVERSAL_DEFAULT = exact.  The tree is the one a render traverses: option "fast_tree" is honoured.
+ *   PT_QUERY_CLOSEST: out_tuv [n, 3] and out_prim [n] hold exactly what pt_debug_intersect writes — {t, u, v} and the shape id of
+ *     the closest hit inside (tnear, tfar), -1 and zeros on a miss; ties on t go to the primitive the caller's tree visits
+ *     first, rays with a zero direction component are traced on the caller's tree.
+ *   PT_QUERY_ANY: out_prim[k] = 1 if any primitive test of ray k succeeds inside its interval, else 0 — by definition
+ *     (closest prim >= 0) of the same ray; the ray stops at its first hit.  out_tuv may be NULL and is not written.
+ *   on_device != 0: device pointers, enqueued on hip_stream (NULL = the default stream) without a host sync; the results are
+ *     written in stream order, and `rays` must stay valid until the stream has passed the call.
+ *   on_device == 0: host pointers, blocking; staged through memory of the handle that grows on demand and is freed with it.
+ *   PT_ERR_INVALID_ARG, pt_last_error() naming the argument: n < 0, n > 2^30, an unknown mode or traversal, and with n > 0 a
+ *   NULL rays or out_prim, or PT_QUERY_CLOSEST with a NULL out_tuv.  n == 0: PT_OK, nothing is written.
+ * The kernel (csrc/pt_query.h): a fixed grid of waves works through the rays; a lane whose ray is finished takes the next one,
+ * so a ray that walks hundreds of nodes holds up one lane, not a wave.  A wave works through ranges of 64 ray indices (info
+ * "query_chunk"): the first is its own, every further one it reserves with one atomic add on the launch's work counter.  Results
+ * are stored and rays handed out when 16 lanes of a wave are idle (option "query_refill", 1 .. 64; 0 = that default).  Every
+ * launch takes the next of 64 counters the handle rotates through (the ring's size), so launches in flight on different streams
+ * never share one; the 65th launch waits, on its stream, for the launch that had its counter.  The call reads scene memory only, takes no frame slot and leaves pt_get_counters, pt_get_frame_times and info
+ * "trace_variant" as they were; pt_scene_update and pt_scene_transform synchronise the device before they write. */
+enum { PT_QUERY_CLOSEST = 0, PT_QUERY_ANY = 1 };
+int pt_trace_rays(pt_scene* scene, const float* rays, int32_t n, int mode, int traversal,
+                  float* out_tuv, int32_t* out_prim, int on_device, void* hip_stream);
+
 int pt_get_counters(pt_scene* scene, pt_counters* out);   /* synchronises the scene's last stream */
 
 /* HIP-event times of the last render calls on the scene, oldest first: kernel_ms[k] / resolve_ms[k] of up to max_frames calls,
@@ -714,6 +749,11 @@ int pt_bvh_build_sweep_device(const pt_scene_desc* desc, pt_bvh_node* out_nodes,
  *   "item_order"    1 (default) a band is worked through row by row (all samples of a row first), 0 = sample by sample
  *   "force_global"  1 = never stage the scene in LDS
  *   "blocks_per_cu" persistent blocks per CU (0 = occupancy query; at most 32)
+ *   "query_blocks"  blocks of a query launch (pt_trace_rays, pt_render_guides_async): 0 (default) = resident blocks per CU (an
+ *                   explicit "blocks_per_cu" as given) x CUs, and no more than give every lane a ray; 1 .. 4096 = exactly that
+ *                   many (and pt_render_guides_async then takes the refilling kernel).  Same results whatever the grid.
+ *   "query_refill"  idle lanes from which a wave of the query kernel stores results and hands out rays, 1 .. 64 (0 = 16)
+ *   "query_guides"  the kernel of pt_render_guides_async: 0 (default) automatic, 1 refilling, 2 one-shot (see there)
  *   "timing_frames" render calls whose HIP events are kept for pt_get_frame_times (0 .. 4096, default 1).  0 = no timing events
  *                   at all (pt_counters.kernel_ms / resolve_ms read 0): four event records less per frame, which an interactive
  *                   loop of 2-spp frames feels (cbox 640x480, host sync per frame: 3,250 -> 3,540 frames/s; scene1 5,300 -> 6,110)
@@ -748,7 +788,9 @@ int pt_bvh_build_sweep_device(const pt_scene_desc* desc, pt_bvh_node* out_nodes,
  * register bank filled 64 at a time: trace_kernel_v2 on LDS-resident scenes of triangles with diffuse materials),
  * "reg_stack" (1 = that kernel kept its traversal stack in a register, see option "reg_stack"; "lds_bytes" of such a launch has no
  * stack columns), "leaf_sweep" (1 = that kernel found its leaves by the box sweep, see option "leaf_sweep"), "sweep_boxes",
- * "frames_in_flight", "sweep_on_device" (the internal tree was built on the GPU),
+ * "frames_in_flight", "sweep_on_device" (the internal tree was built on the GPU), "query_chunk" (ray indices a wave of the query
+ * kernel reserves per atomic), "query_grid" (blocks of the last query launch), "query_guides" (the last pt_render_guides_async
+ * ran on the refilling kernel: 1, or the one-shot kernel: 0),
  * "create_us0".."create_us6" (wall microseconds of pt_scene_create: total, primitive records, caller's tree checked and re-laid,
  * internal tree built, ... re-laid, uploads + probe, tie tables). */
 int pt_scene_set_option(pt_scene* scene, const char* key, int64_t value);

@@ -33,6 +33,7 @@
 #include "pt_temporal.h"
 #include "pt_kernels.h"
 #include "pt_kernel_q.h"
+#include "pt_query.h"
 
 using namespace ptl;
 using namespace ptk;
@@ -229,6 +230,27 @@ struct pt_scene {
     DevBuf<float> gr_host;
     // pt_render_pixels: staging of a list that comes in host memory (the colours go back through fb_tmp)
     DevBuf<int32_t> px_list;
+    // pt_trace_rays / pt_render_guides_async (pt_query.h): every launch of the query kernel takes the next work counter of a ring
+    // (a 128-B line each), cleared on the launch's stream; the entry's event is recorded behind the launch, and a launch that
+    // finds the event of its entry still pending makes its stream wait for it — two launches in flight never share a counter.
+    // Staging of a pt_trace_rays call that comes in host memory: grown on demand, freed with the handle.
+    DevBuf<uint32_t> q_counters;
+    hipEvent_t q_event[ptq::kQueryRing] = {};
+    uint64_t q_seq = 0;                                   // query launches so far
+    DevBuf<float> q_rays, q_tuv;
+    DevBuf<int32_t> q_prim;
+    int64_t opt_query_blocks = 0;                         // 0 = automatic grid, else exactly this many blocks
+    int64_t opt_query_refill = 0;                         // 0 = automatic, else idle lanes from which a wave refills (1 .. 64)
+    int64_t opt_query_guides = 0;                         // pt_render_guides_async: 0 = automatic, 1 = the refilling kernel, 2 = aov_kernel
+    int64_t info_query_guides = 0;                        // the last pt_render_guides_async ran on the refilling kernel (1) or on aov_kernel (0)
+    int64_t info_query_grid = 0;                          // blocks of the last query launch
+    const void* q_cfg_fn = nullptr;                       // occupancy of the last query kernel variant used (as cfg_fn below)
+    uint32_t q_cfg_lds = 0;
+    int q_cfg_occ = 0;
+    void drop_query() {
+        q_counters.release(); q_rays.release(); q_tuv.release(); q_prim.release();
+        for (auto& e : q_event) { if (e) (void)hipEventDestroy(e); e = nullptr; }
+    }
     // What a frame's trace kernel writes lives in a frame slot; render call k uses slot k % frames_in_flight.  With more than one
     // slot a single-pass frame runs on the slot's own stream: the trace kernel at once (it reads the immutable scene and writes
     // the slot only), the resolve — the one step that touches the caller's buffer — once the caller's stream has reached the
@@ -319,11 +341,10 @@ struct pt_scene {
 
 namespace {
 
-// Points the kernel argument block at one of the two trees; fallback: exact traversal on the internal tree — ties settled in the
+// Points a kernel argument block (select_tree: the handle's own) at one of the two trees; fallback: exact traversal on the internal tree — ties settled in the
 // caller's visit order, rays with a zero direction component traced on tree[0].
-void select_tree(pt_scene* S, int which, bool fallback = false) {
+void tree_view(const pt_scene* S, SceneDev& dv, int which, bool fallback) {
     const pt_scene::Tree& T = S->tree[which];
-    SceneDev& dv = S->dev;
     dv.nodes = T.nodes.p;
     dv.nodes_oct = T.have_oct ? T.nodes_oct.p : nullptr;
     dv.num_nodes = T.num_nodes;
@@ -339,6 +360,7 @@ void select_tree(pt_scene* S, int which, bool fallback = false) {
     dv.ref_anc = S->ref_anc.p;
     dv.ref_levels = S->ref_levels;
 }
+void select_tree(pt_scene* S, int which, bool fallback = false) { tree_view(S, S->dev, which, fallback); }
 
 struct TreeHost {
     std::vector<DNode> nodes;
@@ -1783,11 +1805,9 @@ int transform_scene(pt_scene* S, const pt_transform* transforms, int32_t num_gro
     return PT_OK;
 }
 
-// pt_render_aov (m == nullptr) and pt_render_guides: one aov_kernel launch on the default stream, blocking.
-int guide_pass(pt_scene* S, const pt_render_params* p, const pt_motion_params* m, const pt_guide_buffers& out, int on_device) {
-    float *albedo = out.albedo, *normal = out.normal, *depth = out.depth;
-    int32_t* prim = out.prim;
-    float *motion = m ? out.motion : nullptr, *prev_depth = m ? out.prev_depth : nullptr;
+// What a guide pass (pt_render_aov, pt_render_guides, pt_render_guides_async) takes from pt_render_params: the camera, the frame
+// and the row selection as the kernels read them, the traversal mode, the number of selected pixels.
+int guide_render_dev(const pt_render_params* p, RenderDev* rd_out, int* traversal_out, uint64_t* npix_out) {
     if (p->width <= 0 || p->height <= 0) return fail(PT_ERR_INVALID_ARG, "width and height must be positive");
     const int traversal = p->traversal == PT_TRAVERSAL_DEFAULT ? PT_TRAVERSAL_EXACT : p->traversal;
     if (traversal != PT_TRAVERSAL_EXACT && traversal != PT_TRAVERSAL_PRUNED) return fail(PT_ERR_INVALID_ARG, "unknown traversal mode");
@@ -1796,6 +1816,41 @@ int guide_pass(pt_scene* S, const pt_render_params* p, const pt_motion_params* m
     if (rc) return rc;
     const uint64_t npix = (uint64_t)rows.count * (uint64_t)p->width;
     if (npix > (1ull << 30)) return fail(PT_ERR_INVALID_ARG, "more than 2^30 pixels per call");
+    RenderDev rd{};
+    std::memcpy(rd.cam_origin, p->cam_origin, sizeof rd.cam_origin);
+    std::memcpy(rd.cam_top_left, p->cam_top_left, sizeof rd.cam_top_left);
+    std::memcpy(rd.cam_horizontal, p->cam_horizontal, sizeof rd.cam_horizontal);
+    std::memcpy(rd.cam_vertical, p->cam_vertical, sizeof rd.cam_vertical);
+    rd.width = p->width; rd.height = p->height;
+    rd.row_begin = rows.begin; rd.row_step = rows.step; rd.num_rows = rows.count;
+    rd.npix = (uint32_t)npix;
+    rd.div_width = make_fastdiv((uint32_t)p->width);
+    *rd_out = rd;
+    *traversal_out = traversal;
+    *npix_out = npix;
+    return PT_OK;
+}
+
+// ... and from pt_motion_params: the previous camera and the record set that holds the previous geometry.
+void guide_motion_dev(const pt_scene* S, const pt_motion_params* m, MotionDev* mo) {
+    std::memcpy(mo->cam.origin, m->prev_cam_origin, sizeof mo->cam.origin);
+    std::memcpy(mo->cam.top_left, m->prev_cam_top_left, sizeof mo->cam.top_left);
+    std::memcpy(mo->cam.horizontal, m->prev_cam_horizontal, sizeof mo->cam.horizontal);
+    std::memcpy(mo->cam.vertical, m->prev_cam_vertical, sizeof mo->cam.vertical);
+    // a handle that was never updated has previous = current
+    mo->prev_prims = m->geometry == PT_MOTION_GEOMETRY_PREVIOUS && S->have_prev ? S->prev_prims.p : S->prims.p;
+}
+
+// pt_render_aov (m == nullptr) and pt_render_guides: one aov_kernel launch on the default stream, blocking.
+int guide_pass(pt_scene* S, const pt_render_params* p, const pt_motion_params* m, const pt_guide_buffers& out, int on_device) {
+    float *albedo = out.albedo, *normal = out.normal, *depth = out.depth;
+    int32_t* prim = out.prim;
+    float *motion = m ? out.motion : nullptr, *prev_depth = m ? out.prev_depth : nullptr;
+    RenderDev rd{};
+    int traversal = 0;
+    uint64_t npix = 0;
+    int rc = guide_render_dev(p, &rd, &traversal, &npix);
+    if (rc) return rc;
     if (npix == 0 || (!albedo && !normal && !depth && !prim && !motion && !prev_depth)) return PT_OK;
     DeviceGuard guard;
     { int grc = guard.enter(S->device); if (grc) return grc; }
@@ -1814,12 +1869,7 @@ int guide_pass(pt_scene* S, const pt_render_params* p, const pt_motion_params* m
     }
     MotionDev mo{};
     if (m) {
-        std::memcpy(mo.cam.origin, m->prev_cam_origin, sizeof mo.cam.origin);
-        std::memcpy(mo.cam.top_left, m->prev_cam_top_left, sizeof mo.cam.top_left);
-        std::memcpy(mo.cam.horizontal, m->prev_cam_horizontal, sizeof mo.cam.horizontal);
-        std::memcpy(mo.cam.vertical, m->prev_cam_vertical, sizeof mo.cam.vertical);
-        // a handle that was never updated has previous = current
-        mo.prev_prims = m->geometry == PT_MOTION_GEOMETRY_PREVIOUS && S->have_prev ? S->prev_prims.p : S->prims.p;
+        guide_motion_dev(S, m, &mo);
         mo.motion = on_device ? motion : (motion ? d_motion.p : nullptr);
         mo.prev_depth = on_device ? prev_depth : (prev_depth ? d_prev_depth.p : nullptr);
     }
@@ -1829,15 +1879,6 @@ int guide_pass(pt_scene* S, const pt_render_params* p, const pt_motion_params* m
     select_tree(S, fast ? 1 : 0, fast);
     const int cap = fast && S->dev.redo_cap > S->dev.stack_cap ? S->dev.redo_cap : S->dev.stack_cap;
     const uint32_t lds = (uint32_t)(kBlock / 64) * (uint32_t)cap * 64u * 4u;
-    RenderDev rd{};
-    std::memcpy(rd.cam_origin, p->cam_origin, sizeof rd.cam_origin);
-    std::memcpy(rd.cam_top_left, p->cam_top_left, sizeof rd.cam_top_left);
-    std::memcpy(rd.cam_horizontal, p->cam_horizontal, sizeof rd.cam_horizontal);
-    std::memcpy(rd.cam_vertical, p->cam_vertical, sizeof rd.cam_vertical);
-    rd.width = p->width; rd.height = p->height;
-    rd.row_begin = rows.begin; rd.row_step = rows.step; rd.num_rows = rows.count;
-    rd.npix = (uint32_t)npix;
-    rd.div_width = make_fastdiv((uint32_t)p->width);
     const dim3 grid((unsigned)((npix + kBlock - 1) / kBlock));
     if (m && traversal == PT_TRAVERSAL_PRUNED)
         hipLaunchKernelGGL((aov_kernel<true, true>), grid, dim3(kBlock), lds, nullptr, S->dev, rd, o_albedo, o_normal, o_depth, o_prim, mo);
@@ -1859,6 +1900,141 @@ int guide_pass(pt_scene* S, const pt_render_params* p, const pt_motion_params* m
     if (motion) HIP_TRY(hipMemcpy(motion, d_motion.p, npix * 2 * sizeof(float), hipMemcpyDeviceToHost));
     if (prev_depth) HIP_TRY(hipMemcpy(prev_depth, d_prev_depth.p, npix * sizeof(float), hipMemcpyDeviceToHost));
     return PT_OK;
+}
+
+// One launch of the lane-refilling query kernel (pt_query.h) on `stream`, without a host sync: the handle's tree choice in an
+// argument block of its own (the handle's is not touched), the grid, the next work counter of the ring.
+// src: ptq::kSrcClosest / kSrcAny / kSrcGuides; q.n > 0.
+int query_launch(pt_scene* S, int src, bool prune, bool motion, ptq::QueryDev q, const RenderDev& rd, const MotionDev& mo, hipStream_t stream) {
+    using namespace ptq;
+    typedef void (*QueryFn)(SceneDev, QueryDev, RenderDev, MotionDev);
+    const QueryFn fn = src == kSrcAny       ? query_kernel<kSrcAny, false>
+                       : src == kSrcClosest ? (prune ? query_kernel<kSrcClosest, true> : query_kernel<kSrcClosest, false>)
+                       : motion             ? (prune ? query_kernel<kSrcGuides, true, true> : query_kernel<kSrcGuides, false, true>)
+                                            : (prune ? query_kernel<kSrcGuides, true, false> : query_kernel<kSrcGuides, false, false>);
+    // the tree a render traverses (guide_pass has the rule)
+    const bool fast = S->have_fast && S->opt_fast_tree;
+    SceneDev dv = S->dev;
+    tree_view(S, dv, fast ? 1 : 0, fast);
+    const int cap = fast && dv.redo_cap > dv.stack_cap ? dv.redo_cap : dv.stack_cap;
+    const uint32_t lds = (uint32_t)(kBlock / 64) * (uint32_t)cap * 64u * 4u;
+    if (S->q_cfg_fn != (const void*)fn || S->q_cfg_lds != lds) {
+        if (lds > 64 * 1024)
+            HIP_TRY(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        int occ = 0;
+        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void*)fn, kBlock, lds));
+        S->q_cfg_fn = (const void*)fn; S->q_cfg_lds = lds; S->q_cfg_occ = std::max(occ, 1);
+    }
+    // resident blocks x CUs, and no more blocks than give every lane a ray; "query_blocks" overrides both
+    // (four blocks per CU where more are resident: 1,048,576 random rays on bunny 0.789 ms on 1,024 blocks against 0.875 on 2,048
+    // and 1.134 on 512, profiles/query_time.log)
+    const int bpc = S->opt_blocks_per_cu > 0 ? (int)S->opt_blocks_per_cu : std::min(S->q_cfg_occ, 4);
+    const uint64_t by_work = ((uint64_t)q.n + (uint64_t)kBlock - 1) / (uint64_t)kBlock;
+    const int grid = S->opt_query_blocks > 0 ? (int)S->opt_query_blocks
+                                             : (int)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)S->num_cus * (uint64_t)bpc, by_work));
+    int rc;
+    if ((rc = S->q_counters.ensure((size_t)kQueryRing * kQueryCounterStride))) return rc;
+    const size_t entry = (size_t)(S->q_seq % (uint64_t)kQueryRing);
+    hipEvent_t& ev = S->q_event[entry];
+    if (!ev) {
+        HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    } else if (hipEventQuery(ev) != hipSuccess) {        // the launch that used this counter last may still run
+        (void)hipGetLastError();
+        HIP_TRY(hipStreamWaitEvent(stream, ev, 0));
+    }
+    q.counter = S->q_counters.p + entry * kQueryCounterStride;
+    q.refill = S->opt_query_refill > 0 ? (uint32_t)S->opt_query_refill : (uint32_t)kQueryRefill;
+    // the waves' first ranges are their own (pt_query.h): the counter starts behind them, and a launch they cover never reads it
+    const uint64_t first_ranges = (uint64_t)grid * (uint64_t)(kBlock / 64) * (uint64_t)kQueryChunk;
+    if (first_ranges < (uint64_t)q.n)
+        HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(q.counter), (int)first_ranges, 1, stream));
+    hipLaunchKernelGGL(fn, dim3((unsigned)grid), dim3(kBlock), lds, stream, dv, q, rd, mo);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(ev, stream));
+    S->q_seq++;
+    S->info_query_grid = grid;
+    return PT_OK;
+}
+
+// pt_trace_rays behind its null-scene check.
+int trace_rays_call(pt_scene* S, const float* rays, int32_t n, int mode, int traversal_in, float* out_tuv, int32_t* out_prim, int on_device,
+                    void* hip_stream) {
+    const char* fn = "pt_trace_rays: ";
+    if (mode != PT_QUERY_CLOSEST && mode != PT_QUERY_ANY) return fail(PT_ERR_INVALID_ARG, std::string(fn) + "unknown mode");
+    const int traversal = traversal_in == PT_TRAVERSAL_DEFAULT ? PT_TRAVERSAL_EXACT : traversal_in;
+    if (traversal != PT_TRAVERSAL_EXACT && traversal != PT_TRAVERSAL_PRUNED) return fail(PT_ERR_INVALID_ARG, std::string(fn) + "unknown traversal");
+    if (n < 0 || n > (1 << 30)) return fail(PT_ERR_INVALID_ARG, std::string(fn) + "n must be 0 .. 2^30");
+    if (n == 0) return PT_OK;
+    if (!rays) return fail(PT_ERR_INVALID_ARG, std::string(fn) + "null rays");
+    if (!out_prim) return fail(PT_ERR_INVALID_ARG, std::string(fn) + "null out_prim");
+    const bool closest = mode == PT_QUERY_CLOSEST;
+    if (closest && !out_tuv) return fail(PT_ERR_INVALID_ARG, std::string(fn) + "null out_tuv");
+    DeviceGuard guard;
+    { int grc = guard.enter(S->device); if (grc) return grc; }
+    ptq::QueryDev q{};
+    q.n = (uint32_t)n;
+    const bool prune = closest && traversal == PT_TRAVERSAL_PRUNED;      // a lane that stops at its first hit has nothing to prune by
+    const int src = closest ? ptq::kSrcClosest : ptq::kSrcAny;
+    if (on_device) {
+        q.rays = rays; q.out_tuv = closest ? out_tuv : nullptr; q.out_prim = out_prim;
+        return query_launch(S, src, prune, false, q, RenderDev{}, MotionDev{}, (hipStream_t)hip_stream);
+    }
+    int rc;
+    if ((rc = S->q_rays.ensure((size_t)n * 8)) || (closest && (rc = S->q_tuv.ensure((size_t)n * 3))) || (rc = S->q_prim.ensure((size_t)n))) return rc;
+    HIP_TRY(hipMemcpy(S->q_rays.p, rays, (size_t)n * 8 * sizeof(float), hipMemcpyHostToDevice));
+    q.rays = S->q_rays.p; q.out_tuv = closest ? S->q_tuv.p : nullptr; q.out_prim = S->q_prim.p;
+    if ((rc = query_launch(S, src, prune, false, q, RenderDev{}, MotionDev{}, nullptr))) return rc;
+    if (closest) HIP_TRY(hipMemcpy(out_tuv, S->q_tuv.p, (size_t)n * 3 * sizeof(float), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out_prim, S->q_prim.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return PT_OK;
+}
+
+// pt_render_guides_async behind its null checks: guide_pass's arguments and rules, the query kernel on the caller's stream.
+int guides_async_call(pt_scene* S, const pt_render_params* p, const pt_motion_params* m, const pt_guide_buffers& out, void* hip_stream) {
+    RenderDev rd{};
+    int traversal = 0;
+    uint64_t npix = 0;
+    int rc = guide_render_dev(p, &rd, &traversal, &npix);
+    if (rc) return rc;
+    float *motion = m ? out.motion : nullptr, *prev_depth = m ? out.prev_depth : nullptr;
+    if (npix == 0 || (!out.albedo && !out.normal && !out.depth && !out.prim && !motion && !prev_depth)) return PT_OK;
+    DeviceGuard guard;
+    { int grc = guard.enter(S->device); if (grc) return grc; }
+    MotionDev mo{};
+    if (m) {
+        guide_motion_dev(S, m, &mo);
+        mo.motion = motion;
+        mo.prev_depth = prev_depth;
+    }
+    // Camera rays are coherent: the 64 pixels of a one-shot wave walk almost the same nodes and finish together, and the
+    // refilling kernel measured slower on them at every scene and size tried.  So the automatic choice is
+    // aov_kernel, on the caller's stream and on an argument block of this call; "query_guides" = 1 or an explicit "query_blocks"
+    // takes the refilling kernel.
+    const bool refill = S->opt_query_guides == 1 || (S->opt_query_guides == 0 && S->opt_query_blocks > 0);
+    S->info_query_guides = refill ? 1 : 0;
+    if (!refill) {
+        const bool fast = S->have_fast && S->opt_fast_tree;
+        SceneDev dv = S->dev;
+        tree_view(S, dv, fast ? 1 : 0, fast);
+        const int cap = fast && dv.redo_cap > dv.stack_cap ? dv.redo_cap : dv.stack_cap;
+        const uint32_t lds = (uint32_t)(kBlock / 64) * (uint32_t)cap * 64u * 4u;
+        const dim3 grid((unsigned)((npix + kBlock - 1) / kBlock));
+        hipStream_t stream = (hipStream_t)hip_stream;
+        if (m && traversal == PT_TRAVERSAL_PRUNED)
+            hipLaunchKernelGGL((aov_kernel<true, true>), grid, dim3(kBlock), lds, stream, dv, rd, out.albedo, out.normal, out.depth, out.prim, mo);
+        else if (m)
+            hipLaunchKernelGGL((aov_kernel<false, true>), grid, dim3(kBlock), lds, stream, dv, rd, out.albedo, out.normal, out.depth, out.prim, mo);
+        else if (traversal == PT_TRAVERSAL_PRUNED)
+            hipLaunchKernelGGL((aov_kernel<true, false>), grid, dim3(kBlock), lds, stream, dv, rd, out.albedo, out.normal, out.depth, out.prim, mo);
+        else
+            hipLaunchKernelGGL((aov_kernel<false, false>), grid, dim3(kBlock), lds, stream, dv, rd, out.albedo, out.normal, out.depth, out.prim, mo);
+        HIP_TRY(hipGetLastError());
+        return PT_OK;
+    }
+    ptq::QueryDev q{};
+    q.n = (uint32_t)npix;
+    q.albedo = out.albedo; q.normal = out.normal; q.depth = out.depth; q.prim = out.prim;
+    return query_launch(S, ptq::kSrcGuides, traversal == PT_TRAVERSAL_PRUNED, m != nullptr, q, rd, mo, (hipStream_t)hip_stream);
 }
 
 // Arguments of pt_temporal_accumulate, pt_temporal_accumulate_moments and their host twins: nulls, the forbidden aliases, the
@@ -2161,7 +2337,8 @@ int pt_scene_destroy(pt_scene* S) {
     if (!S) return PT_OK;
     DeviceGuard guard;
     (void)guard.enter(S->device);
-    if (S->last_stream || S->have_timing) (void)hipDeviceSynchronize();
+    if (S->last_stream || S->have_timing || S->q_seq) (void)hipDeviceSynchronize();
+    S->drop_query();
     for (auto& T : S->tree) { T.nodes.release(); T.nodes_oct.release(); } S->drop_slots(); S->prims.release(); S->normals.release(); S->materials.release(); S->emission.release();
     S->lights.release(); S->sweep_tab.release(); S->accum.release(); S->fb_tmp.release();
     S->ad_sum.release(); S->ad_mom.release(); S->ad_list[0].release(); S->ad_list[1].release(); S->ad_count.release();
@@ -2408,6 +2585,21 @@ int pt_render_guides(pt_scene* S, const pt_render_params* p, const pt_motion_par
     return guide_pass(S, p, m, *out, on_device);
 }
 
+int pt_render_guides_async(pt_scene* S, const pt_render_params* p, const pt_motion_params* m, const pt_guide_buffers* out, void* hip_stream) {
+    if (!S) return fail(PT_ERR_INVALID_ARG, "pt_render_guides_async: null scene");
+    if (!p) return fail(PT_ERR_INVALID_ARG, "pt_render_guides_async: null p");
+    if (!out) return fail(PT_ERR_INVALID_ARG, "pt_render_guides_async: null out");
+    if (m && m->geometry != PT_MOTION_GEOMETRY_CURRENT && m->geometry != PT_MOTION_GEOMETRY_PREVIOUS)
+        return fail(PT_ERR_INVALID_ARG, "pt_motion_params.geometry must be PT_MOTION_GEOMETRY_CURRENT or PT_MOTION_GEOMETRY_PREVIOUS");
+    return guides_async_call(S, p, m, *out, hip_stream);
+}
+
+int pt_trace_rays(pt_scene* S, const float* rays, int32_t n, int mode, int traversal, float* out_tuv, int32_t* out_prim, int on_device,
+                  void* hip_stream) {
+    if (!S) return fail(PT_ERR_INVALID_ARG, "pt_trace_rays: null scene");
+    return trace_rays_call(S, rays, n, mode, traversal, out_tuv, out_prim, on_device, hip_stream);
+}
+
 int pt_temporal_accumulate(pt_scene* S, const pt_temporal_params* t, const float* color, const float* normal, const float* motion,
                            const float* prev_depth, const float* hist_color, const float* hist_normal, const float* hist_depth,
                            const float* hist_len, float* out_color, float* out_len, int on_device, void* hip_stream) {
@@ -2627,6 +2819,9 @@ int pt_scene_set_option(pt_scene* S, const char* key, int64_t value) {
     else if (k == "v2_minw") S->opt_v2_minw = value;
     else if (k == "reg_stack") { if (value != 0 && value != 1) return fail(PT_ERR_INVALID_ARG, "reg_stack must be 0 or 1"); S->opt_reg_stack = value; }
     else if (k == "leaf_sweep") { if (value != 0 && value != 1) return fail(PT_ERR_INVALID_ARG, "leaf_sweep must be 0 or 1"); S->opt_leaf_sweep = value; }
+    else if (k == "query_refill") { if (value < 0 || value > 64) return fail(PT_ERR_INVALID_ARG, "query_refill must be 0 (automatic) .. 64"); S->opt_query_refill = value; }
+    else if (k == "query_guides") { if (value < 0 || value > 2) return fail(PT_ERR_INVALID_ARG, "query_guides must be 0 (automatic), 1 or 2"); S->opt_query_guides = value; }
+    else if (k == "query_blocks") { if (value < 0 || value > 4096) return fail(PT_ERR_INVALID_ARG, "query_blocks must be 0 (automatic) .. 4096"); S->opt_query_blocks = value; }
     else return fail(PT_ERR_INVALID_ARG, "unknown option " + k);
     return PT_OK;
 }
@@ -2688,6 +2883,9 @@ int pt_scene_get_info(pt_scene* S, const char* key, int64_t* value) {
     else if (k == "reg_stack") *value = S->info_reg_stack;                // ... with the traversal stack in a register (1) or in LDS / global memory (0)
     else if (k == "block_threads") *value = S->info_kernel == 3 ? kQBlock : kBlock;
     else if (k == "frames_in_flight") *value = S->opt_frames_in_flight;
+    else if (k == "query_chunk") *value = ptq::kQueryChunk;               // ray indices a wave of the query kernel reserves per atomic
+    else if (k == "query_guides") *value = S->info_query_guides;          // the last pt_render_guides_async ran on the refilling kernel (1) or on aov_kernel (0)
+    else if (k == "query_grid") *value = S->info_query_grid;              // blocks of the last query launch (pt_trace_rays, pt_render_guides_async)
     else if (k.rfind("qdiag", 0) == 0 && k.size() >= 6 && k.size() <= 7 && k.find_first_not_of("0123456789", 5) == std::string::npos &&
              std::stoi(k.substr(5)) < 11) {
         // schedule diagnostics of the last STATS render of trace_kernel_q: counter slots [4..14], see pt_kernel_q.h

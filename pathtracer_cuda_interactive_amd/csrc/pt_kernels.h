@@ -610,40 +610,13 @@ struct MotionDev {
     float* prev_depth;              // [rows, W] or null
 };
 
-template <bool PRUNE, bool MOTION = false>
-__global__ __launch_bounds__(kBlock) void aov_kernel(SceneDev scn, RenderDev rp, float* __restrict__ albedo,
-                                                     float* __restrict__ normal, float* __restrict__ depth,
-                                                     int32_t* __restrict__ prim, MotionDev mo = MotionDev{}) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    ptd::SceneView sv;
-    sv.nodes = scn.nodes; sv.prims = scn.prims; sv.normals = scn.normals;
-    sv.materials = scn.materials; sv.emission = scn.emission; sv.lights = scn.lights;
-    sv.top_nodes = nullptr; sv.top_count = 0;
-    sv.node_stride = sizeof(DNode);
-    sv.num_emission = scn.num_emission; sv.root_ref = scn.root_ref; sv.fixed_order = scn.fixed_order;
-    sv.ref_nodes = scn.ref_nodes; sv.ref_path = scn.ref_path; sv.ref_anc = scn.ref_anc; sv.ref_levels = scn.ref_levels;
-    sv.bg = ptm::mk(0, 0, 0);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int cap = scn.fallback && scn.redo_cap > scn.stack_cap ? scn.redo_cap : scn.stack_cap;   // one column serves both trees
-    int32_t* stk = reinterpret_cast<int32_t*>(smem) + (size_t)wave * cap * 64 + lane;
-    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= rp.npix) return;
-    const uint32_t row = fastdiv(k, rp.div_width);
-    const int i = (int)(k - row * (uint32_t)rp.width);
-    const int j = rp.row_begin + (int)row * rp.row_step;
-    const float u = ((float)i + 0.5f) / (float)rp.width;
-    const float v = ((float)j + 0.5f) / (float)rp.height;
-    const ptd::Ray r = ptd::primary_ray(rp, u, v);
-    ptd::TravStats st;
-    ptd::Hit h;
-    if (scn.fallback) {
-        ptd::SceneView sv_ref = sv;
-        sv_ref.nodes = scn.ref_nodes; sv_ref.root_ref = scn.ref_root_ref; sv_ref.fixed_order = 0;
-        bool rerun;
-        h = ptd::intersect_any_tree<PRUNE>(sv, sv_ref, r, stk, rerun);
-    } else {
-        h = ptd::intersect<PRUNE, false>(sv, r, stk, st);
-    }
+// What pixel k's guide buffers get from the closest hit `h` of its pixel-centre ray `r` (the rule above), written once for
+// aov_kernel and for the lane-refilling query kernel (pt_query.h): make_surface, the emission / albedo / normal rule, and with
+// MOTION the surface point followed into the previous records and projected into the previous camera.
+template <bool MOTION>
+__device__ __forceinline__ void write_guides(const ptd::SceneView& sv, const RenderDev& rp, const ptd::Ray& r, const ptd::Hit& h,
+                                             const uint32_t k, float* __restrict__ albedo, float* __restrict__ normal,
+                                             float* __restrict__ depth, int32_t* __restrict__ prim, const MotionDev& mo) {
     ptm::V3 n = ptm::mk(0.0f, 0.0f, 0.0f), a = n;
     float t = 0.0f;
     if (h.prim >= 0) {
@@ -688,6 +661,43 @@ __global__ __launch_bounds__(kBlock) void aov_kernel(SceneDev scn, RenderDev rp,
         if (mo.motion) { mo.motion[2 * (size_t)k] = mx; mo.motion[2 * (size_t)k + 1] = my; }
         if (mo.prev_depth) mo.prev_depth[k] = pz;
     }
+}
+
+template <bool PRUNE, bool MOTION = false>
+__global__ __launch_bounds__(kBlock) void aov_kernel(SceneDev scn, RenderDev rp, float* __restrict__ albedo,
+                                                     float* __restrict__ normal, float* __restrict__ depth,
+                                                     int32_t* __restrict__ prim, MotionDev mo = MotionDev{}) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    ptd::SceneView sv;
+    sv.nodes = scn.nodes; sv.prims = scn.prims; sv.normals = scn.normals;
+    sv.materials = scn.materials; sv.emission = scn.emission; sv.lights = scn.lights;
+    sv.top_nodes = nullptr; sv.top_count = 0;
+    sv.node_stride = sizeof(DNode);
+    sv.num_emission = scn.num_emission; sv.root_ref = scn.root_ref; sv.fixed_order = scn.fixed_order;
+    sv.ref_nodes = scn.ref_nodes; sv.ref_path = scn.ref_path; sv.ref_anc = scn.ref_anc; sv.ref_levels = scn.ref_levels;
+    sv.bg = ptm::mk(0, 0, 0);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int cap = scn.fallback && scn.redo_cap > scn.stack_cap ? scn.redo_cap : scn.stack_cap;   // one column serves both trees
+    int32_t* stk = reinterpret_cast<int32_t*>(smem) + (size_t)wave * cap * 64 + lane;
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= rp.npix) return;
+    const uint32_t row = fastdiv(k, rp.div_width);
+    const int i = (int)(k - row * (uint32_t)rp.width);
+    const int j = rp.row_begin + (int)row * rp.row_step;
+    const float u = ((float)i + 0.5f) / (float)rp.width;
+    const float v = ((float)j + 0.5f) / (float)rp.height;
+    const ptd::Ray r = ptd::primary_ray(rp, u, v);
+    ptd::TravStats st;
+    ptd::Hit h;
+    if (scn.fallback) {
+        ptd::SceneView sv_ref = sv;
+        sv_ref.nodes = scn.ref_nodes; sv_ref.root_ref = scn.ref_root_ref; sv_ref.fixed_order = 0;
+        bool rerun;
+        h = ptd::intersect_any_tree<PRUNE>(sv, sv_ref, r, stk, rerun);
+    } else {
+        h = ptd::intersect<PRUNE, false>(sv, r, stk, st);
+    }
+    write_guides<MOTION>(sv, rp, r, h, k, albedo, normal, depth, prim, mo);
 }
 
 // Inner-node visits of a fixed set of probe rays through the tree `scn` points at (pt_api.hip: validate_and_build chooses

@@ -96,6 +96,7 @@ class PtDenoiseParams(C.Structure):
 
 
 PT_MOTION_GEOMETRY_CURRENT, PT_MOTION_GEOMETRY_PREVIOUS = 0, 1                # pt_motion_params.geometry
+PT_QUERY_CLOSEST, PT_QUERY_ANY = 0, 1                                         # pt_trace_rays modes
 
 
 class PtTransform(C.Structure):
@@ -148,6 +149,12 @@ SPARSE_ARGTYPES = {
     "pt_temporal_gradient_sparse": [C.c_void_p, C.POINTER(PtGradientParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                     C.c_void_p],
     "pt_temporal_gradient_sparse_host": [C.POINTER(PtGradientParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+}
+
+# ... and of the ray query and the asynchronous guide pass.
+QUERY_ARGTYPES = {
+    "pt_trace_rays": [C.c_void_p, C.c_void_p, C.c_int32, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p],
+    "pt_render_guides_async": [C.c_void_p, C.POINTER(PtRenderParams), C.POINTER(PtMotionParams), C.POINTER(PtGuideBuffers), C.c_void_p],
 }
 
 

@@ -9,8 +9,8 @@ import os
 import numpy as np
 
 from . import _build
-from .ctypes_defs import (PT_MOTION_GEOMETRY_CURRENT, PT_MOTION_GEOMETRY_PREVIOUS, PT_OK, PT_SHAPE_SPHERE, PT_TRAVERSAL_DEFAULT,
-                          PT_UPDATE_GEOMETRY, PT_UPDATE_SHADING, SPARSE_ARGTYPES, PtAdaptiveParams, PtBvhNode, PtCounters, PtDenoiseParams, PtError,
+from .ctypes_defs import (PT_MOTION_GEOMETRY_CURRENT, PT_MOTION_GEOMETRY_PREVIOUS, PT_OK, PT_QUERY_ANY, PT_QUERY_CLOSEST, PT_SHAPE_SPHERE,
+                          PT_TRAVERSAL_DEFAULT, PT_UPDATE_GEOMETRY, PT_UPDATE_SHADING, QUERY_ARGTYPES, SPARSE_ARGTYPES, PtAdaptiveParams, PtBvhNode, PtCounters, PtDenoiseParams, PtError,
                           PtGradientParams, PtGuideBuffers, PtLight, PtMaterial, PtMesh, PtMotionParams, PtRenderParams, PtSceneDesc, PtShape,
                           PtTemporalIo, PtTemporalParams, PtTransform, PtVdenoiseParams)
 from .host import NODE_DTYPE  # noqa: F401  (one definition; callers also read it from here)
@@ -27,6 +27,7 @@ EXPORTS = [
     "pt_temporal_gradient", "pt_temporal_gradient_host", "pt_temporal_accumulate_adaptive", "pt_temporal_accumulate_adaptive_host",
     "pt_render_pixels", "pt_gradient_pixels", "pt_gradient_pixels_host", "pt_temporal_gradient_sparse", "pt_temporal_gradient_sparse_host",
     "pt_scene_set_groups", "pt_scene_transform", "pt_transform_geometry_host", "pt_transform_sphere_host",
+    "pt_trace_rays", "pt_render_guides_async",
 ]
 
 
@@ -65,7 +66,7 @@ def lib():
         L.pt_denoise_variance_host.argtypes = [C.POINTER(PtVdenoiseParams)] + [vp] * 8
         L.pt_temporal_gradient.argtypes = [vp, C.POINTER(PtGradientParams), vp, vp, vp, C.c_int, vp]
         L.pt_temporal_gradient_host.argtypes = [C.POINTER(PtGradientParams), vp, vp, vp]
-        for name, argtypes in SPARSE_ARGTYPES.items():
+        for name, argtypes in list(SPARSE_ARGTYPES.items()) + list(QUERY_ARGTYPES.items()):
             getattr(L, name).argtypes = argtypes
         L.pt_temporal_accumulate_adaptive.argtypes = [vp, C.POINTER(PtTemporalParams), C.c_float, C.POINTER(PtTemporalIo), vp, C.c_int32,
                                                       C.c_int, vp]
@@ -254,6 +255,33 @@ class DeviceScene:
         g = PtGuideBuffers(*(ptr or None for ptr in (albedo_ptr, normal_ptr, depth_ptr, prim_ptr, motion_ptr, prev_depth_ptr)))
         m = motion_params(prev_camera, previous_geometry)
         _check(lib().pt_render_guides(self._h, C.byref(p), C.byref(m), C.byref(g), 1))
+
+    def render_guides_async_into(self, params, prev_camera=None, previous_geometry=False, albedo_ptr=0, normal_ptr=0, depth_ptr=0,
+                                 prim_ptr=0, motion_ptr=0, prev_depth_ptr=0, stream=None, traversal=None):
+        """pt_render_guides_async: render_guides_into's buffers and bits, enqueued on a HIP stream without a host sync.
+        prev_camera None: pt_render_aov's four buffers only (no motion parameters are passed)."""
+        p = params.copy()
+        if traversal is not None:
+            p.traversal = traversal
+        g = PtGuideBuffers(*(ptr or None for ptr in (albedo_ptr, normal_ptr, depth_ptr, prim_ptr, motion_ptr, prev_depth_ptr)))
+        m = C.byref(motion_params(prev_camera, previous_geometry)) if prev_camera is not None else None
+        _check(lib().pt_render_guides_async(self._h, C.byref(p), m, C.byref(g), C.c_void_p(stream or 0)))
+
+    def trace_rays(self, rays, mode=PT_QUERY_CLOSEST, traversal=PT_TRAVERSAL_DEFAULT):
+        """pt_trace_rays on a host array of rays [n, 8] ({org, dir, tnear, tfar}).  Blocking.  PT_QUERY_CLOSEST: (tuv [n, 3]
+        float32, prim [n] int32), what intersect() returns; PT_QUERY_ANY: hit [n] int32, 1 where the ray hits anything."""
+        rays = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 8)
+        n = rays.shape[0]
+        prim = np.zeros(n, dtype=np.int32)
+        tuv = np.zeros((n, 3), dtype=np.float32) if mode == PT_QUERY_CLOSEST else None
+        _check(lib().pt_trace_rays(self._h, *_ptrs([rays]), n, int(mode), int(traversal), *_ptrs([tuv, prim]), 0, None))
+        return (tuv, prim) if mode == PT_QUERY_CLOSEST else prim
+
+    def trace_rays_into(self, rays_ptr, n, tuv_ptr, prim_ptr, mode=PT_QUERY_CLOSEST, traversal=PT_TRAVERSAL_DEFAULT, stream=None):
+        """pt_trace_rays on device memory (rays_ptr: [n, 8] float32, tuv_ptr: [n, 3] float32 or 0 with PT_QUERY_ANY, prim_ptr: [n]
+        int32), enqueued on a HIP stream without a host sync.  The rays must stay valid until the stream has passed the call."""
+        _check(lib().pt_trace_rays(self._h, C.c_void_p(rays_ptr or 0), int(n), int(mode), int(traversal), C.c_void_p(tuv_ptr or 0),
+                                   C.c_void_p(prim_ptr or 0), 1, C.c_void_p(stream or 0)))
 
     def temporal_accumulate(self, color, normal, motion, prev_depth, history=None, **kw):
         """pt_temporal_accumulate on host arrays: (out_color [H, W, 3], out_len [H, W]) as new arrays.  history: None or

@@ -2,7 +2,7 @@
 
   python tools/animate.py SCENE.pts [--frames 8] [--size 640x480] [--spp 2] [--translate DX,DY,DZ | --orbit DEG] [--wobble]
                           [--denoise | --variance | --gradient | --gradient-sparse] [--relight K:R,G,B] [--reference-spp N] [--out PREFIX] [--time]
-                          [--spin G:AXIS:DEG_PER_FRAME ...]
+                          [--spin G:AXIS:DEG_PER_FRAME ...] [--async-guides]
 
 Per frame: pt_render at --spp, pt_render_guides against the previous frame's camera (and, with --wobble, the previous
 geometry: every mesh gets device.wobbled_desc's per-vertex wobble through DeviceScene.update), pt_temporal_accumulate, and with
@@ -21,6 +21,8 @@ parameters at that list on the current scene (stage "list"), and pt_temporal_gra
 --spin G:AXIS:DEG_PER_FRAME (repeatable): object G — mesh G, or sphere G - num_meshes, device.groups_by_object's
 numbering — turns about the x, y or z axis through its centroid by that many degrees per frame through DeviceScene.transform: the
 matrices go to the device, no vertex is touched on the host, and the guides follow the previous transform's records.  Not with --wobble.
+--async-guides: the guide stage is pt_render_guides_async on the frame's stream, so a frame is enqueued stage after
+stage without a host sync in between; the images are the same, bit for bit.
 --relight K:R,G,B: from frame K on every light's radiance is scaled by (R, G, B) through DeviceScene.update(shading=True).
 --time: after the animation, each stage again on the last frame's inputs, warm, in windows of at least 0.5 s, with
 pt_render_aov and one pt_denoise iteration as yardsticks and the bytes pt_temporal_accumulate must move."""
@@ -138,6 +140,7 @@ def main():
     ap.add_argument("--reference-spp", type=int, default=0)
     ap.add_argument("--out", default="")
     ap.add_argument("--time", action="store_true")
+    ap.add_argument("--async-guides", action="store_true")
     a = ap.parse_args()
     a.gradient = a.gradient or a.gradient_sparse
     a.variance = a.variance or a.gradient
@@ -218,9 +221,12 @@ def main():
             times["rows"].append(once(lambda: ds.render_into(dev.gradient_rows_params(p_prev), rows.data_ptr(), stream)) if k else 0.0)
             times["gradient"].append(once(lambda: ds.temporal_gradient_into(w, h, old["color"].data_ptr(), rows.data_ptr(),
                                                                             lam.data_ptr(), stream)) if k else 0.0)
-        times["guides"].append(once(lambda: ds.render_guides_into(
-            p, p_prev or p, previous_geometry=True, albedo_ptr=albedo.data_ptr(), normal_ptr=cur["normal"].data_ptr(),
-            depth_ptr=cur["depth"].data_ptr(), motion_ptr=motion.data_ptr(), prev_depth_ptr=prev_depth.data_ptr())))
+        guide_ptrs = dict(albedo_ptr=albedo.data_ptr(), normal_ptr=cur["normal"].data_ptr(), depth_ptr=cur["depth"].data_ptr(),
+                          motion_ptr=motion.data_ptr(), prev_depth_ptr=prev_depth.data_ptr())
+        if a.async_guides:
+            times["guides"].append(once(lambda: ds.render_guides_async_into(p, p_prev or p, previous_geometry=True, stream=stream, **guide_ptrs)))
+        else:
+            times["guides"].append(once(lambda: ds.render_guides_into(p, p_prev or p, previous_geometry=True, **guide_ptrs)))
         hist = [old[n].data_ptr() for n in ("out", "normal", "depth", "length")] if k else None
         if a.variance:
             hist5 = hist + [old["moments"].data_ptr()] if k else None
@@ -288,6 +294,9 @@ def main():
         t["pt_render_guides (4 buffers + motion)"] = timed(lambda: ds.render_guides_into(
             p, p_prev, previous_geometry=True, albedo_ptr=albedo.data_ptr(), normal_ptr=scratch.data_ptr(), depth_ptr=cur["depth"].data_ptr(),
             motion_ptr=motion.data_ptr(), prev_depth_ptr=prev_depth.data_ptr()))
+        t["pt_render_guides_async (4 buffers + motion)"] = timed(lambda: ds.render_guides_async_into(
+            p, p_prev, previous_geometry=True, albedo_ptr=albedo.data_ptr(), normal_ptr=scratch.data_ptr(), depth_ptr=cur["depth"].data_ptr(),
+            motion_ptr=motion.data_ptr(), prev_depth_ptr=prev_depth.data_ptr(), stream=stream))
         t["pt_temporal_accumulate"] = timed(lambda: ds.temporal_accumulate_into(
             w, h, color.data_ptr(), cur["normal"].data_ptr(), motion.data_ptr(), prev_depth.data_ptr(), hist, scratch.data_ptr(),
             cur["length"].data_ptr(), stream, **TEMPORAL))

@@ -93,9 +93,18 @@ int pt_oracle_intersect_work(const pt_scene_desc* scene, const float* rays, int 
  *   DIFFUSE_NO_INV_PI  eval_brdf's diffuse value without the 1/pi (scene.h:370-375), pdf unchanged
  *   RR_NO_WEIGHT       Russian-roulette survivors keep their throughput (radiance.cuh:68-74 without the division)
  *   SCHLICK_POW4       (1 - cos)^4 instead of ^5 in schlick_fresnel (scene.h:333-336)
- *   RR_FLOOR_QUARTER   CONTROL: roulette floor 0.25 instead of 0.5 — another estimator with the SAME expectation */
+ *   RR_FLOOR_QUARTER   CONTROL: roulette floor 0.25 instead of 0.5 — another estimator with the SAME expectation
+ * Mutations of the light sample (PT_RENDER_NEE; tests/test_nee_reference.py names the case that must catch each):
+ *   NEE_NO_NUM_LIGHTS    the weight without the factor num_lights
+ *   NEE_COS_SHADING      the emitter's cosine from its shading normal instead of the geometric one
+ *   NEE_NO_LOBE_WEIGHT   PLASTIC's light sample without 1/(1 - F)
+ *   NEE_BOTH_SIDES       no test of the emitting side
+ *   NEE_COUNT_EMISSION   emission found by BSDF sampling always counted (emitters counted twice)
+ *   NEE_TFAR_FULL        an area light's shadow ray runs the whole distance d, so the light shadows itself */
 enum { PT_ORACLE_MUT_DIFFUSE_NO_INV_PI = 1, PT_ORACLE_MUT_RR_NO_WEIGHT = 2, PT_ORACLE_MUT_SCHLICK_POW4 = 4,
-       PT_ORACLE_MUT_RR_FLOOR_QUARTER = 8 };
+       PT_ORACLE_MUT_RR_FLOOR_QUARTER = 8,
+       PT_ORACLE_MUT_NEE_NO_NUM_LIGHTS = 16, PT_ORACLE_MUT_NEE_COS_SHADING = 32, PT_ORACLE_MUT_NEE_NO_LOBE_WEIGHT = 64,
+       PT_ORACLE_MUT_NEE_BOTH_SIDES = 128, PT_ORACLE_MUT_NEE_COUNT_EMISSION = 256, PT_ORACLE_MUT_NEE_TFAR_FULL = 512 };
 int pt_oracle_set_mutation(int bits);
 
 /* math KATs: op 0 sincos(x)->(out0=sin,out1=cos); op 1 powf(x,y)->out0; math_mode as above */

@@ -366,7 +366,8 @@ static inline v3 FN(nee_brdf)(const pt_scene_desc* sc, const o_isect* isect, v3 
         float F0s = q * q;
         v3 F = FN(schlick_fresnel)(v3make(F0s, F0s, F0s), v3dot(n, wi));
         float inv = 1.0f / (1 - F.x);
-        value = v3scale(value, inv);
+        if (!(g_oracle_mutation & PT_ORACLE_MUT_NEE_NO_LOBE_WEIGHT))   /* test hook */
+            value = v3scale(value, inv);
     }
     return value;
 }
@@ -407,6 +408,7 @@ static inline int FN(nee_sample)(const pt_scene_desc* sc, const o_isect* isect, 
         v3 f = FN(nee_brdf)(sc, isect, n, wi, wl);
         if (!(OFMAXF(OFMAXF(f.x, f.y), f.z) > 0)) return 0;
         float w = ((float)nl * geom) / d2;
+        if (g_oracle_mutation & PT_ORACLE_MUT_NEE_NO_NUM_LIGHTS) w = geom / d2;   /* test hook */
         *contrib = v3mul(throughput, v3scale(v3mul(f, le), w));
         shadow->org = p; shadow->dir = wl; shadow->tnear = 1e-4f; shadow->tfar = d;
         return 1;
@@ -455,14 +457,18 @@ static inline int FN(nee_sample)(const pt_scene_desc* sc, const o_isect* isect, 
     float d = sqrtf(d2);
     float invd = 1.0f / d;
     v3 wl = v3scale(dv, invd);
-    if (!(v3dot(v3neg(wl), nx) > 0)) return 0;          /* radiance.cuh:38: emits towards dot(-ray.dir, n) > 0 only */
+    if (!(v3dot(v3neg(wl), nx) > 0) && !(g_oracle_mutation & PT_ORACLE_MUT_NEE_BOTH_SIDES))   /* test hook in the second term */
+        return 0;                                       /* radiance.cuh:38: emits towards dot(-ray.dir, n) > 0 only */
     float cosg = fabsf(v3dot(wl, ng));
+    if (g_oracle_mutation & PT_ORACLE_MUT_NEE_COS_SHADING) cosg = fabsf(v3dot(wl, nx));   /* test hook */
     geom = cosg * area;
     v3 f = FN(nee_brdf)(sc, isect, n, wi, wl);
     if (!(OFMAXF(OFMAXF(f.x, f.y), f.z) > 0)) return 0;
     float w = ((float)nl * geom) / d2;
+    if (g_oracle_mutation & PT_ORACLE_MUT_NEE_NO_NUM_LIGHTS) w = geom / d2;   /* test hook */
     *contrib = v3mul(throughput, v3scale(v3mul(f, le), w));
     shadow->org = p; shadow->dir = wl; shadow->tnear = 1e-4f; shadow->tfar = d * (1.0f - 1e-4f);
+    if (g_oracle_mutation & PT_ORACLE_MUT_NEE_TFAR_FULL) shadow->tfar = d;   /* test hook */
     return 1;
 }
 
@@ -516,6 +522,7 @@ static v3 FN(radiance)(const pt_scene_desc* sc, o_ray ray, o_pcg32* rng, int max
                 cnt->nee_hits++;
             }
             count_emission = peek.is_pure_specular;
+            if (g_oracle_mutation & PT_ORACLE_MUT_NEE_COUNT_EMISSION) count_emission = 1;   /* test hook */
             nee_sampling = peek;
         }
         FN(sampling_record) sampling = nee ? nee_sampling : FN(sample_brdf)(sc, &hit, n, wi, rng, cnt);

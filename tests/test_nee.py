@@ -2,7 +2,9 @@
 light (point lights parsed and unused, light.h:5-8; occlusion query dead, scene.h:306-330), so nothing reference-held
 pins it.  What is tested: (1) the estimator is the SAME image as the reference's BSDF-sampling estimator wherever all
 light comes from area lights (expectation equal, variance lower); (2) point lights light a scene as the closed form
-says; (3) the HIP path equals the oracle's NEE restatement bit for bit on every material, primitive and residency."""
+says; (3) the HIP path equals the oracle's NEE restatement bit for bit on every material, primitive and residency.
+What holds the estimator itself — every factor of the light sample, against fp64 quadrature and depth identities, oracle
+and HIP path alike — is tests/test_nee_reference.py."""
 import numpy as np
 import pytest
 from conftest import assert_bit_equal, load_scene, random_scene

@@ -261,6 +261,45 @@ int pt_transform_geometry_host(const pt_transform* t, int32_t n, const float* po
                                float* positions_out, float* normals_out);
 int pt_transform_sphere_host(const pt_transform* t, const float* center, float radius, float* center_out, float* radius_out);
 
+/* A fresh internal tree on a live handle — an EXTENSION, like pt_scene_update: off unless called; no other entry point's output
+ * changes by a bit and a handle that never calls it behaves and is timed as before.  pt_scene_update and pt_scene_transform keep
+ * the topology of both trees; the internal tree's quality then decays with the geometry (6.8 x the node visits
+ * on a grid of 343 cubes that traded places).  This call builds the internal tree anew over the leaf boxes the handle's copy of
+ * the caller's tree holds now — the caller's own boxes before any geometry update, the exact ones after — by pt_scene_create's
+ * own internal-tree stage (on the device from 4096 shapes, on the host below), probes it against the caller's tree as it stands
+ * with pt_scene_create's rays and adopts it iff it visits at least 10 % fewer nodes.  Any tree over the same leaf boxes
+ * renders the same bits, so a rebuilt handle is a freshly created one, frame for frame and node visit for node
+ * visit, that has kept what a new handle loses: the previous-geometry records pt_render_guides reads, the rest records and the
+ * group assignment, frame slots, options, timing rings and counters.  The caller's tree, its refit plan and the tie tables are
+ * never touched (the tables hold the caller's topology only).
+ *   flags must be 0 (reserved): PT_ERR_INVALID_ARG otherwise and for a NULL scene.
+ *   PT_ERR_UNSUPPORTED, pt_last_error() saying which, when the handle holds no tie tables — pt_scene_create kept no internal tree:
+ *   fewer than 16 shapes, boxes that do not nest, the sweep tree lost the probe on an LDS-resident scene, or no room for the
+ *   tables.  A handle whose internal tree is the caller's own topology ("fast_tree_is_callers" 1) is eligible.
+ *   Blocking, on the default stream, with pt_scene_update's two synchronises.  Everything is made in new buffers; a call that
+ *   fails (out of memory, a HIP error, the builder refusing) leaves the handle exactly as it was.
+ *   Adopted: the internal tree, its depth, stack cap, top prefix and octant tables are replaced, "fast_tree" is 1,
+ *   "fast_tree_is_callers" 0, "fast_tree_cost_permille" the new ratio, "sweep_on_device" follows the new build; the tree's refit
+ *   plan is built again inside this call where the handle had one; scenes of at most 64 primitives get their box sweep back
+ *   under pt_scene_create's admission rules.  Not adopted: PT_OK all the same, the handle keeps the internal tree it had and
+ *   nothing observable changes but the keys below.
+ *   pt_scene_get_info: "rebuilds" = successful calls; "rebuild_adopted" = the last one adopted its tree; "rebuild_cost_permille" =
+ *   the last candidate's probe ratio; "rebuild_us0".."rebuild_us3" = wall microseconds of the last one: total, leaf boxes + build,
+ *   re-layout + probe, plan + sweep tables.
+ * When to call it — pt_scene_set_option "tree_cost" 1 (default 0): every geometry update and transform also measures both trees'
+ * cost, the sum over every inner node below the root of its box area in fp64 (e = (double)max - (double)min per axis,
+ * a = 2.0 * ((ex ey + ey ez) + ez ex), no contraction), on the device in a fixed order (csrc/pt_tree_cost.hip: the same bits on
+ * every run), read back without a further synchronise.  "tree_cost0_bits" / "tree_cost1_bits" = the fp64 bit pattern of the
+ * caller's / the internal tree's cost after the last refit (0: no tree, nothing measured); "tree_cost0_permille" /
+ * "tree_cost1_permille" = (int64)(1000.0 * now / reference + 0.5), the reference being the cost of the boxes as they stood
+ * before the first refit after the option was set; 1000 before any refit.  An adopted rebuild makes the new tree's cost the
+ * internal tree's reference, one that was not adopted makes the current cost the reference.  pt_host_tree_cost (pt_host.h) is
+ * the host twin.  Option "rebuild_at_permille" (default 0 = never, else >= 1001; implies the telemetry): a successful
+ * pt_scene_update(PT_UPDATE_GEOMETRY) or pt_scene_transform whose "tree_cost1_permille" is at or above the value rebuilds inside
+ * the same call, after the refit and before the closing synchronise ("update_us0" / "transform_us0" include it).  A rebuild that
+ * fails there does not fail the update; "rebuilds_auto" counts the ones that succeeded. */
+int pt_scene_rebuild(pt_scene* scene, int flags);
+
 /* Blocking render.  `fb` receives rows x width x 3 floats, rows = the rows
  * selected by (row_begin,row_end,row_stride), packed in increasing row order;
  * fb[(r*W+i)*3+c], linear radiance, row 0 = top (main.cu:35,50).

@@ -73,6 +73,11 @@ int pt_host_scene_bvh_depth(const pt_host_scene* s);       /* computeMaxDepth, b
  * desc->num_nodes nodes (it may be desc->nodes).  It is the tree pt_scene_update (pt_api.h) refits a handle to: what a caller
  * uses to keep their own pool in step with a live handle.  PT_ERR_BAD_SCENE for ids or child indices out of range. */
 int pt_host_refit_bvh(const pt_scene_desc* desc, pt_bvh_node* out_nodes);
+/* The cost of desc's node pool as pt_scene_set_option "tree_cost" measures a handle's trees (pt_api.h): the sum, over every
+ * inner node but the root, of its box area in fp64 — e = (double)max - (double)min per axis, a = 2.0 * ((ex ey + ey ez) + ez ex),
+ * operations in that order, no contraction — added in pool index order.  The device adds the same terms in another fixed
+ * order: the two agree to the rounding of a sum of num_shapes - 2 positive terms, not bit for bit.  Needs no GPU. */
+int pt_host_tree_cost(const pt_scene_desc* desc, double* out);
 /* The vertex normals pt_host_scene_add_mesh(normals = NULL) computes (compute_normals.cpp:13-51), for a caller whose mesh
  * deforms: out_normals [num_vertices*3]. */
 int pt_host_compute_normals(const float* positions, int num_vertices, const int32_t* indices, int num_faces,

@@ -203,6 +203,23 @@ int pt_host_refit_bvh(const pt_scene_desc* d, pt_bvh_node* out) {
     });
 }
 
+int pt_host_tree_cost(const pt_scene_desc* d, double* out) {
+    if (!d || !out || !d->nodes || d->num_nodes <= 0 || d->root < 0 || d->root >= d->num_nodes) {
+        g_err = "bad argument";
+        return PT_ERR_INVALID_ARG;
+    }
+    double sum = 0.0;
+    for (int k = 0; k < d->num_nodes; k++) {
+        const pt_bvh_node& nd = d->nodes[k];
+        if (k == d->root || nd.prim != -1) continue;
+        const double ex = (double)nd.bmax[0] - (double)nd.bmin[0], ey = (double)nd.bmax[1] - (double)nd.bmin[1],
+                     ez = (double)nd.bmax[2] - (double)nd.bmin[2];
+        sum = sum + 2.0 * ((ex * ey + ey * ez) + ez * ex);
+    }
+    *out = sum;
+    return PT_OK;
+}
+
 int pt_host_compute_normals(const float* positions, int num_vertices, const int32_t* indices, int num_faces, float* out_normals) {
     if (!positions || !indices || !out_normals || num_vertices <= 0 || num_faces <= 0) { g_err = "bad mesh arguments"; return PT_ERR_INVALID_ARG; }
     return guard([&] {

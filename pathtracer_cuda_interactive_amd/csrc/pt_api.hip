@@ -26,6 +26,7 @@
 #include "pt_sweep_build.h"
 #include "pt_scene_prep.h"
 #include "pt_scene_refit.h"
+#include "pt_tree_cost.h"
 #include "pt_scene_transform.h"
 #include "pt_transform.h"
 #include "pt_denoise.h"
@@ -201,6 +202,21 @@ struct pt_scene {
     DevBuf<DNormals> rest_normals;
     bool have_rest = false;
     int64_t transforms = 0, transform_us[4] = {0, 0, 0, 0};   // [0] total [1] records [2] refit [3] snapshot + plan build
+    // pt_scene_rebuild: calls that succeeded, those among them a policy made (option rebuild_at_permille), whether the last one
+    // adopted its tree and that tree's probe ratio; wall time: [0] total [1] leaf boxes + build [2] re-layout + probe
+    // [3] plan + sweep tables.  no_fast_why: why pt_scene_create kept no internal tree (the refusal's message).
+    int64_t rebuilds = 0, rebuilds_auto = 0, rebuild_adopted = 0, rebuild_cost_permille = 0, rebuild_us[4] = {0, 0, 0, 0};
+    const char* no_fast_why = "";
+    // tree-cost telemetry (pt_tree_cost.hip; options tree_cost, rebuild_at_permille): per tree the cost of the boxes as built
+    // (taken before the first refit that follows) and after the last refit.  cost_dev / cost_host: [0..1] reference, [2..3]
+    // current, device results and their pinned host copies; the copies are enqueued behind the refit and read once the call
+    // has synchronised (cost_pending_*).
+    int64_t opt_tree_cost = 0, opt_rebuild_at = 0;
+    DevBuf<double> cost_partials, cost_dev;
+    double* cost_host = nullptr;
+    double cost_ref[2] = {0.0, 0.0}, cost_now[2] = {0.0, 0.0};
+    bool cost_have_ref[2] = {false, false}, cost_pending_ref[2] = {false, false}, cost_pending_now[2] = {false, false};
+    bool cost_on() const { return opt_tree_cost != 0 || opt_rebuild_at != 0; }
     bool tri_only = false;           // the scene holds no sphere
     bool diffuse_only = false;       // every material is DIFFUSE
     // scratch
@@ -343,8 +359,8 @@ namespace {
 
 // Points a kernel argument block (select_tree: the handle's own) at one of the two trees; fallback: exact traversal on the internal tree — ties settled in the
 // caller's visit order, rays with a zero direction component traced on tree[0].
-void tree_view(const pt_scene* S, SceneDev& dv, int which, bool fallback) {
-    const pt_scene::Tree& T = S->tree[which];
+// (T: the tree itself — S->tree[which], or pt_scene_rebuild's candidate for tree[1])
+void tree_view(const pt_scene* S, SceneDev& dv, const pt_scene::Tree& T, int which, bool fallback) {
     dv.nodes = T.nodes.p;
     dv.nodes_oct = T.have_oct ? T.nodes_oct.p : nullptr;
     dv.num_nodes = T.num_nodes;
@@ -360,6 +376,7 @@ void tree_view(const pt_scene* S, SceneDev& dv, int which, bool fallback) {
     dv.ref_anc = S->ref_anc.p;
     dv.ref_levels = S->ref_levels;
 }
+void tree_view(const pt_scene* S, SceneDev& dv, int which, bool fallback) { tree_view(S, dv, S->tree[which], which, fallback); }
 void select_tree(pt_scene* S, int which, bool fallback = false) { tree_view(S, S->dev, which, fallback); }
 
 struct TreeHost {
@@ -559,6 +576,119 @@ int pack_shading(const pt_scene_desc* d, int N, std::vector<DMaterial>& mats, st
     return PT_OK;
 }
 
+// ---- the internal-tree stage: what pt_scene_create and pt_scene_rebuild both run ---------------------------------------------
+// A tree the host made, into T's buffers with its metadata.
+int upload_tree(pt_scene::Tree& T, const TreeHost& H) {
+    const std::vector<DNode>& nodes = H.nodes;
+    // 8 ray-octant copies of the node table for LDS-resident scenes: octant bit k set <=> 1/d[k] < 0, in which case
+    // Hit() swaps the two slab distances of axis k (bbox.cuh:40-55); here the two planes are swapped instead.
+    T.have_oct = false;
+    if (nodes.size() * 8 * sizeof(DNode) <= kOctNodeLimit) {
+        std::vector<DNode> nodes_oct(nodes.size() * 8);
+        for (int o = 0; o < 8; o++)
+            for (size_t k = 0; k < nodes.size(); k++) {
+                DNode n = nodes[k];
+                for (int ax = 0; ax < 3; ax++)
+                    if (o & (1 << ax)) { std::swap(n.lmin[ax], n.lmax[ax]); std::swap(n.rmin[ax], n.rmax[ax]); }
+                nodes_oct[(size_t)o * nodes.size() + k] = n;
+            }
+        int r;
+        if ((r = T.nodes_oct.ensure(nodes_oct.size()))) return r;
+        HIP_TRY(hipMemcpy(T.nodes_oct.p, nodes_oct.data(), nodes_oct.size() * sizeof(DNode), hipMemcpyHostToDevice));
+        T.have_oct = true;
+    }
+    int r;
+    if ((r = T.nodes.ensure(nodes.size()))) return r;
+    HIP_TRY(hipMemcpy(T.nodes.p, nodes.data(), nodes.size() * sizeof(DNode), hipMemcpyHostToDevice));
+    T.num_nodes = (int32_t)nodes.size();
+    T.root_ref = H.root_ref;
+    T.stack_cap = H.stack_need + 1;                         // + the kDone sentinel at the bottom
+    T.top_avail = H.top_avail;
+    T.depth = H.depth;
+    return PT_OK;
+}
+
+// The sweep tree of N leaf boxes in device memory, built (pt_sweep_build.hip) and re-laid (pt_scene_prep.hip) there, into T.
+// built(): called between the two (stage timing).  false: the builder handed the input back (depth guard) or something
+// failed; T.nodes is released and the host builder is next.
+template <class Built>
+bool internal_tree_device(const float* boxes_dev, int N, pt_scene::Tree& T, Built built) {
+    DevBuf<pt_bvh_node> fpool_dev;
+    DevBuf<int32_t> fiop_dev;
+    int32_t fdepth = 0;
+    double dev_ms = 0;
+    const size_t pool_nodes = 2 * (size_t)N - 1;
+    const bool ok = !fpool_dev.ensure(pool_nodes) && !fiop_dev.ensure(pool_nodes) && !T.nodes.ensure((size_t)N - 1) &&
+                    boxes_finite_device(boxes_dev, (size_t)N * 6) &&
+                    pts::sweep_build_on_device(boxes_dev, N, fpool_dev.p, &fdepth, &dev_ms) == PT_OK;
+    built();
+    ptp::RelayResult r1;
+    if (ok && ptp::relay_tree_device(fpool_dev.p, (int)pool_nodes, 0, N, true, T.nodes.p, fiop_dev.p, nullptr, kBlock, kTopNodes,
+                                     kMaxLdsBudget, &r1) == PT_OK && r1.nested) {
+        T.have_oct = false; T.num_nodes = N - 1; T.root_ref = 0; T.stack_cap = r1.stack_need + 1; T.top_avail = r1.top_avail; T.depth = r1.depth;
+        return true;
+    }
+    (void)hipGetLastError();
+    T.nodes.release();
+    return false;
+}
+
+// The same tree by the host builder (pt_tree_sweep.h), in internal form.  built(): called once the builder has run.
+template <class Built>
+bool internal_tree_host(const std::vector<float>& leaf_boxes, int N, TreeHost& fast, Built built) {
+    for (size_t k = 0; k < leaf_boxes.size(); k++)
+        if (!std::isfinite(leaf_boxes[k])) return false;
+    std::vector<pt_bvh_node> fnodes;
+    int32_t froot = 0, fdepth = 0;
+    bool ok = true;
+    try {
+        pts::build_sweep_tree(leaf_boxes.data(), N, fnodes, &froot, &fdepth);
+    } catch (const std::exception&) {        // out of host memory: the caller's tree serves alone
+        ok = false;
+    }
+    built();
+    bool fnested = true;
+    return ok && convert_tree(fnodes.data(), (int)fnodes.size(), froot, N, fast, nullptr, &fnested, true) == PT_OK && fnested;
+}
+
+// Inner visits of the probe rays (pt_kernels.h: probe_kernel) through the trees d0 and d1 point at, into v[0] and v[1].
+int probe_trees(const SceneDev& d0, const SceneDev& d1, unsigned long long v[2]) {
+    DevBuf<unsigned long long> visits;
+    int rc;
+    if ((rc = visits.ensure(2))) return rc;
+    HIP_TRY(hipMemset(visits.p, 0, 2 * sizeof(unsigned long long)));
+    const uint32_t lds = (uint32_t)(kBlock / 64) * (uint32_t)std::max(d0.stack_cap, d1.stack_cap) * 64u * 4u;
+    hipLaunchKernelGGL(probe_kernel, dim3(kProbeRays / kBlock, 2), dim3(kBlock), lds, nullptr, d0, d1, visits.p);
+    HIP_TRY(hipGetLastError());
+    v[0] = v[1] = 0;
+    HIP_TRY(hipMemcpy(v, visits.p, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    return PT_OK;
+}
+int64_t probe_permille(const unsigned long long v[2]) { return v[0] ? (int64_t)((1000ull * v[1] + v[0] / 2) / v[0]) : 1000; }
+bool probe_wins(const unsigned long long v[2]) { return v[1] * 100ull < v[0] * 90ull; }   // at least 10 % fewer boxes
+
+// The leaf sweep's groups of equal leaf boxes (pt_leaf_sweep.h) and its tables (pt_sweep_layout.h) from an internal tree as the
+// host built it; prims: the N <= kSweepMaxPrims records on the host.  groups = 0: none; sweep.count stays 0 where a launch
+// would not admit them.
+int make_sweep_tables(const TreeHost& fast, const DPrim* prims, int N, SweepTable& sweep, int& sweep_groups, DevBuf<unsigned char>& sweep_tab) {
+    sweep = SweepTable{};
+    sweep_groups = 0;
+    SweepGroup groups[kSweepMaxPrims];
+    const int n = build_sweep_groups(fast.nodes.data(), (int)fast.nodes.size(), N, kLdsNodeStride, groups);
+    if (n > 0) {
+        sweep_groups = n;
+        std::vector<unsigned char> tab(n <= kSweepMaxBoxes ? sweep_layout_bytes((uint32_t)n, (uint32_t)N) : 0);
+        if (n <= kSweepMaxBoxes && build_sweep_layout(groups, n, fast.nodes.data(), (int)fast.nodes.size(), kLdsNodeStride, prims, N, tab.data())) {
+            int rc;
+            if ((rc = sweep_tab.ensure(tab.size()))) return rc;
+            HIP_TRY(hipMemcpy(sweep_tab.p, tab.data(), tab.size(), hipMemcpyHostToDevice));
+            sweep.count = (uint32_t)n;
+            std::copy(groups, groups + n, sweep.g);
+        }
+    }
+    return PT_OK;
+}
+
 int validate_and_build(const pt_scene_desc* d, pt_scene* S) {
     if (!d) return fail(PT_ERR_INVALID_ARG, "null scene description");
     if (d->num_shapes <= 0 || !d->shapes) return fail(PT_ERR_BAD_SCENE, "scene has no shapes");
@@ -656,42 +786,18 @@ int validate_and_build(const pt_scene_desc* d, pt_scene* S) {
         S->create_us[2] = us_since(t_stage); t_stage = clk::now();
         if (r0.nested) {
             // (why a tree of the library's own may stand in for a nested caller's tree: see the host path below)
-            DevBuf<pt_bvh_node> fpool_dev;
-            DevBuf<int32_t> fiop_dev;
-            int32_t fdepth = 0;
-            double dev_ms = 0;
-            bool ok = !fpool_dev.ensure((size_t)d->num_nodes) && !fiop_dev.ensure((size_t)d->num_nodes) && !S->tree[1].nodes.ensure((size_t)N - 1) &&
-                      boxes_finite_device(boxes_dev.p, (size_t)N * 6) &&
-                      pts::sweep_build_on_device(boxes_dev.p, N, fpool_dev.p, &fdepth, &dev_ms) == PT_OK;
-            S->create_us[3] = us_since(t_stage); t_stage = clk::now();
-            ptp::RelayResult r1;
-            if (ok && ptp::relay_tree_device(fpool_dev.p, d->num_nodes, 0, N, true, S->tree[1].nodes.p, fiop_dev.p, nullptr, kBlock, kTopNodes,
-                                             kMaxLdsBudget, &r1) == PT_OK && r1.nested) {
-                pt_scene::Tree& T1 = S->tree[1];
-                T1.have_oct = false; T1.num_nodes = N - 1; T1.root_ref = 0; T1.stack_cap = r1.stack_need + 1; T1.top_avail = r1.top_avail; T1.depth = r1.depth;
+            if (internal_tree_device(boxes_dev.p, N, S->tree[1], [&] { S->create_us[3] = us_since(t_stage); t_stage = clk::now(); })) {
                 have_fast = true;
                 S->sweep_on_device = 1;
             } else {
-                (void)hipGetLastError();
-                S->tree[1].nodes.release();
-                {
-                    // the device builder handed the input back (depth guard) or failed: the host builder, from the leaf boxes
-                    std::vector<float> leaf_boxes((size_t)N * 6);
-                    std::vector<pt_bvh_node> fnodes;
-                    int32_t froot = 0, hdepth = 0;
-                    bool built = hipMemcpy(leaf_boxes.data(), boxes_dev.p, leaf_boxes.size() * sizeof(float), hipMemcpyDeviceToHost) == hipSuccess;
-                    for (size_t k = 0; k < leaf_boxes.size() && built; k++) built = std::isfinite(leaf_boxes[k]);
-                    if (built) {
-                        try {
-                            pts::build_sweep_tree(leaf_boxes.data(), N, fnodes, &froot, &hdepth);
-                        } catch (const std::exception&) {
-                            built = false;
-                        }
-                    }
-                    bool fnested = true;
-                    have_fast = built && convert_tree(fnodes.data(), (int)fnodes.size(), froot, N, fast, nullptr, &fnested, true) == PT_OK && fnested;
-                }
+                // the device builder handed the input back (depth guard) or failed: the host builder, from the leaf boxes
+                std::vector<float> leaf_boxes((size_t)N * 6);
+                have_fast = hipMemcpy(leaf_boxes.data(), boxes_dev.p, leaf_boxes.size() * sizeof(float), hipMemcpyDeviceToHost) == hipSuccess &&
+                            internal_tree_host(leaf_boxes, N, fast, [] {});
             }
+            if (!have_fast) S->no_fast_why = "the internal tree could not be built";
+        } else {
+            S->no_fast_why = "the caller's boxes do not nest";
         }
     } else {
         std::vector<float> leaf_boxes((size_t)N * 6);
@@ -708,21 +814,10 @@ int validate_and_build(const pt_scene_desc* d, pt_scene* S) {
             // leaf boxes tests the same leaves, and only the ORDER of the tests (ties on t, scene.h:270) still depends on the tree.
             // The tree: all cuts along x, y and z at every node (pt_tree_sweep.h), as deep as it likes — traversed left child
             // first, its stack need is its Strahler number, not its depth (convert_tree).
-            bool finite = true;
-            for (size_t k = 0; k < leaf_boxes.size() && finite; k++) finite = std::isfinite(leaf_boxes[k]);
-            if (finite) {
-                std::vector<pt_bvh_node> fnodes;
-                int32_t froot = 0, fdepth = 0;
-                bool built = true;
-                try {
-                    pts::build_sweep_tree(leaf_boxes.data(), N, fnodes, &froot, &fdepth);
-                } catch (const std::exception&) {        // out of host memory: the caller's tree serves alone
-                    built = false;
-                }
-                S->create_us[3] = us_since(t_stage); t_stage = clk::now();
-                bool fnested = true;
-                have_fast = built && convert_tree(fnodes.data(), (int)fnodes.size(), froot, N, fast, nullptr, &fnested, true) == PT_OK && fnested;
-            }
+            have_fast = internal_tree_host(leaf_boxes, N, fast, [&] { S->create_us[3] = us_since(t_stage); t_stage = clk::now(); });
+            if (!have_fast) S->no_fast_why = "the internal tree could not be built";
+        } else {
+            S->no_fast_why = N < kMinInternalTree ? "fewer than 16 shapes" : "the caller's boxes do not nest";
         }
     }
     S->create_us[4] = us_since(t_stage); t_stage = clk::now();
@@ -733,38 +828,8 @@ int validate_and_build(const pt_scene_desc* d, pt_scene* S) {
     std::vector<DLight> dlights;
     int rc;
     if ((rc = pack_shading(d, N, mats, emis, dlights))) return rc;
-    auto upload_tree = [&](int t, const TreeHost& H) -> int {
-        const std::vector<DNode>& nodes = H.nodes;
-        pt_scene::Tree& T = S->tree[t];
-        // 8 ray-octant copies of the node table for LDS-resident scenes: octant bit k set <=> 1/d[k] < 0, in which case
-        // Hit() swaps the two slab distances of axis k (bbox.cuh:40-55); here the two planes are swapped instead.
-        T.have_oct = false;
-        if (nodes.size() * 8 * sizeof(DNode) <= kOctNodeLimit) {
-            std::vector<DNode> nodes_oct(nodes.size() * 8);
-            for (int o = 0; o < 8; o++)
-                for (size_t k = 0; k < nodes.size(); k++) {
-                    DNode n = nodes[k];
-                    for (int ax = 0; ax < 3; ax++)
-                        if (o & (1 << ax)) { std::swap(n.lmin[ax], n.lmax[ax]); std::swap(n.rmin[ax], n.rmax[ax]); }
-                    nodes_oct[(size_t)o * nodes.size() + k] = n;
-                }
-            int r;
-            if ((r = T.nodes_oct.ensure(nodes_oct.size()))) return r;
-            HIP_TRY(hipMemcpy(T.nodes_oct.p, nodes_oct.data(), nodes_oct.size() * sizeof(DNode), hipMemcpyHostToDevice));
-            T.have_oct = true;
-        }
-        int r;
-        if ((r = T.nodes.ensure(nodes.size()))) return r;
-        HIP_TRY(hipMemcpy(T.nodes.p, nodes.data(), nodes.size() * sizeof(DNode), hipMemcpyHostToDevice));
-        T.num_nodes = (int32_t)nodes.size();
-        T.root_ref = H.root_ref;
-        T.stack_cap = H.stack_need + 1;                         // + the kDone sentinel at the bottom
-        T.top_avail = H.top_avail;
-        T.depth = H.depth;
-        return PT_OK;
-    };
     for (int t = 0; t < 2; t++)
-        if (hosts[t] && (rc = upload_tree(t, *hosts[t]))) return rc;
+        if (hosts[t] && (rc = upload_tree(S->tree[t], *hosts[t]))) return rc;
     S->have_fast = have_fast;
     if (!on_device && ((rc = S->prims.ensure(prims.size())) || (rc = S->normals.ensure(normals.size())))) return rc;
     if ((rc = S->materials.ensure(mats.size()))) return rc;
@@ -792,23 +857,16 @@ int validate_and_build(const pt_scene_desc* d, pt_scene* S) {
     // directions, which is where and how the segments after the first bounce start — through both trees, inner visits counted.
     S->fast_cost_permille = 0;
     if (have_fast) {
-        DevBuf<unsigned long long> visits;
-        if ((rc = visits.ensure(2))) return rc;
-        HIP_TRY(hipMemset(visits.p, 0, 2 * sizeof(unsigned long long)));
-        {
-            select_tree(S, 0);
-            const SceneDev d0 = S->dev;
-            select_tree(S, 1);
-            const SceneDev d1 = S->dev;
-            const uint32_t lds = (uint32_t)(kBlock / 64) * (uint32_t)std::max(d0.stack_cap, d1.stack_cap) * 64u * 4u;
-            hipLaunchKernelGGL(probe_kernel, dim3(kProbeRays / kBlock, 2), dim3(kBlock), lds, nullptr, d0, d1, visits.p);
-            HIP_TRY(hipGetLastError());
-        }
+        select_tree(S, 0);
+        const SceneDev d0 = S->dev;
+        select_tree(S, 1);
+        const SceneDev d1 = S->dev;
         unsigned long long v[2] = {0, 0};
-        HIP_TRY(hipMemcpy(v, visits.p, sizeof(v), hipMemcpyDeviceToHost));
-        S->fast_cost_permille = v[0] ? (int64_t)((1000ull * v[1] + v[0] / 2) / v[0]) : 1000;
-        if (!(v[1] * 100ull < v[0] * 90ull)) {              // not at least 10 % fewer boxes: the sweep tree is not worth having
+        if ((rc = probe_trees(d0, d1, v))) return rc;
+        S->fast_cost_permille = probe_permille(v);
+        if (!probe_wins(v)) {                               // not at least 10 % fewer boxes: the sweep tree is not worth having
             S->have_fast = false;
+            S->no_fast_why = "the sweep tree lost the probe on an LDS-resident scene";
             S->tree[1].nodes.release();
             S->tree[1].nodes_oct.release();
             S->tree[1].have_oct = false;
@@ -821,7 +879,7 @@ int validate_and_build(const pt_scene_desc* d, pt_scene* S) {
                 TreeHost own;
                 bool own_nested = true;
                 if (convert_tree(d->nodes, d->num_nodes, d->root, N, own, nullptr, &own_nested, true) == PT_OK && own_nested) {
-                    if ((rc = upload_tree(1, own))) return rc;
+                    if ((rc = upload_tree(S->tree[1], own))) return rc;
                     S->have_fast = true;
                     S->fast_is_callers_topology = true;
                 }
@@ -838,6 +896,7 @@ int validate_and_build(const pt_scene_desc* d, pt_scene* S) {
             // no room for the tables (num_shapes x depth words): the scene simply keeps to the caller's tree
             (void)hipGetLastError();
             S->have_fast = false;
+            S->no_fast_why = "there was no room for the tie tables";
             S->fast_is_callers_topology = false;
             S->ref_path.release(); S->ref_anc.release();
             S->tree[1].nodes.release(); S->tree[1].nodes_oct.release(); S->tree[1].have_oct = false;
@@ -882,20 +941,9 @@ int validate_and_build(const pt_scene_desc* d, pt_scene* S) {
     // the leaf sweep's groups of equal leaf boxes (pt_leaf_sweep.h), from the internal tree as the host built it
     S->sweep = SweepTable{};
     S->sweep_groups = 0;
-    if (S->have_fast && hosts[1] && !S->fast_is_callers_topology && N <= kSweepMaxPrims) {
-        SweepGroup groups[kSweepMaxPrims];
-        const int n = build_sweep_groups(fast.nodes.data(), (int)fast.nodes.size(), N, kLdsNodeStride, groups);
-        if (n > 0) {
-            S->sweep_groups = n;
-            std::vector<unsigned char> tab(n <= kSweepMaxBoxes ? sweep_layout_bytes((uint32_t)n, (uint32_t)N) : 0);
-            if (n <= kSweepMaxBoxes && build_sweep_layout(groups, n, fast.nodes.data(), (int)fast.nodes.size(), kLdsNodeStride, prims.data(), N, tab.data())) {
-                if ((rc = S->sweep_tab.ensure(tab.size()))) return rc;
-                HIP_TRY(hipMemcpy(S->sweep_tab.p, tab.data(), tab.size(), hipMemcpyHostToDevice));
-                S->sweep.count = (uint32_t)n;
-                std::copy(groups, groups + n, S->sweep.g);
-            }
-        }
-    }
+    if (S->have_fast && hosts[1] && !S->fast_is_callers_topology && N <= kSweepMaxPrims &&
+        (rc = make_sweep_tables(fast, prims.data(), N, S->sweep, S->sweep_groups, S->sweep_tab)))
+        return rc;
     // everything the scene holds is complete from here on: trace kernels run on streams of the handle's own (FrameSlot) that do
     // not synchronise with the stream the preparation kernels ran on
     HIP_TRY(hipDeviceSynchronize());
@@ -1649,6 +1697,34 @@ int ensure_staging(pt_scene* S) {
     return PT_OK;
 }
 
+// ---- tree-cost telemetry (pt_tree_cost.hip) ---------------------------------------------------------------------------------
+int ensure_cost(pt_scene* S) {
+    int rc;
+    const size_t need = std::max(ptc::partials_needed(S->tree[0].num_nodes), ptc::partials_needed(S->tree[1].num_nodes));
+    if ((rc = S->cost_partials.ensure(need)) || (rc = S->cost_dev.ensure(4))) return rc;
+    if (!S->cost_host) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&S->cost_host), 4 * sizeof(double), hipHostMallocDefault));
+    return PT_OK;
+}
+// T's cost into cost_dev[slot] and from there to cost_host[slot], all on the default stream; read once that has synchronised
+int enqueue_cost(pt_scene* S, const pt_scene::Tree& T, int slot) {
+    int rc;
+    if ((rc = ptc::tree_cost(T.nodes.p, T.num_nodes, S->cost_partials.p, S->cost_dev.p + slot))) return rc;
+    HIP_TRY(hipMemcpyAsync(S->cost_host + slot, S->cost_dev.p + slot, sizeof(double), hipMemcpyDeviceToHost, nullptr));
+    return PT_OK;
+}
+// after the synchronise that closes the call: what adopt_staged enqueued
+void collect_costs(pt_scene* S) {
+    for (int t = 0; t < 2; t++) {
+        if (S->cost_pending_ref[t]) { S->cost_ref[t] = S->cost_host[t]; S->cost_have_ref[t] = true; }
+        if (S->cost_pending_now[t]) S->cost_now[t] = S->cost_host[2 + t];
+        S->cost_pending_ref[t] = S->cost_pending_now[t] = false;
+    }
+}
+int64_t cost_permille(const pt_scene* S, int t) {
+    if (!S->cost_have_ref[t] || !(S->cost_ref[t] > 0.0) || !(S->cost_now[t] > 0.0)) return 1000;
+    return (int64_t)(1000.0 * S->cost_now[t] / S->cost_ref[t] + 0.5);
+}
+
 // What pt_scene_update and pt_scene_transform do once new records stand in st_prims / st_normals: the refit plans where none
 // exist yet, leaf boxes and the status read-back, both trees refitted, and only then the handle changes — the three record
 // buffers rotate (staging -> current -> previous) and the box sweep is dropped.  `who` heads the messages.  *us_plan: wall
@@ -1672,6 +1748,17 @@ int adopt_staged(pt_scene* S, const char* who, bool tri_only, int64_t* us_plan, 
         if (S->tree[t].have_oct && !pl.whole_tree) return fail(PT_ERR_UNSUPPORTED, std::string(who) + ": octant tables on a tree of wide levels");
     }
     if (planned) { *us_plan = std::max<int64_t>(us_since(t_stage), 1); t_stage = clk::now(); }
+    const bool costs = S->cost_on() && n_trees > 0;
+    for (int t = 0; t < 2; t++) S->cost_pending_ref[t] = S->cost_pending_now[t] = false;
+    if (costs) {
+        // the reference cost of a tree that has none yet: from the boxes as they stand, before this refit writes them
+        if ((rc = ensure_cost(S))) return rc;
+        for (int t = 0; t < n_trees; t++)
+            if (!S->cost_have_ref[t]) {
+                if ((rc = enqueue_cost(S, S->tree[t], t))) return rc;
+                S->cost_pending_ref[t] = true;
+            }
+    }
     HIP_TRY(hipMemsetAsync(S->st_status.p, 0, sizeof(unsigned int), nullptr));
     unsigned int bad = 0;
     if (!whole || n_trees == 0) {
@@ -1687,6 +1774,9 @@ int adopt_staged(pt_scene* S, const char* who, bool tri_only, int64_t* us_plan, 
     }
     if (whole && n_trees) HIP_TRY(hipMemcpy(&bad, S->st_status.p, sizeof bad, hipMemcpyDeviceToHost));
     if (bad) return fail(PT_ERR_UNSUPPORTED, std::string(who) + ": a new coordinate, radius or leaf box is not finite");
+    // behind the refit on its stream; the caller reads it after the synchronise that closes the call (collect_costs).  The
+    // trees are written: a launch that fails here costs the measurement, not the update.
+    for (int t = 0; costs && t < n_trees; t++) S->cost_pending_now[t] = enqueue_cost(S, S->tree[t], 2 + t) == PT_OK;
     std::swap(S->prev_prims.p, S->st_prims.p); std::swap(S->prev_prims.n, S->st_prims.n);   // the new records, for a moment
     std::swap(S->prims.p, S->prev_prims.p); std::swap(S->prims.n, S->prev_prims.n);         // current -> previous, new -> current
     S->have_prev = true;
@@ -1697,6 +1787,111 @@ int adopt_staged(pt_scene* S, const char* who, bool tri_only, int64_t* us_plan, 
     S->sweep_tab.release();                      // (no frame is in flight: the update synchronised before it wrote)
     *us_refit = us_since(t_stage);
     return PT_OK;
+}
+
+// pt_scene_rebuild (include/pt_api.h) between the two synchronises: the caller has made the device current and quiet, and
+// synchronises again before a frame may start.  Everything is made in buffers of its own — leaf boxes out of tree[0], the
+// candidate by pt_scene_create's internal-tree stage, its refit plan, its sweep tables — and only then does the handle change,
+// by steps that cannot fail.  tree[0], the tie tables and every record set are read, never written.
+int rebuild_scene(pt_scene* S) {
+    using clk = std::chrono::steady_clock;
+    auto us_since = [](clk::time_point t0) { return (int64_t)std::chrono::duration_cast<std::chrono::microseconds>(clk::now() - t0).count(); };
+    if (!S->have_fast)
+        return fail(PT_ERR_UNSUPPORTED, std::string("pt_scene_rebuild: the handle holds no tie tables, pt_scene_create kept no internal tree: ") +
+                                            (S->no_fast_why[0] ? S->no_fast_why : "none was built"));
+    const int N = S->dev.num_prims;
+    const pt_scene::Tree& T0 = S->tree[0];
+    const clk::time_point t_all = clk::now();
+    clk::time_point t_stage = t_all;
+    int64_t us[4] = {0, 0, 0, 0};
+    int rc;
+    // ---- leaf boxes: what the caller's tree holds (the caller's own before a geometry update, the exact ones after)
+    DevBuf<float> boxes_dev;
+    if ((rc = boxes_dev.ensure((size_t)N * 6)) || (rc = ptf::tree_leaf_boxes(T0.nodes.p, T0.num_nodes, N, boxes_dev.p))) return rc;
+    // ---- build: create's branches
+    pt_scene::Tree cand;
+    TreeHost fast;
+    auto built = [&] { us[1] = us_since(t_stage); t_stage = clk::now(); };
+    bool on_device = N >= kDeviceSweepMin && !host_sweep_forced() && internal_tree_device(boxes_dev.p, N, cand, built);
+    if (!on_device) {
+        std::vector<float> leaf_boxes((size_t)N * 6);
+        HIP_TRY(hipMemcpy(leaf_boxes.data(), boxes_dev.p, leaf_boxes.size() * sizeof(float), hipMemcpyDeviceToHost));
+        t_stage = t_all;                              // stage 1 runs from the start of the call, whichever builder ends it
+        if (!internal_tree_host(leaf_boxes, N, fast, built))
+            return fail(PT_ERR_UNSUPPORTED, "pt_scene_rebuild: no internal tree could be built of the leaf boxes (not finite, or they no longer nest)");
+        if ((rc = upload_tree(cand, fast))) return rc;
+    }
+    boxes_dev.release();
+    // ---- probe: create's rays and create's rule, the caller's tree as it stands against the candidate.  (As at create: no tie
+    // tables in view, the probe counts box tests.)
+    SceneDev d0 = S->dev, d1 = S->dev;
+    tree_view(S, d0, 0, false);
+    tree_view(S, d1, cand, 1, false);
+    for (SceneDev* dv : {&d0, &d1}) { dv->ref_path = nullptr; dv->ref_anc = nullptr; dv->ref_levels = 0; dv->redo_stack = nullptr; }
+    unsigned long long v[2] = {0, 0};
+    if ((rc = probe_trees(d0, d1, v))) return rc;
+    const bool adopt = probe_wins(v);
+    us[2] = us_since(t_stage); t_stage = clk::now();
+    // ---- what goes with an adopted tree: its refit plan where the handle has refitted before (the next update does not pay for
+    // it), the box sweep of a small scene under create's admission rules, its cost where telemetry is on
+    ptf::Plan plan;
+    SweepTable sweep{};
+    int sweep_groups = 0;
+    DevBuf<unsigned char> sweep_tab;
+    double cost = 0.0;
+    if (adopt) {
+        if (S->refit_plan[1].built && (rc = ptf::plan_build(cand.nodes.p, cand.num_nodes, N, &plan))) return rc;
+        struct PlanGuard { ptf::Plan* p; ~PlanGuard() { if (p) ptf::plan_release(p); } } plan_guard{&plan};
+        if (!on_device && N <= kSweepMaxPrims) {
+            std::vector<DPrim> prims((size_t)N);
+            HIP_TRY(hipMemcpy(prims.data(), S->prims.p, prims.size() * sizeof(DPrim), hipMemcpyDeviceToHost));
+            if ((rc = make_sweep_tables(fast, prims.data(), N, sweep, sweep_groups, sweep_tab))) return rc;
+        }
+        if (S->cost_on()) {
+            if ((rc = ensure_cost(S)) || (rc = enqueue_cost(S, cand, 3))) return rc;
+            HIP_TRY(hipStreamSynchronize(nullptr));
+            cost = S->cost_host[3];
+        }
+        // ---- adoption
+        pt_scene::Tree& T1 = S->tree[1];
+        std::swap(T1.nodes.p, cand.nodes.p); std::swap(T1.nodes.n, cand.nodes.n);
+        std::swap(T1.nodes_oct.p, cand.nodes_oct.p); std::swap(T1.nodes_oct.n, cand.nodes_oct.n);
+        T1.have_oct = cand.have_oct; T1.num_nodes = cand.num_nodes; T1.root_ref = cand.root_ref; T1.stack_cap = cand.stack_cap;
+        T1.top_avail = cand.top_avail; T1.depth = cand.depth;
+        S->have_fast = true;
+        S->fast_is_callers_topology = false;
+        S->fast_cost_permille = probe_permille(v);
+        S->sweep_on_device = on_device ? 1 : 0;
+        std::swap(S->refit_plan[1], plan);            // the old plan goes with the old tree, once the call is timed
+        plan_guard.p = &plan;
+        S->sweep = sweep;
+        S->sweep_groups = sweep_groups;
+        std::swap(S->sweep_tab.p, sweep_tab.p); std::swap(S->sweep_tab.n, sweep_tab.n);
+        S->cfg_fn = nullptr;                          // stack and LDS needs follow the tree: the next launch asks again
+        S->q_cfg_fn = nullptr;
+        if (S->cost_on()) { S->cost_ref[1] = S->cost_now[1] = cost; S->cost_have_ref[1] = true; }
+    } else if (S->cost_have_ref[1] && S->cost_now[1] > 0.0) {
+        S->cost_ref[1] = S->cost_now[1];              // no better tree to be had of these boxes: a policy waits for the next drift
+    }
+    us[3] = us_since(t_stage);
+    us[0] = us_since(t_all);
+    select_tree(S, 0);
+    S->rebuilds++;
+    S->rebuild_adopted = adopt ? 1 : 0;
+    S->rebuild_cost_permille = probe_permille(v);
+    std::copy(us, us + 4, S->rebuild_us);
+    return PT_OK;
+}
+
+// The policy of option rebuild_at_permille, inside a geometry update or transform that has refitted: the internal tree's cost
+// is awaited and compared, and the rebuild runs before the call's closing synchronise.  A rebuild that fails leaves the refitted
+// tree in place and does not fail the call.
+void rebuild_by_policy(pt_scene* S) {
+    if (S->opt_rebuild_at <= 0 || !S->have_fast || !S->cost_pending_now[1]) return;
+    if (hipStreamSynchronize(nullptr) != hipSuccess) return;
+    collect_costs(S);
+    if (cost_permille(S, 1) < S->opt_rebuild_at) return;
+    if (rebuild_scene(S) == PT_OK) S->rebuilds_auto++;
 }
 
 // pt_scene_update (include/pt_api.h).  Order of events: everything that can be refused is made and checked first — argument
@@ -1740,6 +1935,7 @@ int update_scene(pt_scene* S, const pt_scene_desc* d, int flags) {
         us_records = us_since(t_stage);
         if ((rc = adopt_staged(S, "pt_scene_update", !has_sphere, &us_plan, &us_refit))) return rc;
         S->have_rest = false;                        // the next pt_scene_transform starts from these records
+        rebuild_by_policy(S);
     }
     if (shading) {
         const clk::time_point t_stage = clk::now();
@@ -1752,6 +1948,7 @@ int update_scene(pt_scene* S, const pt_scene_desc* d, int flags) {
     }
     // the handle's own streams do not synchronise with the default stream the kernels above ran on
     HIP_TRY(hipDeviceSynchronize());
+    collect_costs(S);
     select_tree(S, 0);
     S->updates++;
     S->update_us[0] = us_since(t_all); S->update_us[1] = us_records; S->update_us[2] = us_refit; S->update_us[3] = us_plan;
@@ -1796,9 +1993,11 @@ int transform_scene(pt_scene* S, const pt_transform* transforms, int32_t num_gro
     us_records = us_since(t_stage);
     int64_t us_plan = 0;
     if ((rc = adopt_staged(S, "pt_scene_transform", S->tri_only, &us_plan, &us_refit))) return rc;
+    rebuild_by_policy(S);
     // the handle's own streams do not synchronise with the default stream the kernels above ran on
     HIP_TRY(hipDeviceSynchronize());
-    S->have_rest = true;                                 // (a refused call leaves the flag as it was: the next one copies again)
+    collect_costs(S);
+    S->have_rest = true;                                // (a refused call leaves the flag as it was: the next one copies again)
     select_tree(S, 0);
     S->transforms++;
     S->transform_us[0] = us_since(t_all); S->transform_us[1] = us_records; S->transform_us[2] = us_refit; S->transform_us[3] = us_once + us_plan;
@@ -2349,6 +2548,9 @@ int pt_scene_destroy(pt_scene* S) {
     S->st_prims.release(); S->prev_prims.release(); S->st_normals.release(); S->st_boxes.release(); S->st_status.release();
     S->group_of.release(); S->group_tab.release(); S->rest_prims.release(); S->rest_normals.release();
     for (auto& pl : S->refit_plan) ptf::plan_release(&pl);
+    S->cost_partials.release(); S->cost_dev.release();
+    if (S->cost_host) (void)hipHostFree(S->cost_host);
+    S->cost_host = nullptr;
     S->drop_events();
     delete S;
     return PT_OK;
@@ -2360,6 +2562,21 @@ int pt_scene_update(pt_scene* S, const pt_scene_desc* desc, int flags) {
     if (flags == 0 || (flags & ~(PT_UPDATE_GEOMETRY | PT_UPDATE_SHADING)))
         return fail(PT_ERR_INVALID_ARG, "pt_scene_update: flags must be PT_UPDATE_GEOMETRY, PT_UPDATE_SHADING or both");
     return update_scene(S, desc, flags);
+}
+
+int pt_scene_rebuild(pt_scene* S, int flags) {
+    if (!S) return fail(PT_ERR_INVALID_ARG, "pt_scene_rebuild: null scene");
+    if (flags != 0) return fail(PT_ERR_INVALID_ARG, "pt_scene_rebuild: flags must be 0 (reserved)");
+    DeviceGuard guard;
+    { int grc = guard.enter(S->device); if (grc) return grc; }
+    // frames of this handle that are still in flight, on the caller's streams and on the slots' own, read the scene
+    HIP_TRY(hipDeviceSynchronize());
+    const int rc = rebuild_scene(S);
+    // the handle's own streams do not synchronise with the default stream the kernels above ran on
+    const hipError_t e = hipDeviceSynchronize();
+    if (rc) return rc;
+    HIP_TRY(e);
+    return PT_OK;
 }
 
 int pt_scene_set_groups(pt_scene* S, const int32_t* group_of_shape, int32_t num_groups) {
@@ -2822,6 +3039,11 @@ int pt_scene_set_option(pt_scene* S, const char* key, int64_t value) {
     else if (k == "query_refill") { if (value < 0 || value > 64) return fail(PT_ERR_INVALID_ARG, "query_refill must be 0 (automatic) .. 64"); S->opt_query_refill = value; }
     else if (k == "query_guides") { if (value < 0 || value > 2) return fail(PT_ERR_INVALID_ARG, "query_guides must be 0 (automatic), 1 or 2"); S->opt_query_guides = value; }
     else if (k == "query_blocks") { if (value < 0 || value > 4096) return fail(PT_ERR_INVALID_ARG, "query_blocks must be 0 (automatic) .. 4096"); S->opt_query_blocks = value; }
+    else if (k == "tree_cost") { if (value != 0 && value != 1) return fail(PT_ERR_INVALID_ARG, "tree_cost must be 0 or 1"); S->opt_tree_cost = value; }
+    else if (k == "rebuild_at_permille") {
+        if (value != 0 && value < 1001) return fail(PT_ERR_INVALID_ARG, "rebuild_at_permille must be 0 (never) or at least 1001");
+        S->opt_rebuild_at = value;
+    }
     else return fail(PT_ERR_INVALID_ARG, "unknown option " + k);
     return PT_OK;
 }
@@ -2869,6 +3091,22 @@ int pt_scene_get_info(pt_scene* S, const char* key, int64_t* value) {
     else if (k == "rest_geometry") *value = S->have_rest ? 1 : 0;         // a snapshot of the rest records is held (pt_scene_transform)
     else if (k == "transforms") *value = S->transforms;                   // successful pt_scene_transform calls so far
     else if (k.rfind("transform_us", 0) == 0 && k.size() == 13 && k[12] >= '0' && k[12] <= '3') *value = S->transform_us[k[12] - '0'];
+    else if (k == "rebuilds") *value = S->rebuilds;                       // successful pt_scene_rebuild calls so far, a policy's included
+    else if (k == "rebuilds_auto") *value = S->rebuilds_auto;             // ... those that option rebuild_at_permille made
+    else if (k == "rebuild_adopted") *value = S->rebuild_adopted;         // the last one adopted its tree (1) or kept the one it had (0)
+    else if (k == "rebuild_cost_permille") *value = S->rebuild_cost_permille;   // the last candidate's probe ratio (as fast_tree_cost_permille)
+    else if (k.rfind("rebuild_us", 0) == 0 && k.size() == 11 && k[10] >= '0' && k[10] <= '3') *value = S->rebuild_us[k[10] - '0'];
+    else if (k == "tree_cost0_bits" || k == "tree_cost1_bits") {
+        // option tree_cost: the fp64 bit pattern of tree 0's / 1's cost after the last refit (0: no such tree, nothing measured)
+        const int t = k[9] - '0';
+        const double c = (S->cost_on() && (t == 0 || S->have_fast)) ? S->cost_now[t] : 0.0;
+        *value = c > 0.0 ? __builtin_bit_cast(int64_t, c) : 0;
+    }
+    else if (k == "tree_cost0_permille" || k == "tree_cost1_permille") {
+        // ... and that cost over the cost of the boxes as built (or as last rebuilt), x 1000; 1000 before any refit
+        const int t = k[9] - '0';
+        *value = (S->cost_on() && (t == 0 || S->have_fast)) ? cost_permille(S, t) : 1000;
+    }
     else if (k == "refit_shape0" || k == "refit_shape1") {
         // how a geometry update refits tree 0 (the caller's) / 1 (the internal one): 0 no plan (no such tree, a one-shape scene, or
         // no geometry update yet), 1 one launch, 2 scatter + a launch per wide level + the narrow top, 3 scatter + the narrow top alone

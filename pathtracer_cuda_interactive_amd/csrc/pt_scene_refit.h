@@ -36,6 +36,11 @@ void plan_release(Plan* p);
 // host pipeline's `a < b ? a : b` form (csrc/host/scene_build.cpp, vecmath.h).
 int leaf_boxes(const void* prims_dev, int N, float* boxes_dev, unsigned int* status_dev);
 
+// The leaf boxes a DNode array holds, back into the builders' layout (pt_scene_rebuild): one thread per node copies the boxes
+// of its leaf children to boxes_dev [N][6].  num_nodes = N - 1 >= 1; a tree of that size over N primitives names each once
+// (pt_scene_create checked), so every row is written.  Default stream, nothing synchronised.
+int tree_leaf_boxes(const void* dnodes_dev, int num_nodes, int N, float* boxes_dev);
+
 // Writes exact new boxes into one tree: leaf boxes into their parents' child slots, then every inner node's box = the union of
 // its two child boxes into ITS parent's slot, levels deepest first; the 8 octant tables after that (dnodes_oct_dev, or null).
 //   plan.whole_tree: ONE single-workgroup launch that computes the leaf boxes from prims_dev itself, checks them (a

@@ -32,7 +32,8 @@ using ptl::DPrim;
 
 constexpr int kThreads = 256;
 constexpr int kMaxLevels = 256;       // caller's trees: <= 64 levels (scene.h:251); the library's own: <= 2 log2 n + 18
-constexpr int kNarrow = 1024;         // a level of at most this many nodes is "narrow": four nodes per thread of one workgroup
+static_assert(kThreads == kMaxLevels, "the plan kernels keep one LDS counter per level and thread");
+constexpr int kNarrow = 1024;        // a level of at most this many nodes is "narrow": four nodes per thread of one workgroup
 constexpr int kWholeTreeNodes = 4096; // trees up to this size whose levels are all narrow are refitted by one launch
 
 // ---- plan -------------------------------------------------------------------------------------------------------------------
@@ -62,23 +63,48 @@ __global__ void plan_links_kernel(const DNode* __restrict__ nodes, int num_nodes
 // depth of every node by a walk to the root (node 0), as relay_level_kernel does it for a node pool
 __global__ void plan_depth_kernel(int num_nodes, const int32_t* __restrict__ parent_slot, int32_t* __restrict__ depth,
                                   PlanCtl* __restrict__ ctl) {
+    // counted per workgroup in LDS first: a million device-scope atomics on a few dozen words took most of the plan build
+    __shared__ unsigned int hist[kMaxLevels];
+    hist[threadIdx.x] = 0;                                // kThreads == kMaxLevels
+    __syncthreads();
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= num_nodes) return;
-    int e = 0;
-    for (int v = k; v != 0; e++) {
-        const int32_t ps = parent_slot[v];
-        if (ps < 0 || e >= kMaxLevels - 1) { atomicOr(&ctl->err, 2u); depth[k] = -1; return; }
-        v = ps >> 1;
+    if (k < num_nodes) {
+        int e = 0;
+        bool ok = true;
+        for (int v = k; v != 0 && ok; e++) {
+            const int32_t ps = parent_slot[v];
+            if (ps < 0 || e >= kMaxLevels - 1) { ok = false; break; }
+            v = ps >> 1;
+        }
+        if (ok) {
+            depth[k] = e;
+            atomicAdd(&hist[e], 1u);
+        } else {
+            atomicOr(&ctl->err, 2u);
+            depth[k] = -1;
+        }
     }
-    depth[k] = e;
-    atomicAdd(&ctl->count[e], 1u);
+    __syncthreads();
+    if (hist[threadIdx.x]) atomicAdd(&ctl->count[threadIdx.x], hist[threadIdx.x]);
 }
 __global__ void plan_order_kernel(int num_nodes, const int32_t* __restrict__ depth, const int32_t* __restrict__ level_begin,
                                   int32_t* __restrict__ order, PlanCtl* __restrict__ ctl) {
+    // a workgroup reserves its nodes' places level by level: ranks inside the workgroup from LDS, one atomic per level it holds
+    __shared__ unsigned int hist[kMaxLevels];             // count of the level, then the workgroup's first place in it
+    hist[threadIdx.x] = 0;                                // kThreads == kMaxLevels
+    __syncthreads();
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= num_nodes) return;
-    const int32_t d = depth[k];
-    order[level_begin[d] + (int32_t)atomicAdd(&ctl->count[d], 1u)] = k;      // the order inside a level does not matter
+    const int32_t d = k < num_nodes ? depth[k] : -1;
+    const unsigned int rank = d >= 0 ? atomicAdd(&hist[d], 1u) : 0u;
+    __syncthreads();
+    if (hist[threadIdx.x]) hist[threadIdx.x] = atomicAdd(&ctl->count[threadIdx.x], hist[threadIdx.x]);
+    __syncthreads();
+    if (d >= 0) order[level_begin[d] + (int32_t)(hist[d] + rank)] = k;       // the order inside a level does not matter
+}
+
+__global__ void plan_leaves_kernel(const int32_t* __restrict__ leaf_slot, int N, int num_nodes, PlanCtl* __restrict__ ctl) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < N && (leaf_slot[i] < 0 || leaf_slot[i] >= 2 * num_nodes)) atomicOr(&ctl->err, 4u);
 }
 
 // ---- boxes ------------------------------------------------------------------------------------------------------------------
@@ -149,6 +175,22 @@ __global__ void scatter_leaves_kernel(const float* __restrict__ boxes, int N, co
     Box b;
     for (int c = 0; c < 3; c++) { b.lo[c] = s[c]; b.hi[c] = s[3 + c]; }
     store_slot(nodes, leaf_slot[i], b);
+}
+// the other way round (pt_scene_rebuild): every node hands the boxes of its leaf children to boxes[prim]
+__global__ void gather_leaves_kernel(const DNode* __restrict__ nodes, int num_nodes, int N, float* __restrict__ boxes) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= num_nodes) return;
+    const float4* rec = reinterpret_cast<const float4*>(nodes + k);
+    const float4 a = rec[0], b = rec[1], c = rec[2];      // lmin.xyz lmax.x | lmax.yz rmin.xy | rmin.z rmax.xyz
+    const int32_t left = nodes[k].left, right = nodes[k].right;
+    if (left < 0 && ~left < N) {
+        float* o = boxes + 6 * (size_t)~left;
+        o[0] = a.x; o[1] = a.y; o[2] = a.z; o[3] = a.w; o[4] = b.x; o[5] = b.y;
+    }
+    if (right < 0 && ~right < N) {
+        float* o = boxes + 6 * (size_t)~right;
+        o[0] = b.z; o[1] = b.w; o[2] = c.x; o[3] = c.y; o[4] = c.z; o[5] = c.w;
+    }
 }
 // one wide level: order[begin .. begin + count)
 __global__ void lift_level_kernel(DNode* __restrict__ nodes, const int32_t* __restrict__ order, int begin, int count,
@@ -258,19 +300,15 @@ int ptf::plan_build(const void* dnodes_dev, int num_nodes, int N, Plan* out) {
         hipMemsetAsync(ctl, 0, sizeof(PlanCtl), nullptr) != hipSuccess)
         return bail(pt_fail(PT_ERR_DEVICE, "refit plan: upload failed"));
     hipLaunchKernelGGL(plan_order_kernel, dim3(G), dim3(kThreads), 0, nullptr, num_nodes, depth, out->level_begin, out->order, ctl);
-    if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess)
+    // every primitive must have found its leaf (leaf_slot is what the scatter indexes the node array with): count of leaf
+    // slots = 2 * inner nodes - (inner nodes - 1) = N holds for any binary tree that passed the checks above with in-range,
+    // distinct children; a primitive named twice would leave another one without a slot.  Checked where the table lives: one
+    // word comes back, not 4 bytes per primitive.
+    hipLaunchKernelGGL(plan_leaves_kernel, dim3(grid_for(N)), dim3(kThreads), 0, nullptr, out->leaf_slot, N, num_nodes, ctl);
+    unsigned int leaf_err = 1;
+    if (hipGetLastError() != hipSuccess || hipMemcpy(&leaf_err, &ctl->err, sizeof leaf_err, hipMemcpyDeviceToHost) != hipSuccess)
         return bail(pt_fail(PT_ERR_DEVICE, "refit plan: kernels failed"));
-    // every primitive must have found its leaf (leaf_slot is what the scatter indexes the node array with)
-    {
-        // count of leaf slots = 2 * inner nodes - (inner nodes - 1) = N holds for any binary tree that passed the checks
-        // above with in-range, distinct children; a primitive named twice would leave another one without a slot
-        std::vector<int32_t> ls;
-        try { ls.resize((size_t)N); } catch (const std::exception&) { return bail(pt_fail(PT_ERR_DEVICE, "refit plan: out of host memory")); }
-        if (hipMemcpy(ls.data(), out->leaf_slot, (size_t)N * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess)
-            return bail(pt_fail(PT_ERR_DEVICE, "refit plan: readback failed"));
-        for (int32_t s : ls)
-            if (s < 0 || s >= 2 * num_nodes) return bail(pt_fail(PT_ERR_UNSUPPORTED, "refit plan: a primitive has no leaf"));
-    }
+    if (leaf_err) return bail(pt_fail(PT_ERR_UNSUPPORTED, "refit plan: a primitive has no leaf"));
     out->levels = levels;
     int top = 0;
     while (top + 1 < levels && lb[top + 2] - lb[top + 1] <= kNarrow) top++;
@@ -283,6 +321,14 @@ int ptf::plan_build(const void* dnodes_dev, int num_nodes, int N, Plan* out) {
 int ptf::leaf_boxes(const void* prims_dev, int N, float* boxes_dev, unsigned int* status_dev) {
     hipLaunchKernelGGL(leaf_boxes_kernel, dim3(grid_for(N)), dim3(kThreads), 0, nullptr, reinterpret_cast<const DPrim*>(prims_dev), N,
                        boxes_dev, status_dev);
+    HIPF(hipGetLastError());
+    return PT_OK;
+}
+
+int ptf::tree_leaf_boxes(const void* dnodes_dev, int num_nodes, int N, float* boxes_dev) {
+    if (!dnodes_dev || !boxes_dev || N < 2 || num_nodes != N - 1) return pt_fail(PT_ERR_INVALID_ARG, "leaf boxes of a tree: bad argument");
+    hipLaunchKernelGGL(gather_leaves_kernel, dim3(grid_for(num_nodes)), dim3(kThreads), 0, nullptr, reinterpret_cast<const DNode*>(dnodes_dev),
+                       num_nodes, N, boxes_dev);
     HIPF(hipGetLastError());
     return PT_OK;
 }

@@ -27,7 +27,7 @@ EXPORTS = [
     "pt_temporal_gradient", "pt_temporal_gradient_host", "pt_temporal_accumulate_adaptive", "pt_temporal_accumulate_adaptive_host",
     "pt_render_pixels", "pt_gradient_pixels", "pt_gradient_pixels_host", "pt_temporal_gradient_sparse", "pt_temporal_gradient_sparse_host",
     "pt_scene_set_groups", "pt_scene_transform", "pt_transform_geometry_host", "pt_transform_sphere_host",
-    "pt_trace_rays", "pt_render_guides_async",
+    "pt_trace_rays", "pt_render_guides_async", "pt_scene_rebuild",
 ]
 
 
@@ -46,6 +46,7 @@ def lib():
         L.pt_scene_create.argtypes = [C.POINTER(PtSceneDesc), C.POINTER(vp)]
         L.pt_scene_destroy.argtypes = [vp]
         L.pt_scene_update.argtypes = [vp, C.POINTER(PtSceneDesc), C.c_int]
+        L.pt_scene_rebuild.argtypes = [vp, C.c_int]
         L.pt_scene_set_groups.argtypes = [vp, ip, C.c_int32]
         L.pt_scene_transform.argtypes = [vp, C.POINTER(PtTransform), C.c_int32]
         L.pt_transform_geometry_host.argtypes = [C.POINTER(PtTransform), C.c_int32, vp, vp, vp, vp]
@@ -131,6 +132,13 @@ class DeviceScene:
         records are made on the device and both trees refitted.  Absolute, not cumulative.  Blocking."""
         M = _matrices(matrices)
         _check(lib().pt_scene_transform(self._h, M.ctypes.data_as(C.POINTER(PtTransform)), M.shape[0]))
+
+    def rebuild(self):
+        """pt_scene_rebuild: a fresh internal tree over the leaf boxes the handle holds now, adopted where it visits at least 10 %
+        fewer nodes than the caller's tree; records, groups, options and frame slots carry on.  Blocking.  Returns whether the
+        tree was adopted (info "rebuild_adopted")."""
+        _check(lib().pt_scene_rebuild(self._h, 0))
+        return bool(self.info("rebuild_adopted"))
 
     def set_option(self, key, value):
         _check(lib().pt_scene_set_option(self._h, key.encode(), int(value)))

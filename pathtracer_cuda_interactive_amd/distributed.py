@@ -120,5 +120,10 @@ class ShardedRenderer:
         """DeviceScene.update on this rank's scene (every rank applies the same edit before the next frame)."""
         self.scene.update(desc, geometry=geometry, shading=shading)
 
+    def rebuild(self):
+        """DeviceScene.rebuild on this rank's scene (every rank rebuilds at the same frame: the images do not depend on it, the
+        frame times do).  Returns whether this rank adopted its tree."""
+        return self.scene.rebuild()
+
     def close(self):
         self.scene.close()

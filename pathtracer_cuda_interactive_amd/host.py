@@ -39,6 +39,7 @@ def lib():
         L.pt_host_scene_get_desc.argtypes = [vp, C.POINTER(PtSceneDesc)]
         L.pt_host_scene_bvh_depth.argtypes = [vp]
         L.pt_host_refit_bvh.argtypes = [C.POINTER(PtSceneDesc), C.POINTER(PtBvhNode)]
+        L.pt_host_tree_cost.argtypes = [C.POINTER(PtSceneDesc), C.POINTER(C.c_double)]
         L.pt_host_compute_normals.argtypes = [C.POINTER(C.c_float), C.c_int, C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_float)]
         L.pt_host_camera_ray_data.argtypes = [C.POINTER(PtCamera), C.c_int, C.c_int, C.POINTER(C.c_float)]
         L.pt_host_camera_ray_data.restype = None
@@ -196,6 +197,14 @@ def refit_bvh(desc):
     d2.nodes = nodes.ctypes.data_as(C.POINTER(PtBvhNode))
     d2._keep = (nodes, desc)
     return d2
+
+
+def tree_cost(desc):
+    """pt_host_tree_cost: the summed fp64 box area of every inner node of desc's pool but the root, in pool index order — what
+    DeviceScene.info("tree_cost0_bits") measures on the device, up to the order of the sum.  Needs no GPU."""
+    out = C.c_double()
+    _check(lib().pt_host_tree_cost(C.byref(desc), C.byref(out)))
+    return out.value
 
 
 def compute_normals(P, I):

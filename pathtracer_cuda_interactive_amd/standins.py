@@ -106,3 +106,38 @@ def dragon_standin(scene_dir):
 
 
 BUILDERS = {"buddha_standin": buddha_standin, "dragon_standin": dragon_standin}
+
+
+# ---- a grid of cubes that trade places: the animation a refitted tree copes with worst ----------------------
+_CUBE_V = np.array([[x, y, z] for x in (-0.2, 0.2) for y in (-0.2, 0.2) for z in (-0.2, 0.2)], np.float32)
+_CUBE_I = np.array([[0, 1, 3], [0, 3, 2], [4, 6, 7], [4, 7, 5], [0, 4, 5], [0, 5, 1], [2, 3, 7], [2, 7, 6], [0, 2, 6], [0, 6, 4],
+                    [1, 5, 7], [1, 7, 3]], np.int32)
+
+
+def grid_cell_centres(n):
+    k = np.arange(n ** 3)
+    return np.stack([k // (n * n), (k // n) % n, k % n], axis=1).astype(np.float64)
+
+
+def grid_scene(n, width=64, height=48, spp=4):
+    """n^3 cubes of edge 0.4 on a unit grid, one mesh of 12 triangles per cube (device.groups_by_object: one group per cube),
+    four diffuse materials, a point light and a bright background."""
+    hs = HostScene()
+    c = 0.5 * (n - 1)
+    hs.set_camera((c + 1.3 * n, c + 0.9 * n, c + 1.7 * n), (c, c, c), (0, 1, 0), 40.0, width, height, spp)
+    hs.set_background((0.7, 0.8, 0.9))
+    rng = np.random.default_rng(100 + n)
+    mats = [hs.add_material(PT_MAT_DIFFUSE, rng.random(3) * 0.7 + 0.2) for _ in range(4)]
+    hs.add_point_light((c, 3.0 * n, c + 0.5 * n), (40.0 * n * n,) * 3)
+    for k, ctr in enumerate(grid_cell_centres(n)):
+        hs.add_mesh(_CUBE_V + ctr.astype(np.float32), _CUBE_I, mats[k % 4])
+    return hs
+
+
+def grid_shuffle_matrices(n, seed=1):
+    """One row-major 3x4 translation per cube [n^3, 3, 4]: cube i moves to the cell np.random.default_rng(seed).permutation(n^3)[i]."""
+    ctr = grid_cell_centres(n)
+    M = np.zeros((n ** 3, 3, 4), np.float32)
+    M[:, 0, 0] = M[:, 1, 1] = M[:, 2, 2] = 1.0
+    M[:, :, 3] = (ctr[np.random.default_rng(seed).permutation(n ** 3)] - ctr).astype(np.float32)
+    return M

@@ -2,7 +2,7 @@
 
   python tools/animate.py SCENE.pts [--frames 8] [--size 640x480] [--spp 2] [--translate DX,DY,DZ | --orbit DEG] [--wobble]
                           [--denoise | --variance | --gradient | --gradient-sparse] [--relight K:R,G,B] [--reference-spp N] [--out PREFIX] [--time]
-                          [--spin G:AXIS:DEG_PER_FRAME ...] [--async-guides]
+                          [--spin G:AXIS:DEG_PER_FRAME ... [--rebuild-at PERMILLE]] [--async-guides]
 
 Per frame: pt_render at --spp, pt_render_guides against the previous frame's camera (and, with --wobble, the previous
 geometry: every mesh gets device.wobbled_desc's per-vertex wobble through DeviceScene.update), pt_temporal_accumulate, and with
@@ -21,6 +21,9 @@ parameters at that list on the current scene (stage "list"), and pt_temporal_gra
 --spin G:AXIS:DEG_PER_FRAME (repeatable): object G — mesh G, or sphere G - num_meshes, device.groups_by_object's
 numbering — turns about the x, y or z axis through its centroid by that many degrees per frame through DeviceScene.transform: the
 matrices go to the device, no vertex is touched on the host, and the guides follow the previous transform's records.  Not with --wobble.
+--rebuild-at PERMILLE (with --spin): option "rebuild_at_permille" on the animated handle — a transform after which
+the internal tree's summed box area has reached PERMILLE / 1000 of what it was built with rebuilds the tree inside the same call.
+Frames are rendered with "stats" 1; every frame's line carries its node visits, the cost ratio and "rebuilt" where that happened.
 --async-guides: the guide stage is pt_render_guides_async on the frame's stream, so a frame is enqueued stage after
 stage without a host sync in between; the images are the same, bit for bit.
 --relight K:R,G,B: from frame K on every light's radiance is scaled by (R, G, B) through DeviceScene.update(shading=True).
@@ -141,7 +144,10 @@ def main():
     ap.add_argument("--out", default="")
     ap.add_argument("--time", action="store_true")
     ap.add_argument("--async-guides", action="store_true")
+    ap.add_argument("--rebuild-at", type=int, default=0, metavar="PERMILLE")
     a = ap.parse_args()
+    if a.rebuild_at and not a.spin:
+        ap.error("--rebuild-at needs --spin")
     a.gradient = a.gradient or a.gradient_sparse
     a.variance = a.variance or a.gradient
     relight_at, relight_factor = None, None
@@ -157,6 +163,9 @@ def main():
         if a.wobble:
             ap.error("--spin and --wobble both move the geometry: give one")
         spin_matrices = spin_setup(d0, a.spin, [s for s in (ds, ref) if s is not None])
+        if a.rebuild_at:
+            ds.set_option("rebuild_at_permille", a.rebuild_at)
+            ds.set_option("stats", 1)
     stream = torch.cuda.current_stream().cuda_stream
     f3 = lambda: torch.empty((h, w, 3), device="cuda")           # noqa: E731
     f1 = lambda: torch.empty((h, w), device="cuda")              # noqa: E731
@@ -205,8 +214,10 @@ def main():
             ds.update(desc_k, geometry=moved, shading=relit)
             update_ms = ds.info("update_us0") / 1e3
         if spin_matrices is not None and k:
+            rebuilds = ds.info("rebuilds_auto")
             ds.transform(spin_matrices(k))
             update_ms = ds.info("transform_us0") / 1e3
+            rebuilt = ds.info("rebuilds_auto") > rebuilds
         if a.gradient:
             color = cur["color"]
         times["render"].append(once(lambda: ds.render_into(p, color.data_ptr(), stream)))
@@ -259,6 +270,10 @@ def main():
             line += f"  (update {update_ms:.3f} ms)"
         elif spin_matrices is not None and k:
             line += f"  (transform {update_ms:.3f} ms)"
+            if a.rebuild_at:
+                line += f"  tree cost {ds.info('tree_cost1_permille')} permille" + ("  rebuilt" if rebuilt else "")
+        if a.rebuild_at:
+            line += f"  node visits {ds.counters().node_visits}"
         if a.gradient and k:
             line += f"  lambda: mean {float(lam.mean()):.3f}, {float((lam > 0).float().mean()):.3f} of the tiles positive"
         valid = prev_depth > 0

@@ -1,11 +1,8 @@
 // pt_api.hip — kernels and C ABI of libpt_hip.so (gfx950 only).  See include/pt_api.h.
 //
-// Host half of the library: scene validation and re-layout, scratch management, kernel selection and launch,
-// the extern "C" entry points.  The kernels live in pt_kernels.h, the device functions in pt_trace.h / pt_math.h.
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
-#include <chrono>
+// Host half of a live handle: scratch management, kernel selection and launch, guides and queries, the image-space stages,
+// options and info, the debug entry points.  The handle and its lifecycle: pt_scene.h, pt_scene_life.hip.  The kernels live
+// in pt_kernels.h, the device functions in pt_trace.h / pt_math.h.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -14,20 +11,9 @@
 #include <iterator>
 #include <limits>
 #include <mutex>
-#include <queue>
-#include <string>
 #include <type_traits>
-#include <utility>
-#include <vector>
 
-#include "../../include/pt_api.h"
-#include "pt_internal.h"
-#include "pt_tree_sweep.h"
-#include "pt_sweep_build.h"
-#include "pt_scene_prep.h"
-#include "pt_scene_refit.h"
-#include "pt_tree_cost.h"
-#include "pt_scene_transform.h"
+#include "pt_scene.h"
 #include "pt_transform.h"
 #include "pt_denoise.h"
 #include "pt_gradient.h"
@@ -36,101 +22,22 @@
 #include "pt_kernel_q.h"
 #include "pt_query.h"
 
-using namespace ptl;
 using namespace ptk;
 
-// ------------------------------------------------------------------------------------------
-// host side
-// ------------------------------------------------------------------------------------------
-namespace {
+static thread_local std::string g_err;
+int pt_fail(int code, const std::string& msg) { g_err = msg; return code; }
+static int fail(int code, const std::string& msg) { return pt_fail(code, msg); }
 
-thread_local std::string g_err;
-
-int fail(int code, const std::string& msg) {
-    g_err = msg;
-    return code;
-}
-
-}  // namespace
-
-int pt_fail(int code, const std::string& msg) { return fail(code, msg); }
-
-namespace {
-
-#define HIP_TRY(expr)                                                                              \
-    do {                                                                                           \
-        hipError_t e_ = (expr);                                                                    \
-        if (e_ != hipSuccess)                                                                      \
-            return fail(e_ == hipErrorNoDevice ? PT_ERR_NO_DEVICE : PT_ERR_DEVICE,                 \
-                        std::string(#expr) + ": " + hipGetErrorString(e_));                        \
-    } while (0)
-
-template <class T>
-struct DevBuf {
-    T* p = nullptr;
-    size_t n = 0;
-    DevBuf() = default;
-    DevBuf(const DevBuf&) = delete;
-    DevBuf& operator=(const DevBuf&) = delete;
-    ~DevBuf() { release(); }          // the owner makes the buffer's device current first (pt_scene_destroy)
-    int ensure(size_t count) {
-        if (count <= n && p) return PT_OK;
-        if (p) { (void)hipFree(p); p = nullptr; n = 0; }
-        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&p), std::max<size_t>(count, 1) * sizeof(T)));
-        n = count;
-        return PT_OK;
-    }
-    void release() { if (p) (void)hipFree(p); p = nullptr; n = 0; }
-};
-
-// Makes the scene's device current for the duration of a call and restores the caller's device afterwards.
-struct DeviceGuard {
-    int prev = -1;
-    bool switched = false;
-    int enter(int device) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != device) {
-            HIP_TRY(hipSetDevice(device));
-            switched = true;
-        }
-        return PT_OK;
-    }
-    ~DeviceGuard() { if (switched && prev >= 0) (void)hipSetDevice(prev); }
-};
-
-constexpr uint32_t kLdsSceneLimit = 36 * 1024;   // scenes up to this size (64-B nodes) are staged whole into LDS
-constexpr uint32_t kOctNodeLimit = 24 * 1024;    // 8 octant copies of the node table must fit in this many bytes of LDS
-constexpr int kMaxStack = 64;                    // the reference's own cap (scene.h:251)
-constexpr int kMinInternalTree = 16;              // primitives below which no internal tree is built (a handful of nodes either way: scene1, 4 shapes, is 6 % slower with one)
-constexpr int kDeviceSweepMin = 4096;             // primitives from which the internal tree is built on the device (below: a few ms on the host either way)
-constexpr int kProbeRays = 32768;                // validate_and_build: rays that choose between the caller's tree and the internal one
-constexpr uint64_t kDefaultScratchBytes = 8ull << 30;   // per-sample scratch cap (3 % of the 288 GB of HBM): every sample pass
-                                                        // pays the launch floor once (buddha stand-in 135.6 ms in 5 passes, 130.6 in 1)
-#ifndef PT_TOP_NODES
-#define PT_TOP_NODES 512
-#endif
-constexpr uint32_t kTopNodes = PT_TOP_NODES;              // scenes read from global memory: this many nodes are numbered breadth-first
-                                                 // from the root, so that [0, k) is the top of the tree for every k (LDS cache)
-#ifndef PT_TOP_LDS_KB
-#define PT_TOP_LDS_KB 26
-#endif
-constexpr uint32_t kTopLdsBudget = PT_TOP_LDS_KB * 1024;    // LDS per block that keeps 6 blocks per CU resident (160 KB / 6)
-constexpr uint32_t kMaxLdsBudget = 160 * 1024;               // the breadth-first numbered prefix is sized for the largest budget an option may ask for
-constexpr int kMaxFramesInFlight = 4;            // frame slots a handle may hold (option frames_in_flight)
-#ifndef PT_FRAMES_IN_FLIGHT
-#define PT_FRAMES_IN_FLIGHT 2
-#endif
-constexpr int kDefaultFramesInFlight = PT_FRAMES_IN_FLIGHT;
-constexpr size_t kWorkBytes = 8 * kCounterStride * sizeof(uint32_t);   // 8 band counters, one 128-B line each
-constexpr size_t kWorkWords = kWorkBytes / sizeof(unsigned long long);
-
-uint32_t align16(uint32_t v) { return (v + 15u) & ~15u; }
+static_assert(ptkc::kBlock == ptk::kBlock && ptkc::kLdsNodeStride == ptk::kLdsNodeStride && ptkc::kCounterStride == ptk::kCounterStride &&
+                  ptkc::kQueryRing == ptq::kQueryRing, "pt_scene.h restates these constants of pt_kernels.h / pt_query.h (a -DPT_BLOCK or -DPT_LDS_NODE_STRIDE build changes them there too)");
 
 // every float finite?  (leaf boxes that stayed on the device)
+namespace {
 __global__ void finite_kernel(const float* __restrict__ v, size_t n, unsigned int* __restrict__ bad) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n && !__builtin_isfinite(v[i])) atomicAdd(bad, 1u);
 }
+}  // namespace
 bool boxes_finite_device(const float* v_dev, size_t n) {
     unsigned int* bad = nullptr;
     if (hipMalloc(reinterpret_cast<void**>(&bad), sizeof(unsigned int)) != hipSuccess) return false;
@@ -143,519 +50,12 @@ bool boxes_finite_device(const float* v_dev, size_t n) {
     return h == 0;
 }
 
-// PT_SWEEP_BUILD=host in the environment keeps the internal tree's build on the host (A/B timing, debugging)
-bool host_sweep_forced() {
-    const char* v = std::getenv("PT_SWEEP_BUILD");
-    return v && std::string(v) == "host";
-}
+constexpr int kProbeRays = 32768;                // pt_scene_create, pt_scene_rebuild: rays that choose between the caller's tree and the internal one
 
-}  // namespace
-
-struct pt_scene {
-    int device = 0;
-    int num_cus = 0;
-    size_t lds_per_block_max = 0;
-    // scene arrays.  Two layouts of the hierarchy: tree[0] = the caller's tree (the reference's, bvh.cu:16-54), tree[1] = the
-    // library's internal tree over the SAME leaf boxes, made at create time (validate_and_build: the full-sweep surface-area
-    // tree of pt_tree_sweep.h / pt_sweep_build.hip, or the caller's own topology in internal form).  Exact traversal runs on
-    // tree[1] and falls back to tree[0] for the rays whose result depends on the visit order (see launch_render).
-    struct Tree {
-        DevBuf<DNode> nodes;
-        DevBuf<DNode> nodes_oct;     // [8][num_nodes] octant-specialised copies (small scenes only)
-        bool have_oct = false;
-        int32_t num_nodes = 0, root_ref = 0, stack_cap = 0;
-        uint32_t top_avail = 0;      // nodes [0, top_avail) are the top of the tree in breadth-first order (0 = plain pre-order)
-        int depth = 0;
-    } tree[2];
-    bool have_fast = false;
-    DevBuf<unsigned long long> ref_path;   // per primitive: its root-to-leaf turns in the caller's tree (ties on t, pt_trace.h: ref_visits_first)
-    DevBuf<int32_t> ref_anc;         // per primitive and level: the inner node of the caller's tree there
-    int32_t ref_levels = 0;
-    bool fast_is_callers_topology = false;   // tree[1] = the caller's own tree in internal form (the sweep tree did not win)
-    DevBuf<DPrim> prims;
-    DevBuf<DNormals> normals;
-    DevBuf<DMaterial> materials;
-    DevBuf<DEmission> emission;
-    DevBuf<DLight> lights;
-    SceneDev dev{};
-    uint32_t scene_bytes = 0;
-    // pt_scene_update: new primitive records and leaf boxes are made and checked in staging memory before the handle changes
-    // (the record buffers then trade places with prims / normals); one refit plan per tree, made on the first geometry update
-    DevBuf<DPrim> st_prims;
-    DevBuf<DNormals> st_normals;
-    // pt_render_guides: the primitive records that were live before the last successful geometry update.  Allocated on the
-    // first geometry update; the three record buffers then rotate (staging -> current -> previous -> staging), so that an
-    // update that fails in staging destroys neither set and none is ever copied.
-    DevBuf<DPrim> prev_prims;
-    bool have_prev = false;
-    DevBuf<float> st_boxes;
-    DevBuf<unsigned int> st_status;
-    ptf::Plan refit_plan[2];
-    int64_t updates = 0, update_us[4] = {0, 0, 0, 0};   // [0] total [1] records + uploads [2] refit + octant tables [3] plan build
-    // pt_scene_transform: the group of every shape and the table of group entries (pt_transform.h); the REST records, a copy of
-    // prims / normals made on the first transform after pt_scene_create or a geometry update, which every transform starts from
-    DevBuf<int32_t> group_of;
-    DevBuf<float> group_tab;
-    int32_t num_groups = 0;
-    bool have_groups = false;
-    DevBuf<DPrim> rest_prims;
-    DevBuf<DNormals> rest_normals;
-    bool have_rest = false;
-    int64_t transforms = 0, transform_us[4] = {0, 0, 0, 0};   // [0] total [1] records [2] refit [3] snapshot + plan build
-    // pt_scene_rebuild: calls that succeeded, those among them a policy made (option rebuild_at_permille), whether the last one
-    // adopted its tree and that tree's probe ratio; wall time: [0] total [1] leaf boxes + build [2] re-layout + probe
-    // [3] plan + sweep tables.  no_fast_why: why pt_scene_create kept no internal tree (the refusal's message).
-    int64_t rebuilds = 0, rebuilds_auto = 0, rebuild_adopted = 0, rebuild_cost_permille = 0, rebuild_us[4] = {0, 0, 0, 0};
-    const char* no_fast_why = "";
-    // tree-cost telemetry (pt_tree_cost.hip; options tree_cost, rebuild_at_permille): per tree the cost of the boxes as built
-    // (taken before the first refit that follows) and after the last refit.  cost_dev / cost_host: [0..1] reference, [2..3]
-    // current, device results and their pinned host copies; the copies are enqueued behind the refit and read once the call
-    // has synchronised (cost_pending_*).
-    int64_t opt_tree_cost = 0, opt_rebuild_at = 0;
-    DevBuf<double> cost_partials, cost_dev;
-    double* cost_host = nullptr;
-    double cost_ref[2] = {0.0, 0.0}, cost_now[2] = {0.0, 0.0};
-    bool cost_have_ref[2] = {false, false}, cost_pending_ref[2] = {false, false}, cost_pending_now[2] = {false, false};
-    bool cost_on() const { return opt_tree_cost != 0 || opt_rebuild_at != 0; }
-    bool tri_only = false;           // the scene holds no sphere
-    bool diffuse_only = false;       // every material is DIFFUSE
-    // scratch
-    DevBuf<float> accum;
-    DevBuf<float> fb_tmp;
-    // pt_render_adaptive: per packed pixel the running fp32 sum and fp64 moments, the two ping-pong lists of pixels still
-    // sampled, the next list's length, and host-output staging for spp_map / err_map
-    DevBuf<float> ad_sum;
-    DevBuf<double> ad_mom;
-    DevBuf<uint32_t> ad_list[2];
-    DevBuf<uint32_t> ad_count;
-    DevBuf<int32_t> ad_spp_tmp;
-    DevBuf<float> ad_err_tmp;
-    int64_t info_adaptive_rounds = 0;
-    // pt_denoise: the guide record and the two ping-pong colour records per pixel (pt_denoise.h), and staging of a frame that
-    // comes in host memory (run_staged: the planes of the call; the result goes back through the colour plane)
-    DevBuf<float4> dn_guide, dn_x[2];
-    DevBuf<float> dn_host;
-    DevBuf<float> tp_host;           // pt_temporal_accumulate(_moments): staging of a call that comes in host memory
-    // pt_denoise_variance: records of its own (a call may be in flight on another stream than pt_denoise's) and staging of a
-    // call that comes in host memory
-    DevBuf<float4> vd_guide, vd_x[2];
-    DevBuf<float> vd_host;
-    // pt_temporal_gradient: the two ping-pong tile records (pt_gradient.h, two float4 per tile), allocated on first use and
-    // grown when a larger frame arrives, and staging of a call that comes in host memory
-    DevBuf<float4> gr_x[2];
-    DevBuf<float> gr_host;
-    // pt_render_pixels: staging of a list that comes in host memory (the colours go back through fb_tmp)
-    DevBuf<int32_t> px_list;
-    // pt_trace_rays / pt_render_guides_async (pt_query.h): every launch of the query kernel takes the next work counter of a ring
-    // (a 128-B line each), cleared on the launch's stream; the entry's event is recorded behind the launch, and a launch that
-    // finds the event of its entry still pending makes its stream wait for it — two launches in flight never share a counter.
-    // Staging of a pt_trace_rays call that comes in host memory: grown on demand, freed with the handle.
-    DevBuf<uint32_t> q_counters;
-    hipEvent_t q_event[ptq::kQueryRing] = {};
-    uint64_t q_seq = 0;                                   // query launches so far
-    DevBuf<float> q_rays, q_tuv;
-    DevBuf<int32_t> q_prim;
-    int64_t opt_query_blocks = 0;                         // 0 = automatic grid, else exactly this many blocks
-    int64_t opt_query_refill = 0;                         // 0 = automatic, else idle lanes from which a wave refills (1 .. 64)
-    int64_t opt_query_guides = 0;                         // pt_render_guides_async: 0 = automatic, 1 = the refilling kernel, 2 = aov_kernel
-    int64_t info_query_guides = 0;                        // the last pt_render_guides_async ran on the refilling kernel (1) or on aov_kernel (0)
-    int64_t info_query_grid = 0;                          // blocks of the last query launch
-    const void* q_cfg_fn = nullptr;                       // occupancy of the last query kernel variant used (as cfg_fn below)
-    uint32_t q_cfg_lds = 0;
-    int q_cfg_occ = 0;
-    void drop_query() {
-        q_counters.release(); q_rays.release(); q_tuv.release(); q_prim.release();
-        for (auto& e : q_event) { if (e) (void)hipEventDestroy(e); e = nullptr; }
-    }
-    // What a frame's trace kernel writes lives in a frame slot; render call k uses slot k % frames_in_flight.  With more than one
-    // slot a single-pass frame runs on the slot's own stream: the trace kernel at once (it reads the immutable scene and writes
-    // the slot only), the resolve — the one step that touches the caller's buffer — once the caller's stream has reached the
-    // point of the call (in_ev), and the caller's stream continues behind the resolve (free_ev).  The next frame's trace kernel
-    // then fills the CUs while this one's last paths drain (the tail of a persistent launch is a partly empty chip), and
-    // everything the caller can observe stays in the order of the caller's stream.  Both waits across streams sit beside the
-    // chain trace k -> resolve k -> trace k + slots, which is in order on ONE stream (an event wait across streams costs tens of
-    // microseconds on this runtime; with the resolve on the caller's stream, two of them per frame sat on that chain and
-    // two slots rendered slower than one).  A slot is reused once the resolve that read its samples has finished (free_ev).
-    struct FrameSlot {
-        DevBuf<float4> samples;
-        // control block: [0, kWorkBytes) the band work counters, then the statistics (kNumCounters uint64, pt_kernels.h)
-        DevBuf<unsigned long long> ctl;
-        DevBuf<int32_t> redo_stack;  // global-memory traversal stacks of the reference-order reruns (one column per lane of the grid)
-        hipStream_t stream = nullptr;
-        hipEvent_t free_ev = nullptr, in_ev = nullptr;
-        hipStream_t free_stream = nullptr;   // the stream free_ev was last recorded on
-        bool used = false;
-    } slot[kMaxFramesInFlight];
-    int cur_slot = 0;                // the slot of the last render call
-    int64_t opt_frames_in_flight = kDefaultFramesInFlight;
-    FrameSlot& cur() { return slot[cur_slot]; }
-    const FrameSlot& cur() const { return slot[cur_slot]; }
-    uint32_t* work_counter() const { return reinterpret_cast<uint32_t*>(cur().ctl.p); }
-    unsigned long long* counters() const { return cur().ctl.p ? cur().ctl.p + kWorkWords : nullptr; }
-    void drop_slots() {
-        for (auto& f : slot) {
-            f.samples.release(); f.ctl.release(); f.redo_stack.release();
-            if (f.stream) (void)hipStreamDestroy(f.stream);
-            if (f.free_ev) (void)hipEventDestroy(f.free_ev);
-            if (f.in_ev) (void)hipEventDestroy(f.in_ev);
-            f.stream = nullptr; f.free_ev = nullptr; f.in_ev = nullptr; f.used = false;
-        }
-    }
-    hipStream_t last_stream = nullptr;
-    bool have_timing = false;
-    // options
-    int64_t opt_blocks_per_cu = 0;
-    int64_t opt_scratch_bytes = 0;
-    int64_t opt_force_global = 0;
-    int64_t opt_stats = 0;
-    int64_t opt_specialize = 1;      // compile-time specialisation on scene content (no spheres -> sphere code removed)
-    int64_t opt_octants = 1;         // use the 8 ray-octant node tables when the scene is small enough
-    int64_t opt_top_cache = 1;       // scenes in global memory: keep the top of the tree in LDS
-    int64_t opt_fast_tree = 1;       // exact traversal on the library's internal tree where one was kept (0 = on the caller's tree)
-    int64_t opt_chunk = 0;           // work items a wave reserves per atomic (0 = automatic)
-    int64_t opt_lds_budget_kb = 0;   // scenes in global memory: LDS per block for traversal stacks + top-of-tree cache (0 = 26 KB: 6 blocks per CU)
-    int64_t opt_item_order = 1;      // work item order inside a band: 1 = row-major (all samples of a row, then the next row), 0 = sample-major
-    int64_t opt_xcd_regions = 0;     // 0 = 8 row bands (one per XCD); 1 = a single work queue
-    int64_t opt_kernel = 2;          // 2 = decoupled traversal/shading (default), 1 = segment-synchronous wavefront kernel,
-                                     // 3 = paths regrouped across the waves of a workgroup (pt_kernel_q.h; LDS-resident scenes, else as 2)
-    int64_t opt_q_target = 0, opt_q_swap = 0, opt_q_low = 0;   // schedule knobs of kernel 3; 0 = automatic
-    int64_t opt_v2_thresh = 0, opt_v2_inner = 0, opt_v2_minw = 0;   // 0 = auto (see v2_schedule)
-    int64_t opt_reg_stack = 1;      // 1 = register traversal stack where it applies (choose_trace), 0 = always the LDS stack
-    int64_t opt_leaf_sweep = 1;     // 1 = leaves found by the box sweep where it applies (choose_trace), 0 = always the tree
-    // the groups of equal leaf boxes of tree[1] (pt_leaf_sweep.h), made at scene creation where the tree was built on the host
-    // and the scene has at most 64 primitives.  sweep_groups = 0: none (also after a geometry update: boxes that were equal need
-    // not be any more); it may exceed what a launch admits, sweep.count then stays 0.
-    SweepTable sweep{};
-    int sweep_groups = 0;
-    // what a sweep launch stages in place of the octant node tables (pt_sweep_layout.h: box tables, then slot records), made
-    // and uploaded with sweep.count, dropped with it
-    DevBuf<unsigned char> sweep_tab;
-    // info of last launch
-    // wall time of pt_scene_create's stages, microseconds: [0] total [1] primitive records [2] caller's tree checked and re-laid
-    // [3] internal tree built [4] ... re-laid [5] uploads + probe [6] tie tables; built_on_device: the sweep ran on the GPU
-    int64_t create_us[7] = {0, 0, 0, 0, 0, 0, 0}, sweep_on_device = 0;
-    int64_t info_grid = 0, info_lds_bytes = 0, info_lds_scene = 0, info_passes = 0, info_occupancy = 0, info_blocks_per_cu = 0, info_debug_reruns = 0, fast_cost_permille = 0, info_kernel = 0, info_trace_variant = 0, info_path_bank = 0, info_reg_stack = 0, info_leaf_sweep = 0;
-    struct PassEvents { hipEvent_t t0, t1, r0, r1; };            // trace begin, trace end (on the trace kernel's stream); resolve begin, end (caller's)
-    // HIP events of the last `opt_timing_frames` render calls (a ring; default 1): a caller that enqueues frame after frame
-    // without a host sync in between — bench.py's timed loop — reads every frame's kernel time afterwards (pt_get_frame_times)
-    struct FrameRec { std::vector<PassEvents> ev; size_t passes = 0; };
-    std::vector<FrameRec> frames;
-    uint64_t frame_seq = 0;                                      // render calls so far; the last one sits in frames[(frame_seq - 1) % size]
-    int64_t opt_timing_frames = 1;
-    const FrameRec* last_frame() const { return frame_seq && !frames.empty() ? &frames[(frame_seq - 1) % frames.size()] : nullptr; }
-    void drop_events() {
-        for (auto& f : frames)
-            for (auto& pe : f.ev) { (void)hipEventDestroy(pe.t0); (void)hipEventDestroy(pe.t1); (void)hipEventDestroy(pe.r0); (void)hipEventDestroy(pe.r1); }
-        frames.clear();
-        frame_seq = 0;
-    }
-    // launch configuration of the last kernel variant used (occupancy query and attribute call are not free per frame)
-    const void* cfg_fn = nullptr;
-    uint32_t cfg_lds = 0;
-    int cfg_occ = 0;
-};
-
-namespace {
-
-// Points a kernel argument block (select_tree: the handle's own) at one of the two trees; fallback: exact traversal on the internal tree — ties settled in the
-// caller's visit order, rays with a zero direction component traced on tree[0].
-// (T: the tree itself — S->tree[which], or pt_scene_rebuild's candidate for tree[1])
-void tree_view(const pt_scene* S, SceneDev& dv, const pt_scene::Tree& T, int which, bool fallback) {
-    dv.nodes = T.nodes.p;
-    dv.nodes_oct = T.have_oct ? T.nodes_oct.p : nullptr;
-    dv.num_nodes = T.num_nodes;
-    dv.root_ref = T.root_ref;
-    dv.stack_cap = T.stack_cap;
-    dv.fallback = fallback ? 1 : 0;
-    dv.ref_nodes = S->tree[0].nodes.p;
-    dv.ref_root_ref = S->tree[0].root_ref;
-    dv.redo_cap = S->tree[0].stack_cap;
-    dv.redo_stack = S->cur().redo_stack.p;
-    dv.fixed_order = which == 1 ? 1 : 0;
-    dv.ref_path = S->ref_path.p;
-    dv.ref_anc = S->ref_anc.p;
-    dv.ref_levels = S->ref_levels;
-}
-void tree_view(const pt_scene* S, SceneDev& dv, int which, bool fallback) { tree_view(S, dv, S->tree[which], which, fallback); }
-void select_tree(pt_scene* S, int which, bool fallback = false) { tree_view(S, S->dev, which, fallback); }
-
-struct TreeHost {
-    std::vector<DNode> nodes;
-    int32_t root_ref = 0;
-    int depth = 1;
-    int stack_need = 1;            // stack entries a traversal can hold at once (without the sentinel)
-    std::vector<int32_t> inner_of_pool;   // caller's node pool index -> index in `nodes` (-1: a leaf)
-    uint32_t top_avail = 0;
-};
-
-// pt_bvh_node pool (one node per leaf and per inner node, bvh.cuh:7-15) -> inner-only DNodes carrying both child boxes.
-// Validates the topology.  leaf_boxes (optional, [N][6]): receives every primitive's leaf box.  *nested: every node's box
-// below the root contains its children's boxes.
-int convert_tree(const pt_bvh_node* in, int num_nodes, int root, int N, TreeHost& out, float* leaf_boxes, bool* nested, bool internal = false) {
-    std::vector<int32_t> inner_id(num_nodes, -1);
-    std::vector<DNode>& nodes = out.nodes;
-    nodes.clear();
-    nodes.reserve(N > 1 ? N - 1 : 1);
-    int depth = 1;
-    std::vector<char> prim_seen(N, 0);
-    auto leaf_ok = [&](const pt_bvh_node& nd) { return nd.prim >= 0 && nd.prim < N; };
-    auto contains = [](const pt_bvh_node& outer, const pt_bvh_node& inner) {
-        for (int k = 0; k < 3; k++)
-            if (!(inner.bmin[k] >= outer.bmin[k] && inner.bmax[k] <= outer.bmax[k])) return false;
-        return true;
-    };
-    const pt_bvh_node& rootn = in[root];
-    if (rootn.prim != -1) {
-        if (!leaf_ok(rootn)) return fail(PT_ERR_BAD_SCENE, "leaf primitive id out of range");
-        out.root_ref = ~rootn.prim;
-        prim_seen[rootn.prim] = 1;
-        if (leaf_boxes) { std::memcpy(leaf_boxes + 6 * (size_t)rootn.prim, rootn.bmin, 12); std::memcpy(leaf_boxes + 6 * (size_t)rootn.prim + 3, rootn.bmax, 12); }
-    } else {
-        // The internal tree is traversed left child first (pt_trace.h: visit_node).  While the left subtree is being worked
-        // on, the right child waits on the stack: entries needed = max(1 + need(left), need(right)), so the child that needs
-        // less goes LEFT and the need of a node is the larger of its children's, plus one only when they are equal — the
-        // Strahler number of the tree, at most log2(leaves) + 1 whatever its depth.
-        std::vector<int32_t> need;
-        if (internal) {                                               // (the library's own tree: no validation needed here)
-            need.assign(num_nodes, 0);
-            std::vector<int32_t> pre, open;
-            open.push_back(root);
-            while (!open.empty()) {
-                const int32_t k = open.back();
-                open.pop_back();
-                pre.push_back(k);
-                for (int32_t ch : {in[k].left, in[k].right})
-                    if (in[ch].prim == -1) open.push_back(ch);
-            }
-            for (size_t k = pre.size(); k-- > 0;) {                  // parents come before their children in `pre`
-                const pt_bvh_node& nd = in[pre[k]];
-                const int32_t a = need[nd.left], b = need[nd.right];
-                need[pre[k]] = a == b ? a + 1 : std::max(a, b);
-            }
-            out.stack_need = need[root];
-        }
-        auto swapped = [&](const pt_bvh_node& nd) { return internal && need[nd.left] > need[nd.right]; };
-        // DFS pre-order: a parent and the subtree of the child it lists first are contiguous in memory
-        struct Item { int32_t ref_node; int depth; };
-        std::vector<Item> todo;
-        todo.push_back({root, 1});
-        size_t visited = 0;
-        std::vector<int32_t> order;
-        while (!todo.empty()) {
-            Item it = todo.back();
-            todo.pop_back();
-            const pt_bvh_node& nd = in[it.ref_node];
-            if (++visited > (size_t)num_nodes) return fail(PT_ERR_BAD_SCENE, "BVH is not a tree (cycle)");
-            if (inner_id[it.ref_node] != -1) return fail(PT_ERR_BAD_SCENE, "BVH node referenced twice");
-            if (nd.left < 0 || nd.left >= num_nodes || nd.right < 0 || nd.right >= num_nodes)
-                return fail(PT_ERR_BAD_SCENE, "BVH child index out of range");
-            inner_id[it.ref_node] = (int32_t)order.size();
-            order.push_back(it.ref_node);
-            if (it.depth + 1 > depth) depth = it.depth + 1;
-            const pt_bvh_node& ln = in[nd.left];
-            const pt_bvh_node& rn = in[nd.right];
-            if (it.ref_node != root && nested && !(contains(nd, ln) && contains(nd, rn))) *nested = false;
-            const bool sw = swapped(nd);
-            const int32_t first = sw ? nd.right : nd.left, second = sw ? nd.left : nd.right;
-            if (in[second].prim == -1) todo.push_back({second, it.depth + 1});
-            if (in[first].prim == -1) todo.push_back({first, it.depth + 1});
-        }
-        // Scenes too big for LDS: renumber so that the first kTopNodes ids are the top of the tree in breadth-first order
-        // (every ray starts there; the kernel keeps a prefix of them in LDS), the rest stays in pre-order.
-        if ((size_t)N * (sizeof(DPrim) + sizeof(DNormals)) + order.size() * sizeof(DNode) > kLdsSceneLimit && order.size() > 1) {
-            // only as many as fit next to the traversal stacks (make_plan)
-            const uint32_t stack_bytes = (uint32_t)(kBlock / 64) * (uint32_t)((internal ? out.stack_need : std::max(depth - 1, 1)) + 1) * 64u * 4u;
-            const size_t want = std::min<size_t>(kTopNodes, kMaxLdsBudget > stack_bytes ? (kMaxLdsBudget - stack_bytes) / sizeof(DNode) : 0);
-            // which ones: without pruning a node is visited iff the ray hits its box, so the nodes most rays visit are the ones
-            // with the largest boxes — take them in order of surface area (a child's box is never larger than its parent's,
-            // so every prefix of this list is closed under "parent of"; the kernel stages a prefix)
-            std::vector<int32_t> top;
-            std::vector<char> in_top(num_nodes, 0);
-            auto area = [&](int32_t k) {
-                const pt_bvh_node& b = in[k];
-                const double x = (double)b.bmax[0] - b.bmin[0], y = (double)b.bmax[1] - b.bmin[1], z = (double)b.bmax[2] - b.bmin[2];
-                return 2.0 * (x * y + y * z + z * x);
-            };
-            typedef std::pair<double, int32_t> Cand;                  // (area, -position in pre-order): ties go to the earlier node
-            std::priority_queue<Cand> open;
-            if (want) open.push(Cand(std::numeric_limits<double>::infinity(), 0));
-            while (!open.empty() && top.size() < want) {
-                const int32_t k = order[(size_t)-open.top().second];
-                open.pop();
-                top.push_back(k);
-                const pt_bvh_node& nd = in[k];
-                for (int32_t ch : {nd.left, nd.right})
-                    if (in[ch].prim == -1) open.push(Cand(area(ch), -inner_id[ch]));
-            }
-            for (int32_t r : top) in_top[r] = 1;
-            std::vector<int32_t> renum(top);
-            for (int32_t r : order)
-                if (!in_top[r]) renum.push_back(r);
-            order.swap(renum);
-            for (size_t k = 0; k < order.size(); k++) inner_id[order[k]] = (int32_t)k;
-            out.top_avail = (uint32_t)top.size();
-        }
-        nodes.resize(order.size());
-        for (size_t k = 0; k < order.size(); k++) {
-            const pt_bvh_node& nd = in[order[k]];
-            const bool sw = swapped(nd);
-            const int32_t li = sw ? nd.right : nd.left, ri = sw ? nd.left : nd.right;
-            const pt_bvh_node& ln = in[li];
-            const pt_bvh_node& rn = in[ri];
-            DNode& o = nodes[k];
-            std::memcpy(o.lmin, ln.bmin, 12); std::memcpy(o.lmax, ln.bmax, 12);
-            std::memcpy(o.rmin, rn.bmin, 12); std::memcpy(o.rmax, rn.bmax, 12);
-            for (const pt_bvh_node* ch : {&ln, &rn})
-                if (ch->prim != -1) {
-                    if (!leaf_ok(*ch)) return fail(PT_ERR_BAD_SCENE, "leaf primitive id out of range");
-                    if (prim_seen[ch->prim]) return fail(PT_ERR_BAD_SCENE, "primitive referenced by two leaves");
-                    prim_seen[ch->prim] = 1;
-                    if (leaf_boxes) { std::memcpy(leaf_boxes + 6 * (size_t)ch->prim, ch->bmin, 12); std::memcpy(leaf_boxes + 6 * (size_t)ch->prim + 3, ch->bmax, 12); }
-                }
-            o.left = ln.prim != -1 ? ~ln.prim : inner_id[li];
-            o.right = rn.prim != -1 ? ~rn.prim : inner_id[ri];
-            o.pad0 = o.pad1 = 0;
-        }
-        out.root_ref = 0;
-    }
-    for (int i = 0; i < N; i++)
-        if (!prim_seen[i]) return fail(PT_ERR_BAD_SCENE, "primitive not covered by any leaf");
-    if (!internal && depth - 1 > kMaxStack - 1)
-        return fail(PT_ERR_BAD_SCENE, "BVH deeper than the traversal stack (reference cap 64, scene.h:251)");
-    out.depth = depth;
-    out.inner_of_pool.swap(inner_id);
-    if (!internal) out.stack_need = std::max(depth - 1, 1);           // nearer child first: a pending sibling per level
-    if (nodes.empty()) nodes.resize(1);   // single-primitive scene: no inner nodes; keep a dummy so pointers are valid
-    return PT_OK;
-}
-
-// ---- checks and conversions pt_scene_create and pt_scene_update share -------------------------------------------------------
-int check_materials(const pt_scene_desc* d) {
-    for (int m = 0; m < d->num_materials; m++)
-        if (d->materials[m].type < PT_MAT_DIFFUSE || d->materials[m].type > PT_MAT_PHONG)
-            return fail(PT_ERR_BAD_SCENE, "unknown material type (scene.h:410 asserts)");
-    return PT_OK;
-}
-int check_meshes(const pt_scene_desc* d, int num_materials) {
-    for (int m = 0; m < d->num_meshes; m++) {
-        const pt_mesh& me = d->meshes[m];
-        if (me.num_vertices <= 0 || me.num_faces <= 0 || !me.positions || !me.indices)
-            return fail(PT_ERR_BAD_SCENE, "empty mesh");
-        if (!me.normals) return fail(PT_ERR_BAD_SCENE, "mesh without vertex normals (required, SURVEY H5a)");
-        if (me.material_id < 0 || me.material_id >= num_materials) return fail(PT_ERR_BAD_SCENE, "mesh material id out of range");
-    }
-    return PT_OK;
-}
-bool all_diffuse(const pt_scene_desc* d) {
-    for (int m = 0; m < d->num_materials; m++)
-        if (d->materials[m].type != PT_MAT_DIFFUSE) return false;
-    return true;
-}
-// materials and lights as the kernels read them; N = number of shapes (an area light names its emitting shape)
-int pack_shading(const pt_scene_desc* d, int N, std::vector<DMaterial>& mats, std::vector<DEmission>& emis, std::vector<DLight>& dlights) {
-    mats.resize(d->num_materials);
-    for (int m = 0; m < d->num_materials; m++) {
-        const pt_material& src = d->materials[m];
-        mats[m] = DMaterial{src.type, src.reflectance[0], src.reflectance[1], src.reflectance[2], src.eta, src.exponent, 0.0f, 0.0f};
-    }
-    emis.resize(std::max(d->num_lights, 1));
-    std::memset(emis.data(), 0, sizeof(DEmission) * emis.size());
-    for (int l = 0; l < d->num_lights; l++) {
-        const pt_light& src = d->lights[l];
-        emis[l] = DEmission{src.radiance[0], src.radiance[1], src.radiance[2], src.type == PT_LIGHT_DIFFUSE_AREA ? 1 : 0};
-    }
-    dlights.resize(std::max(d->num_lights, 1));
-    std::memset(dlights.data(), 0, sizeof(DLight) * dlights.size());
-    for (int l = 0; l < d->num_lights; l++) {
-        const pt_light& src = d->lights[l];
-        dlights[l] = DLight{src.radiance[0], src.radiance[1], src.radiance[2], src.type == PT_LIGHT_DIFFUSE_AREA ? 1 : 0,
-                            src.position[0], src.position[1], src.position[2], src.shape_id};
-        if (src.type == PT_LIGHT_DIFFUSE_AREA && (src.shape_id < 0 || src.shape_id >= N))
-            return fail(PT_ERR_BAD_SCENE, "area light refers to a shape that does not exist");
-    }
-    return PT_OK;
-}
-
-// ---- the internal-tree stage: what pt_scene_create and pt_scene_rebuild both run ---------------------------------------------
-// A tree the host made, into T's buffers with its metadata.
-int upload_tree(pt_scene::Tree& T, const TreeHost& H) {
-    const std::vector<DNode>& nodes = H.nodes;
-    // 8 ray-octant copies of the node table for LDS-resident scenes: octant bit k set <=> 1/d[k] < 0, in which case
-    // Hit() swaps the two slab distances of axis k (bbox.cuh:40-55); here the two planes are swapped instead.
-    T.have_oct = false;
-    if (nodes.size() * 8 * sizeof(DNode) <= kOctNodeLimit) {
-        std::vector<DNode> nodes_oct(nodes.size() * 8);
-        for (int o = 0; o < 8; o++)
-            for (size_t k = 0; k < nodes.size(); k++) {
-                DNode n = nodes[k];
-                for (int ax = 0; ax < 3; ax++)
-                    if (o & (1 << ax)) { std::swap(n.lmin[ax], n.lmax[ax]); std::swap(n.rmin[ax], n.rmax[ax]); }
-                nodes_oct[(size_t)o * nodes.size() + k] = n;
-            }
-        int r;
-        if ((r = T.nodes_oct.ensure(nodes_oct.size()))) return r;
-        HIP_TRY(hipMemcpy(T.nodes_oct.p, nodes_oct.data(), nodes_oct.size() * sizeof(DNode), hipMemcpyHostToDevice));
-        T.have_oct = true;
-    }
-    int r;
-    if ((r = T.nodes.ensure(nodes.size()))) return r;
-    HIP_TRY(hipMemcpy(T.nodes.p, nodes.data(), nodes.size() * sizeof(DNode), hipMemcpyHostToDevice));
-    T.num_nodes = (int32_t)nodes.size();
-    T.root_ref = H.root_ref;
-    T.stack_cap = H.stack_need + 1;                         // + the kDone sentinel at the bottom
-    T.top_avail = H.top_avail;
-    T.depth = H.depth;
-    return PT_OK;
-}
-
-// The sweep tree of N leaf boxes in device memory, built (pt_sweep_build.hip) and re-laid (pt_scene_prep.hip) there, into T.
-// built(): called between the two (stage timing).  false: the builder handed the input back (depth guard) or something
-// failed; T.nodes is released and the host builder is next.
-template <class Built>
-bool internal_tree_device(const float* boxes_dev, int N, pt_scene::Tree& T, Built built) {
-    DevBuf<pt_bvh_node> fpool_dev;
-    DevBuf<int32_t> fiop_dev;
-    int32_t fdepth = 0;
-    double dev_ms = 0;
-    const size_t pool_nodes = 2 * (size_t)N - 1;
-    const bool ok = !fpool_dev.ensure(pool_nodes) && !fiop_dev.ensure(pool_nodes) && !T.nodes.ensure((size_t)N - 1) &&
-                    boxes_finite_device(boxes_dev, (size_t)N * 6) &&
-                    pts::sweep_build_on_device(boxes_dev, N, fpool_dev.p, &fdepth, &dev_ms) == PT_OK;
-    built();
-    ptp::RelayResult r1;
-    if (ok && ptp::relay_tree_device(fpool_dev.p, (int)pool_nodes, 0, N, true, T.nodes.p, fiop_dev.p, nullptr, kBlock, kTopNodes,
-                                     kMaxLdsBudget, &r1) == PT_OK && r1.nested) {
-        T.have_oct = false; T.num_nodes = N - 1; T.root_ref = 0; T.stack_cap = r1.stack_need + 1; T.top_avail = r1.top_avail; T.depth = r1.depth;
-        return true;
-    }
-    (void)hipGetLastError();
-    T.nodes.release();
-    return false;
-}
-
-// The same tree by the host builder (pt_tree_sweep.h), in internal form.  built(): called once the builder has run.
-template <class Built>
-bool internal_tree_host(const std::vector<float>& leaf_boxes, int N, TreeHost& fast, Built built) {
-    for (size_t k = 0; k < leaf_boxes.size(); k++)
-        if (!std::isfinite(leaf_boxes[k])) return false;
-    std::vector<pt_bvh_node> fnodes;
-    int32_t froot = 0, fdepth = 0;
-    bool ok = true;
-    try {
-        pts::build_sweep_tree(leaf_boxes.data(), N, fnodes, &froot, &fdepth);
-    } catch (const std::exception&) {        // out of host memory: the caller's tree serves alone
-        ok = false;
-    }
-    built();
-    bool fnested = true;
-    return ok && convert_tree(fnodes.data(), (int)fnodes.size(), froot, N, fast, nullptr, &fnested, true) == PT_OK && fnested;
-}
-
-// Inner visits of the probe rays (pt_kernels.h: probe_kernel) through the trees d0 and d1 point at, into v[0] and v[1].
+// Inner visits of the probe rays (pt_kernels.h: probe_kernel) through the trees d0 and d1 point at, into v[0] and v[1] (pt_scene.h).
 int probe_trees(const SceneDev& d0, const SceneDev& d1, unsigned long long v[2]) {
     DevBuf<unsigned long long> visits;
-    int rc;
-    if ((rc = visits.ensure(2))) return rc;
+    if (int rc = visits.ensure(2)) return rc;
     HIP_TRY(hipMemset(visits.p, 0, 2 * sizeof(unsigned long long)));
     const uint32_t lds = (uint32_t)(kBlock / 64) * (uint32_t)std::max(d0.stack_cap, d1.stack_cap) * 64u * 4u;
     hipLaunchKernelGGL(probe_kernel, dim3(kProbeRays / kBlock, 2), dim3(kBlock), lds, nullptr, d0, d1, visits.p);
@@ -664,297 +64,17 @@ int probe_trees(const SceneDev& d0, const SceneDev& d1, unsigned long long v[2])
     HIP_TRY(hipMemcpy(v, visits.p, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     return PT_OK;
 }
-int64_t probe_permille(const unsigned long long v[2]) { return v[0] ? (int64_t)((1000ull * v[1] + v[0] / 2) / v[0]) : 1000; }
-bool probe_wins(const unsigned long long v[2]) { return v[1] * 100ull < v[0] * 90ull; }   // at least 10 % fewer boxes
 
-// The leaf sweep's groups of equal leaf boxes (pt_leaf_sweep.h) and its tables (pt_sweep_layout.h) from an internal tree as the
-// host built it; prims: the N <= kSweepMaxPrims records on the host.  groups = 0: none; sweep.count stays 0 where a launch
-// would not admit them.
-int make_sweep_tables(const TreeHost& fast, const DPrim* prims, int N, SweepTable& sweep, int& sweep_groups, DevBuf<unsigned char>& sweep_tab) {
-    sweep = SweepTable{};
-    sweep_groups = 0;
-    SweepGroup groups[kSweepMaxPrims];
-    const int n = build_sweep_groups(fast.nodes.data(), (int)fast.nodes.size(), N, kLdsNodeStride, groups);
-    if (n > 0) {
-        sweep_groups = n;
-        std::vector<unsigned char> tab(n <= kSweepMaxBoxes ? sweep_layout_bytes((uint32_t)n, (uint32_t)N) : 0);
-        if (n <= kSweepMaxBoxes && build_sweep_layout(groups, n, fast.nodes.data(), (int)fast.nodes.size(), kLdsNodeStride, prims, N, tab.data())) {
-            int rc;
-            if ((rc = sweep_tab.ensure(tab.size()))) return rc;
-            HIP_TRY(hipMemcpy(sweep_tab.p, tab.data(), tab.size(), hipMemcpyHostToDevice));
-            sweep.count = (uint32_t)n;
-            std::copy(groups, groups + n, sweep.g);
-        }
-    }
-    return PT_OK;
-}
+namespace {
 
-int validate_and_build(const pt_scene_desc* d, pt_scene* S) {
-    if (!d) return fail(PT_ERR_INVALID_ARG, "null scene description");
-    if (d->num_shapes <= 0 || !d->shapes) return fail(PT_ERR_BAD_SCENE, "scene has no shapes");
-    if (d->num_nodes != 2 * d->num_shapes - 1 || !d->nodes)
-        return fail(PT_ERR_BAD_SCENE, "BVH must have 2*num_shapes-1 nodes (bvh.cu:16-54)");
-    if (d->root < 0 || d->root >= d->num_nodes) return fail(PT_ERR_BAD_SCENE, "BVH root out of range");
-    if (d->num_materials <= 0 || !d->materials) return fail(PT_ERR_BAD_SCENE, "scene has no materials");
-    if (d->num_meshes < 0 || (d->num_meshes > 0 && !d->meshes)) return fail(PT_ERR_BAD_SCENE, "bad mesh array");
-    if (d->num_lights < 0 || (d->num_lights > 0 && !d->lights)) return fail(PT_ERR_BAD_SCENE, "bad light array");
-    int crc;
-    if ((crc = check_materials(d)) || (crc = check_meshes(d, d->num_materials))) return crc;
+constexpr uint64_t kDefaultScratchBytes = 8ull << 30;   // per-sample scratch cap (3 % of the 288 GB of HBM): every sample pass
+                                                        // pays the launch floor once (buddha stand-in 135.6 ms in 5 passes, 130.6 in 1)
+#ifndef PT_TOP_LDS_KB
+#define PT_TOP_LDS_KB 26
+#endif
+constexpr uint32_t kTopLdsBudget = PT_TOP_LDS_KB * 1024;    // LDS per block that keeps 6 blocks per CU resident (160 KB / 6)
 
-    // ---- primitives
-    using clk = std::chrono::steady_clock;
-    auto us_since = [](clk::time_point t0) { return (int64_t)std::chrono::duration_cast<std::chrono::microseconds>(clk::now() - t0).count(); };
-    const clk::time_point t_all = clk::now();
-    clk::time_point t_stage = t_all;
-    const int N = d->num_shapes;
-    const bool on_device = N >= kDeviceSweepMin && !host_sweep_forced();     // big scenes are prepared on the device (see below)
-    std::vector<DPrim> prims(on_device ? 0 : N);
-    std::vector<DNormals> normals(on_device ? 0 : N);
-    S->tri_only = true;
-    if (on_device) {
-        int prc, has_sphere = 0;
-        if ((prc = S->prims.ensure((size_t)N)) || (prc = S->normals.ensure((size_t)N))) return prc;
-        if ((prc = ptp::prims_device(d, S->prims.p, S->normals.p, &has_sphere))) return prc;
-        S->tri_only = !has_sphere;
-    } else {
-    std::memset(prims.data(), 0, sizeof(DPrim) * N);
-    std::memset(normals.data(), 0, sizeof(DNormals) * N);
-    for (int i = 0; i < N; i++) {
-        const pt_shape& s = d->shapes[i];
-        DPrim& p = prims[i];
-        if (s.type == PT_SHAPE_SPHERE) {
-            if (s.material_id < 0 || s.material_id >= d->num_materials) return fail(PT_ERR_BAD_SCENE, "sphere material id out of range");
-            p.v[0] = s.center[0]; p.v[1] = s.center[1]; p.v[2] = s.center[2]; p.v[3] = s.radius;
-            p.info = (int32_t)(0x80000000u | (uint32_t)s.material_id);
-            p.light = s.area_light_id;
-            S->tri_only = false;
-        } else if (s.type == PT_SHAPE_TRIANGLE) {
-            if (s.mesh_index < 0 || s.mesh_index >= d->num_meshes) return fail(PT_ERR_BAD_SCENE, "triangle mesh index out of range");
-            const pt_mesh& me = d->meshes[s.mesh_index];
-            if (s.face_index < 0 || s.face_index >= me.num_faces) return fail(PT_ERR_BAD_SCENE, "triangle face index out of range");
-            const int32_t* idx = me.indices + 3 * (size_t)s.face_index;
-            for (int k = 0; k < 3; k++) {
-                if (idx[k] < 0 || idx[k] >= me.num_vertices) return fail(PT_ERR_BAD_SCENE, "vertex index out of range");
-                for (int c = 0; c < 3; c++) {
-                    p.v[3 * k + c] = me.positions[3 * (size_t)idx[k] + c];
-                    normals[i].n[3 * k + c] = me.normals[3 * (size_t)idx[k] + c];
-                }
-            }
-            p.info = me.material_id;
-            p.light = me.area_light_id;
-        } else {
-            return fail(PT_ERR_BAD_SCENE, "unknown shape type");
-        }
-    }
-    }
-
-    S->diffuse_only = all_diffuse(d);
-
-    S->create_us[1] = us_since(t_stage); t_stage = clk::now();
-    // ---- BVH: the caller's tree (validated), and the internal tree over the same leaf boxes
-    // From kDeviceSweepMin primitives up all of it happens on the device (pt_scene_prep.hip, pt_sweep_build.hip): the caller's
-    // pool goes up once, is checked and re-laid there, its leaf boxes feed the sweep builder, the builder's pool is re-laid in
-    // turn — nothing of either tree comes back to the host.  The host code below serves small scenes, PT_SWEEP_BUILD=host, and
-    // whatever the device path hands back (input that runs into the sweep builder's depth guard).
-    TreeHost ref;
-    TreeHost fast;
-    bool have_fast = false;
-    bool trees_on_device = false;              // tree[0] (and tree[1] when have_fast) already sit in S->tree[]
-    int ref_depth = 0;
-    size_t ref_inner = 0;
-    DevBuf<pt_bvh_node> pool_dev;              // the caller's pool and the map pool index -> DNode index (tie tables)
-    DevBuf<int32_t> iop_dev;
-    S->sweep_on_device = 0;
-    if (on_device) {
-        DevBuf<float> boxes_dev;
-        ptp::RelayResult r0;
-        int prc;
-        if ((prc = pool_dev.ensure((size_t)d->num_nodes)) || (prc = iop_dev.ensure((size_t)d->num_nodes)) || (prc = boxes_dev.ensure((size_t)N * 6)) ||
-            (prc = S->tree[0].nodes.ensure((size_t)N - 1)))
-            return prc;
-        HIP_TRY(hipMemcpy(pool_dev.p, d->nodes, (size_t)d->num_nodes * sizeof(pt_bvh_node), hipMemcpyHostToDevice));
-        prc = ptp::relay_tree_device(pool_dev.p, d->num_nodes, d->root, N, false, S->tree[0].nodes.p, iop_dev.p, boxes_dev.p, kBlock, kTopNodes,
-                                     kMaxLdsBudget, &r0);
-        if (prc) return prc;                   // PT_ERR_BAD_SCENE with the host path's messages
-        {
-            pt_scene::Tree& T0 = S->tree[0];
-            T0.have_oct = false; T0.num_nodes = N - 1; T0.root_ref = 0; T0.stack_cap = r0.stack_need + 1; T0.top_avail = r0.top_avail; T0.depth = r0.depth;
-        }
-        ref_depth = r0.depth;
-        ref_inner = (size_t)N - 1;
-        trees_on_device = true;
-        S->create_us[2] = us_since(t_stage); t_stage = clk::now();
-        if (r0.nested) {
-            // (why a tree of the library's own may stand in for a nested caller's tree: see the host path below)
-            if (internal_tree_device(boxes_dev.p, N, S->tree[1], [&] { S->create_us[3] = us_since(t_stage); t_stage = clk::now(); })) {
-                have_fast = true;
-                S->sweep_on_device = 1;
-            } else {
-                // the device builder handed the input back (depth guard) or failed: the host builder, from the leaf boxes
-                std::vector<float> leaf_boxes((size_t)N * 6);
-                have_fast = hipMemcpy(leaf_boxes.data(), boxes_dev.p, leaf_boxes.size() * sizeof(float), hipMemcpyDeviceToHost) == hipSuccess &&
-                            internal_tree_host(leaf_boxes, N, fast, [] {});
-            }
-            if (!have_fast) S->no_fast_why = "the internal tree could not be built";
-        } else {
-            S->no_fast_why = "the caller's boxes do not nest";
-        }
-    } else {
-        std::vector<float> leaf_boxes((size_t)N * 6);
-        bool nested = true;
-        int trc = convert_tree(d->nodes, d->num_nodes, d->root, N, ref, leaf_boxes.data(), &nested);
-        if (trc) return trc;
-        ref_depth = ref.depth;
-        ref_inner = ref.nodes.size();
-        S->create_us[2] = us_since(t_stage); t_stage = clk::now();
-        if (N >= kMinInternalTree && nested) {
-            // A leaf is tested by the reference iff the ray hits every box on its way down (scene.h:278-297, no pruning).  The slab
-            // test is monotone in the box (rounding is), so where every box contains its children's that is: iff it hits the LEAF's
-            // own box — whatever the tree above it.  `nested` says the caller's tree is of that kind; then any tree over the same
-            // leaf boxes tests the same leaves, and only the ORDER of the tests (ties on t, scene.h:270) still depends on the tree.
-            // The tree: all cuts along x, y and z at every node (pt_tree_sweep.h), as deep as it likes — traversed left child
-            // first, its stack need is its Strahler number, not its depth (convert_tree).
-            have_fast = internal_tree_host(leaf_boxes, N, fast, [&] { S->create_us[3] = us_since(t_stage); t_stage = clk::now(); });
-            if (!have_fast) S->no_fast_why = "the internal tree could not be built";
-        } else {
-            S->no_fast_why = N < kMinInternalTree ? "fewer than 16 shapes" : "the caller's boxes do not nest";
-        }
-    }
-    S->create_us[4] = us_since(t_stage); t_stage = clk::now();
-    // trees the device path made are in S->tree[] already; what the host made is uploaded below
-    const TreeHost* hosts[2] = {trees_on_device ? nullptr : &ref, (have_fast && !S->sweep_on_device) ? &fast : nullptr};
-    std::vector<DMaterial> mats;
-    std::vector<DEmission> emis;
-    std::vector<DLight> dlights;
-    int rc;
-    if ((rc = pack_shading(d, N, mats, emis, dlights))) return rc;
-    for (int t = 0; t < 2; t++)
-        if (hosts[t] && (rc = upload_tree(S->tree[t], *hosts[t]))) return rc;
-    S->have_fast = have_fast;
-    if (!on_device && ((rc = S->prims.ensure(prims.size())) || (rc = S->normals.ensure(normals.size())))) return rc;
-    if ((rc = S->materials.ensure(mats.size()))) return rc;
-    if ((rc = S->emission.ensure(emis.size()))) return rc;
-    if ((rc = S->lights.ensure(dlights.size()))) return rc;
-    HIP_TRY(hipMemcpy(S->lights.p, dlights.data(), dlights.size() * sizeof(DLight), hipMemcpyHostToDevice));
-    if (!on_device) {
-        HIP_TRY(hipMemcpy(S->prims.p, prims.data(), prims.size() * sizeof(DPrim), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(S->normals.p, normals.data(), normals.size() * sizeof(DNormals), hipMemcpyHostToDevice));
-    }
-    HIP_TRY(hipMemcpy(S->materials.p, mats.data(), mats.size() * sizeof(DMaterial), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(S->emission.p, emis.data(), emis.size() * sizeof(DEmission), hipMemcpyHostToDevice));
-
-    SceneDev& dv = S->dev;
-    dv.prims = S->prims.p; dv.normals = S->normals.p;
-    dv.materials = S->materials.p; dv.emission = S->emission.p; dv.lights = S->lights.p;
-    dv.num_prims = N;
-    dv.num_materials = d->num_materials;
-    dv.num_emission = d->num_lights;
-    dv.bg[0] = d->background[0]; dv.bg[1] = d->background[1]; dv.bg[2] = d->background[2];
-    // Keep the internal tree only where it is the better one FOR THIS KIND OF RAY: without pruning a node is visited iff the
-    // ray hits its box, and what the boxes of a tree add up to depends on the scene (a soup of large overlapping triangles is
-    // better off with the caller's median splits than with cuts of the Morton order; a far-away ground sphere skews any
-    // surface-area estimate).  So measure: the same probe rays — from random points on the primitives into uniform
-    // directions, which is where and how the segments after the first bounce start — through both trees, inner visits counted.
-    S->fast_cost_permille = 0;
-    if (have_fast) {
-        select_tree(S, 0);
-        const SceneDev d0 = S->dev;
-        select_tree(S, 1);
-        const SceneDev d1 = S->dev;
-        unsigned long long v[2] = {0, 0};
-        if ((rc = probe_trees(d0, d1, v))) return rc;
-        S->fast_cost_permille = probe_permille(v);
-        if (!probe_wins(v)) {                               // not at least 10 % fewer boxes: the sweep tree is not worth having
-            S->have_fast = false;
-            S->no_fast_why = "the sweep tree lost the probe on an LDS-resident scene";
-            S->tree[1].nodes.release();
-            S->tree[1].nodes_oct.release();
-            S->tree[1].have_oct = false;
-            // ... but the way the internal tree is TRAVERSED still is, for scenes in global memory: left child first with the
-            // children ordered for a short stack, leaves set aside, ties settled in place.  So the caller's own topology becomes the
-            // internal tree (a caller who hands in a tree as good as the sweep tree: 5.43 -> 4.9 ms on bunny,
-            // profiles/r02_device_bvh_build.log).
-            const bool global_scene = (size_t)N * (sizeof(DPrim) + sizeof(DNormals)) + ref_inner * sizeof(DNode) > kLdsSceneLimit;
-            if (global_scene) {
-                TreeHost own;
-                bool own_nested = true;
-                if (convert_tree(d->nodes, d->num_nodes, d->root, N, own, nullptr, &own_nested, true) == PT_OK && own_nested) {
-                    if ((rc = upload_tree(S->tree[1], own))) return rc;
-                    S->have_fast = true;
-                    S->fast_is_callers_topology = true;
-                }
-            }
-        }
-    }
-    S->create_us[5] = us_since(t_stage); t_stage = clk::now();
-    if (S->have_fast) {
-        // what settles ties on t in the caller's visit order: every primitive's path from the caller's root (turn bits) and
-        // the inner nodes along it.  (Depth <= 64 levels of leaves and inner nodes: at most 63 turns.)
-        const int levels = std::max(ref_depth - 1, 1);
-        const size_t anc_words = (size_t)N * (size_t)levels;
-        if (S->ref_path.ensure((size_t)N) || S->ref_anc.ensure(anc_words)) {
-            // no room for the tables (num_shapes x depth words): the scene simply keeps to the caller's tree
-            (void)hipGetLastError();
-            S->have_fast = false;
-            S->no_fast_why = "there was no room for the tie tables";
-            S->fast_is_callers_topology = false;
-            S->ref_path.release(); S->ref_anc.release();
-            S->tree[1].nodes.release(); S->tree[1].nodes_oct.release(); S->tree[1].have_oct = false;
-        } else {
-            bool made = false;
-            if (trees_on_device) {
-                // on the device: every leaf of the caller's pool (uploaded above) walks to the root (pt_scene_prep.hip) — a
-                // depth-first walk over a million leaves writing a 100 MB table is 150 ms of host time, and the table would
-                // have to be uploaded
-                DevBuf<int32_t> parent_dev;
-                if (!parent_dev.ensure((size_t)d->num_nodes) && hipMemset(S->ref_anc.p, 0, anc_words * sizeof(int32_t)) == hipSuccess)
-                    made = ptp::tie_tables_device(pool_dev.p, d->num_nodes, d->root, iop_dev.p, N, levels, parent_dev.p, S->ref_path.p, S->ref_anc.p) == PT_OK;
-                if (!made) return fail(PT_ERR_DEVICE, "tie tables on the device failed");
-            }
-            if (!made) {
-                std::vector<unsigned long long> path(N, 0ull);
-                std::vector<int32_t> anc(anc_words, 0);
-                struct Walk { int32_t node; int32_t level; unsigned long long turns; };
-                std::vector<Walk> todo;
-                std::vector<int32_t> trail(levels, 0);
-                todo.push_back({d->root, 0, 0ull});
-                while (!todo.empty()) {
-                    const Walk w = todo.back();
-                    todo.pop_back();
-                    const pt_bvh_node& nd = d->nodes[w.node];
-                    if (nd.prim != -1) {
-                        path[nd.prim] = w.turns;
-                        std::memcpy(&anc[(size_t)nd.prim * levels], trail.data(), (size_t)w.level * sizeof(int32_t));
-                        continue;
-                    }
-                    trail[w.level] = ref.inner_of_pool[w.node];
-                    // depth-first, left subtree first: `trail` below w.level is still this node's path when its right child is taken up
-                    todo.push_back({nd.right, w.level + 1, w.turns | (1ull << w.level)});
-                    todo.push_back({nd.left, w.level + 1, w.turns});
-                }
-                HIP_TRY(hipMemcpy(S->ref_path.p, path.data(), path.size() * sizeof(unsigned long long), hipMemcpyHostToDevice));
-                HIP_TRY(hipMemcpy(S->ref_anc.p, anc.data(), anc.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-            }
-            S->ref_levels = levels;
-        }
-    }
-    // the leaf sweep's groups of equal leaf boxes (pt_leaf_sweep.h), from the internal tree as the host built it
-    S->sweep = SweepTable{};
-    S->sweep_groups = 0;
-    if (S->have_fast && hosts[1] && !S->fast_is_callers_topology && N <= kSweepMaxPrims &&
-        (rc = make_sweep_tables(fast, prims.data(), N, S->sweep, S->sweep_groups, S->sweep_tab)))
-        return rc;
-    // everything the scene holds is complete from here on: trace kernels run on streams of the handle's own (FrameSlot) that do
-    // not synchronise with the stream the preparation kernels ran on
-    HIP_TRY(hipDeviceSynchronize());
-    S->create_us[6] = us_since(t_stage);
-    S->create_us[0] = us_since(t_all);
-    select_tree(S, 0);
-    S->scene_bytes = (uint32_t)std::min<size_t>(
-        ref_inner * sizeof(DNode) + (size_t)N * (sizeof(DPrim) + sizeof(DNormals)) + mats.size() * sizeof(DMaterial) +
-            emis.size() * sizeof(DEmission) + 64, 0xffffffffu);
-    return PT_OK;
-}
+uint32_t align16(uint32_t v) { return (v + 15u) & ~15u; }
 
 // The tree a render traverses: the internal tree on the default kernel where scene creation kept one (see launch_render), the
 // caller's tree otherwise.  Pruned traversal (opt-in, tolerance semantics: DESIGN.md §6) takes the internal tree as well — left
@@ -1548,8 +668,7 @@ int launch_render(pt_scene* S, const pt_render_params* p, float* out_dev, int mo
     RowSel rows;
     int rc = check_render_args(S, p, out_dev, pl, &rows);
     if (rc) return rc;
-    DeviceGuard guard;
-    { int grc = guard.enter(S->device); if (grc) return grc; }
+    ENTER_DEVICE(S);
     const bool cont = ad && ad->round > 0;
     OpenFrame f;
     if ((rc = open_frame(S, stream, cont, &f))) return rc;
@@ -1652,7 +771,7 @@ int launch_render(pt_scene* S, const pt_render_params* p, float* out_dev, int mo
 // The frame's counters, summed over the counter slots, once its stream has drained; zeros where the handle has no control block
 // yet.  Enters the handle's device under the caller's guard.
 int synced_slot_sums(pt_scene* S, DeviceGuard& guard, unsigned long long* c) {
-    { int grc = guard.enter(S->device); if (grc) return grc; }
+    if (int grc = guard.enter(S->device)) return grc;
     HIP_TRY(hipStreamSynchronize(S->last_stream));
     std::fill(c, c + kSlotStride, 0ull);
     return S->cur().ctl.p ? read_slot_sums(S, c) : PT_OK;
@@ -1684,323 +803,6 @@ int frame_times(const pt_scene::FrameRec& f, double* kernel_ms, double* resolve_
     }
     *kernel_ms = t;
     *resolve_ms = r;
-    return PT_OK;
-}
-
-
-// The staging buffers of a geometry change: new records and vertex normals, the buffer the live records retire into, the status word.
-int ensure_staging(pt_scene* S) {
-    const size_t N = (size_t)S->dev.num_prims;
-    int rc;
-    if ((rc = S->st_prims.ensure(N)) || (rc = S->prev_prims.ensure(N)) || (rc = S->st_normals.ensure(N)) || (rc = S->st_status.ensure(1)))
-        return rc;
-    return PT_OK;
-}
-
-// ---- tree-cost telemetry (pt_tree_cost.hip) ---------------------------------------------------------------------------------
-int ensure_cost(pt_scene* S) {
-    int rc;
-    const size_t need = std::max(ptc::partials_needed(S->tree[0].num_nodes), ptc::partials_needed(S->tree[1].num_nodes));
-    if ((rc = S->cost_partials.ensure(need)) || (rc = S->cost_dev.ensure(4))) return rc;
-    if (!S->cost_host) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&S->cost_host), 4 * sizeof(double), hipHostMallocDefault));
-    return PT_OK;
-}
-// T's cost into cost_dev[slot] and from there to cost_host[slot], all on the default stream; read once that has synchronised
-int enqueue_cost(pt_scene* S, const pt_scene::Tree& T, int slot) {
-    int rc;
-    if ((rc = ptc::tree_cost(T.nodes.p, T.num_nodes, S->cost_partials.p, S->cost_dev.p + slot))) return rc;
-    HIP_TRY(hipMemcpyAsync(S->cost_host + slot, S->cost_dev.p + slot, sizeof(double), hipMemcpyDeviceToHost, nullptr));
-    return PT_OK;
-}
-// after the synchronise that closes the call: what adopt_staged enqueued
-void collect_costs(pt_scene* S) {
-    for (int t = 0; t < 2; t++) {
-        if (S->cost_pending_ref[t]) { S->cost_ref[t] = S->cost_host[t]; S->cost_have_ref[t] = true; }
-        if (S->cost_pending_now[t]) S->cost_now[t] = S->cost_host[2 + t];
-        S->cost_pending_ref[t] = S->cost_pending_now[t] = false;
-    }
-}
-int64_t cost_permille(const pt_scene* S, int t) {
-    if (!S->cost_have_ref[t] || !(S->cost_ref[t] > 0.0) || !(S->cost_now[t] > 0.0)) return 1000;
-    return (int64_t)(1000.0 * S->cost_now[t] / S->cost_ref[t] + 0.5);
-}
-
-// What pt_scene_update and pt_scene_transform do once new records stand in st_prims / st_normals: the refit plans where none
-// exist yet, leaf boxes and the status read-back, both trees refitted, and only then the handle changes — the three record
-// buffers rotate (staging -> current -> previous) and the box sweep is dropped.  `who` heads the messages.  *us_plan: wall
-// microseconds of the plan build (left alone where none was due); *us_refit: of everything after it.
-int adopt_staged(pt_scene* S, const char* who, bool tri_only, int64_t* us_plan, int64_t* us_refit) {
-    using clk = std::chrono::steady_clock;
-    auto us_since = [](clk::time_point t0) { return (int64_t)std::chrono::duration_cast<std::chrono::microseconds>(clk::now() - t0).count(); };
-    const int N = S->dev.num_prims;
-    int rc;
-    clk::time_point t_stage = clk::now();
-    const int n_trees = N > 1 ? (S->have_fast ? 2 : 1) : 0;   // one shape: a dummy node, the root is never box-tested
-    bool whole = true, planned = false;
-    for (int t = 0; t < n_trees; t++) {
-        ptf::Plan& pl = S->refit_plan[t];
-        if (!pl.built) {
-            if ((rc = ptf::plan_build(S->tree[t].nodes.p, S->tree[t].num_nodes, N, &pl))) return rc;
-            planned = true;
-        }
-        whole = whole && pl.whole_tree;
-        // octant tables are made by the single-workgroup launch alone; they exist only for trees far smaller than its reach
-        if (S->tree[t].have_oct && !pl.whole_tree) return fail(PT_ERR_UNSUPPORTED, std::string(who) + ": octant tables on a tree of wide levels");
-    }
-    if (planned) { *us_plan = std::max<int64_t>(us_since(t_stage), 1); t_stage = clk::now(); }
-    const bool costs = S->cost_on() && n_trees > 0;
-    for (int t = 0; t < 2; t++) S->cost_pending_ref[t] = S->cost_pending_now[t] = false;
-    if (costs) {
-        // the reference cost of a tree that has none yet: from the boxes as they stand, before this refit writes them
-        if ((rc = ensure_cost(S))) return rc;
-        for (int t = 0; t < n_trees; t++)
-            if (!S->cost_have_ref[t]) {
-                if ((rc = enqueue_cost(S, S->tree[t], t))) return rc;
-                S->cost_pending_ref[t] = true;
-            }
-    }
-    HIP_TRY(hipMemsetAsync(S->st_status.p, 0, sizeof(unsigned int), nullptr));
-    unsigned int bad = 0;
-    if (!whole || n_trees == 0) {
-        // the leaf boxes, checked before any node array is written (a tree done by one launch checks for itself)
-        if ((rc = S->st_boxes.ensure((size_t)N * 6)) || (rc = ptf::leaf_boxes(S->st_prims.p, N, S->st_boxes.p, S->st_status.p))) return rc;
-        HIP_TRY(hipMemcpy(&bad, S->st_status.p, sizeof bad, hipMemcpyDeviceToHost));
-    }
-    for (int t = 0; t < n_trees && !bad; t++) {
-        pt_scene::Tree& T = S->tree[t];
-        if ((rc = ptf::refit_tree(S->refit_plan[t], T.nodes.p, T.have_oct ? T.nodes_oct.p : nullptr, T.num_nodes, S->st_prims.p,
-                                  whole ? nullptr : S->st_boxes.p, N, S->st_status.p)))
-            return rc;
-    }
-    if (whole && n_trees) HIP_TRY(hipMemcpy(&bad, S->st_status.p, sizeof bad, hipMemcpyDeviceToHost));
-    if (bad) return fail(PT_ERR_UNSUPPORTED, std::string(who) + ": a new coordinate, radius or leaf box is not finite");
-    // behind the refit on its stream; the caller reads it after the synchronise that closes the call (collect_costs).  The
-    // trees are written: a launch that fails here costs the measurement, not the update.
-    for (int t = 0; costs && t < n_trees; t++) S->cost_pending_now[t] = enqueue_cost(S, S->tree[t], 2 + t) == PT_OK;
-    std::swap(S->prev_prims.p, S->st_prims.p); std::swap(S->prev_prims.n, S->st_prims.n);   // the new records, for a moment
-    std::swap(S->prims.p, S->prev_prims.p); std::swap(S->prims.n, S->prev_prims.n);         // current -> previous, new -> current
-    S->have_prev = true;
-    std::swap(S->normals.p, S->st_normals.p); std::swap(S->normals.n, S->st_normals.n);
-    S->dev.prims = S->prims.p; S->dev.normals = S->normals.p;
-    S->tri_only = tri_only;
-    S->sweep_groups = 0; S->sweep.count = 0;     // leaf boxes that were equal need not be any more: back to the tree
-    S->sweep_tab.release();                      // (no frame is in flight: the update synchronised before it wrote)
-    *us_refit = us_since(t_stage);
-    return PT_OK;
-}
-
-// pt_scene_rebuild (include/pt_api.h) between the two synchronises: the caller has made the device current and quiet, and
-// synchronises again before a frame may start.  Everything is made in buffers of its own — leaf boxes out of tree[0], the
-// candidate by pt_scene_create's internal-tree stage, its refit plan, its sweep tables — and only then does the handle change,
-// by steps that cannot fail.  tree[0], the tie tables and every record set are read, never written.
-int rebuild_scene(pt_scene* S) {
-    using clk = std::chrono::steady_clock;
-    auto us_since = [](clk::time_point t0) { return (int64_t)std::chrono::duration_cast<std::chrono::microseconds>(clk::now() - t0).count(); };
-    if (!S->have_fast)
-        return fail(PT_ERR_UNSUPPORTED, std::string("pt_scene_rebuild: the handle holds no tie tables, pt_scene_create kept no internal tree: ") +
-                                            (S->no_fast_why[0] ? S->no_fast_why : "none was built"));
-    const int N = S->dev.num_prims;
-    const pt_scene::Tree& T0 = S->tree[0];
-    const clk::time_point t_all = clk::now();
-    clk::time_point t_stage = t_all;
-    int64_t us[4] = {0, 0, 0, 0};
-    int rc;
-    // ---- leaf boxes: what the caller's tree holds (the caller's own before a geometry update, the exact ones after)
-    DevBuf<float> boxes_dev;
-    if ((rc = boxes_dev.ensure((size_t)N * 6)) || (rc = ptf::tree_leaf_boxes(T0.nodes.p, T0.num_nodes, N, boxes_dev.p))) return rc;
-    // ---- build: create's branches
-    pt_scene::Tree cand;
-    TreeHost fast;
-    auto built = [&] { us[1] = us_since(t_stage); t_stage = clk::now(); };
-    bool on_device = N >= kDeviceSweepMin && !host_sweep_forced() && internal_tree_device(boxes_dev.p, N, cand, built);
-    if (!on_device) {
-        std::vector<float> leaf_boxes((size_t)N * 6);
-        HIP_TRY(hipMemcpy(leaf_boxes.data(), boxes_dev.p, leaf_boxes.size() * sizeof(float), hipMemcpyDeviceToHost));
-        t_stage = t_all;                              // stage 1 runs from the start of the call, whichever builder ends it
-        if (!internal_tree_host(leaf_boxes, N, fast, built))
-            return fail(PT_ERR_UNSUPPORTED, "pt_scene_rebuild: no internal tree could be built of the leaf boxes (not finite, or they no longer nest)");
-        if ((rc = upload_tree(cand, fast))) return rc;
-    }
-    boxes_dev.release();
-    // ---- probe: create's rays and create's rule, the caller's tree as it stands against the candidate.  (As at create: no tie
-    // tables in view, the probe counts box tests.)
-    SceneDev d0 = S->dev, d1 = S->dev;
-    tree_view(S, d0, 0, false);
-    tree_view(S, d1, cand, 1, false);
-    for (SceneDev* dv : {&d0, &d1}) { dv->ref_path = nullptr; dv->ref_anc = nullptr; dv->ref_levels = 0; dv->redo_stack = nullptr; }
-    unsigned long long v[2] = {0, 0};
-    if ((rc = probe_trees(d0, d1, v))) return rc;
-    const bool adopt = probe_wins(v);
-    us[2] = us_since(t_stage); t_stage = clk::now();
-    // ---- what goes with an adopted tree: its refit plan where the handle has refitted before (the next update does not pay for
-    // it), the box sweep of a small scene under create's admission rules, its cost where telemetry is on
-    ptf::Plan plan;
-    SweepTable sweep{};
-    int sweep_groups = 0;
-    DevBuf<unsigned char> sweep_tab;
-    double cost = 0.0;
-    if (adopt) {
-        if (S->refit_plan[1].built && (rc = ptf::plan_build(cand.nodes.p, cand.num_nodes, N, &plan))) return rc;
-        struct PlanGuard { ptf::Plan* p; ~PlanGuard() { if (p) ptf::plan_release(p); } } plan_guard{&plan};
-        if (!on_device && N <= kSweepMaxPrims) {
-            std::vector<DPrim> prims((size_t)N);
-            HIP_TRY(hipMemcpy(prims.data(), S->prims.p, prims.size() * sizeof(DPrim), hipMemcpyDeviceToHost));
-            if ((rc = make_sweep_tables(fast, prims.data(), N, sweep, sweep_groups, sweep_tab))) return rc;
-        }
-        if (S->cost_on()) {
-            if ((rc = ensure_cost(S)) || (rc = enqueue_cost(S, cand, 3))) return rc;
-            HIP_TRY(hipStreamSynchronize(nullptr));
-            cost = S->cost_host[3];
-        }
-        // ---- adoption
-        pt_scene::Tree& T1 = S->tree[1];
-        std::swap(T1.nodes.p, cand.nodes.p); std::swap(T1.nodes.n, cand.nodes.n);
-        std::swap(T1.nodes_oct.p, cand.nodes_oct.p); std::swap(T1.nodes_oct.n, cand.nodes_oct.n);
-        T1.have_oct = cand.have_oct; T1.num_nodes = cand.num_nodes; T1.root_ref = cand.root_ref; T1.stack_cap = cand.stack_cap;
-        T1.top_avail = cand.top_avail; T1.depth = cand.depth;
-        S->have_fast = true;
-        S->fast_is_callers_topology = false;
-        S->fast_cost_permille = probe_permille(v);
-        S->sweep_on_device = on_device ? 1 : 0;
-        std::swap(S->refit_plan[1], plan);            // the old plan goes with the old tree, once the call is timed
-        plan_guard.p = &plan;
-        S->sweep = sweep;
-        S->sweep_groups = sweep_groups;
-        std::swap(S->sweep_tab.p, sweep_tab.p); std::swap(S->sweep_tab.n, sweep_tab.n);
-        S->cfg_fn = nullptr;                          // stack and LDS needs follow the tree: the next launch asks again
-        S->q_cfg_fn = nullptr;
-        if (S->cost_on()) { S->cost_ref[1] = S->cost_now[1] = cost; S->cost_have_ref[1] = true; }
-    } else if (S->cost_have_ref[1] && S->cost_now[1] > 0.0) {
-        S->cost_ref[1] = S->cost_now[1];              // no better tree to be had of these boxes: a policy waits for the next drift
-    }
-    us[3] = us_since(t_stage);
-    us[0] = us_since(t_all);
-    select_tree(S, 0);
-    S->rebuilds++;
-    S->rebuild_adopted = adopt ? 1 : 0;
-    S->rebuild_cost_permille = probe_permille(v);
-    std::copy(us, us + 4, S->rebuild_us);
-    return PT_OK;
-}
-
-// The policy of option rebuild_at_permille, inside a geometry update or transform that has refitted: the internal tree's cost
-// is awaited and compared, and the rebuild runs before the call's closing synchronise.  A rebuild that fails leaves the refitted
-// tree in place and does not fail the call.
-void rebuild_by_policy(pt_scene* S) {
-    if (S->opt_rebuild_at <= 0 || !S->have_fast || !S->cost_pending_now[1]) return;
-    if (hipStreamSynchronize(nullptr) != hipSuccess) return;
-    collect_costs(S);
-    if (cost_permille(S, 1) < S->opt_rebuild_at) return;
-    if (rebuild_scene(S) == PT_OK) S->rebuilds_auto++;
-}
-
-// pt_scene_update (include/pt_api.h).  Order of events: everything that can be refused is made and checked first — argument
-// counts and the desc on the host, primitive records and leaf boxes in staging memory on the device — and only then does the
-// handle change: node arrays written, record buffers traded, shading tables overwritten.
-int update_scene(pt_scene* S, const pt_scene_desc* d, int flags) {
-    using clk = std::chrono::steady_clock;
-    auto us_since = [](clk::time_point t0) { return (int64_t)std::chrono::duration_cast<std::chrono::microseconds>(clk::now() - t0).count(); };
-    const bool geometry = (flags & PT_UPDATE_GEOMETRY) != 0, shading = (flags & PT_UPDATE_SHADING) != 0;
-    const int N = S->dev.num_prims;
-    if (geometry && d->num_shapes != N) return fail(PT_ERR_INVALID_ARG, "pt_scene_update: num_shapes differs from pt_scene_create's");
-    if (shading && d->num_materials != S->dev.num_materials) return fail(PT_ERR_INVALID_ARG, "pt_scene_update: num_materials differs from pt_scene_create's");
-    if (shading && d->num_lights != S->dev.num_emission) return fail(PT_ERR_INVALID_ARG, "pt_scene_update: num_lights differs from pt_scene_create's");
-    int rc;
-    std::vector<DMaterial> mats;
-    std::vector<DEmission> emis;
-    std::vector<DLight> dlights;
-    if (shading) {
-        if (!d->materials) return fail(PT_ERR_BAD_SCENE, "scene has no materials");
-        if (d->num_lights > 0 && !d->lights) return fail(PT_ERR_BAD_SCENE, "bad light array");
-        if ((rc = check_materials(d)) || (rc = pack_shading(d, N, mats, emis, dlights))) return rc;
-    }
-    if (geometry) {
-        if (!d->shapes) return fail(PT_ERR_BAD_SCENE, "scene has no shapes");
-        if (d->num_meshes < 0 || (d->num_meshes > 0 && !d->meshes)) return fail(PT_ERR_BAD_SCENE, "bad mesh array");
-        if ((rc = check_meshes(d, S->dev.num_materials))) return rc;
-    }
-    DeviceGuard guard;
-    { int grc = guard.enter(S->device); if (grc) return grc; }
-    // frames of this handle that are still in flight, on the caller's streams and on the slots' own, read the scene
-    HIP_TRY(hipDeviceSynchronize());
-    const clk::time_point t_all = clk::now();
-    int64_t us_records = 0, us_refit = 0, us_plan = 0;
-    if (geometry) {
-        const clk::time_point t_stage = clk::now();
-        pt_scene_desc dg = *d;                                // material ids are checked against the handle's table
-        dg.num_materials = S->dev.num_materials;
-        int has_sphere = 0;
-        if ((rc = ensure_staging(S))) return rc;
-        if ((rc = ptp::prims_device(&dg, S->st_prims.p, S->st_normals.p, &has_sphere))) return rc;
-        us_records = us_since(t_stage);
-        if ((rc = adopt_staged(S, "pt_scene_update", !has_sphere, &us_plan, &us_refit))) return rc;
-        S->have_rest = false;                        // the next pt_scene_transform starts from these records
-        rebuild_by_policy(S);
-    }
-    if (shading) {
-        const clk::time_point t_stage = clk::now();
-        HIP_TRY(hipMemcpy(S->materials.p, mats.data(), mats.size() * sizeof(DMaterial), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(S->emission.p, emis.data(), emis.size() * sizeof(DEmission), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(S->lights.p, dlights.data(), dlights.size() * sizeof(DLight), hipMemcpyHostToDevice));
-        S->dev.bg[0] = d->background[0]; S->dev.bg[1] = d->background[1]; S->dev.bg[2] = d->background[2];
-        S->diffuse_only = all_diffuse(d);
-        us_records += us_since(t_stage);
-    }
-    // the handle's own streams do not synchronise with the default stream the kernels above ran on
-    HIP_TRY(hipDeviceSynchronize());
-    collect_costs(S);
-    select_tree(S, 0);
-    S->updates++;
-    S->update_us[0] = us_since(t_all); S->update_us[1] = us_records; S->update_us[2] = us_refit; S->update_us[3] = us_plan;
-    return PT_OK;
-}
-
-// pt_scene_transform (include/pt_api.h).  pt_scene_update's order of events with another producer of the staged records: the
-// matrices are checked and their entries made on the host, the rest records are snapshot where none are held, one kernel writes
-// the staged records from them (pt_scene_transform.hip), and adopt_staged does the rest.
-int transform_scene(pt_scene* S, const pt_transform* transforms, int32_t num_groups) {
-    using clk = std::chrono::steady_clock;
-    auto us_since = [](clk::time_point t0) { return (int64_t)std::chrono::duration_cast<std::chrono::microseconds>(clk::now() - t0).count(); };
-    if (!S->have_groups) return fail(PT_ERR_INVALID_ARG, "pt_scene_transform: the scene has no group assignment (pt_scene_set_groups)");
-    if (num_groups != S->num_groups) return fail(PT_ERR_INVALID_ARG, "pt_scene_transform: num_groups differs from pt_scene_set_groups'");
-    if (num_groups > 0 && !transforms) return fail(PT_ERR_INVALID_ARG, "pt_scene_transform: null transforms");
-    std::vector<ptx::Entry> tab((size_t)std::max(num_groups, 1));
-    for (int32_t g = 0; g < num_groups; g++)
-        if (const int bad = ptx::prepare(&transforms[g], &tab[(size_t)g]))
-            return fail(ptx::refusal_status(bad), "pt_scene_transform: transforms[" + std::to_string(g) + "]: " + ptx::refusal(bad));
-    const int N = S->dev.num_prims;
-    DeviceGuard guard;
-    { int grc = guard.enter(S->device); if (grc) return grc; }
-    // frames of this handle that are still in flight, on the caller's streams and on the slots' own, read the scene
-    HIP_TRY(hipDeviceSynchronize());
-    const clk::time_point t_all = clk::now();
-    int64_t us_records = 0, us_refit = 0, us_once = 0;
-    int rc;
-    if ((rc = ensure_staging(S)) || (rc = S->group_tab.ensure(tab.size() * ptx::kEntryFloats))) return rc;
-    const bool snapshot = !S->have_rest;
-    if (snapshot) {
-        const clk::time_point t_stage = clk::now();
-        if ((rc = S->rest_prims.ensure((size_t)N)) || (rc = S->rest_normals.ensure((size_t)N))) return rc;
-        HIP_TRY(hipMemcpyAsync(S->rest_prims.p, S->prims.p, (size_t)N * sizeof(DPrim), hipMemcpyDeviceToDevice, nullptr));
-        HIP_TRY(hipMemcpyAsync(S->rest_normals.p, S->normals.p, (size_t)N * sizeof(DNormals), hipMemcpyDeviceToDevice, nullptr));
-        HIP_TRY(hipStreamSynchronize(nullptr));           // paid once: timed on its own
-        us_once = std::max<int64_t>(us_since(t_stage), 1);
-    }
-    const clk::time_point t_stage = clk::now();
-    HIP_TRY(hipMemcpy(S->group_tab.p, tab.data(), tab.size() * sizeof(ptx::Entry), hipMemcpyHostToDevice));
-    if ((rc = ptx::transform_records(S->rest_prims.p, S->rest_normals.p, S->group_of.p, S->group_tab.p, N, S->st_prims.p, S->st_normals.p)))
-        return rc;
-    us_records = us_since(t_stage);
-    int64_t us_plan = 0;
-    if ((rc = adopt_staged(S, "pt_scene_transform", S->tri_only, &us_plan, &us_refit))) return rc;
-    rebuild_by_policy(S);
-    // the handle's own streams do not synchronise with the default stream the kernels above ran on
-    HIP_TRY(hipDeviceSynchronize());
-    collect_costs(S);
-    S->have_rest = true;                                // (a refused call leaves the flag as it was: the next one copies again)
-    select_tree(S, 0);
-    S->transforms++;
-    S->transform_us[0] = us_since(t_all); S->transform_us[1] = us_records; S->transform_us[2] = us_refit; S->transform_us[3] = us_once + us_plan;
     return PT_OK;
 }
 
@@ -2051,8 +853,7 @@ int guide_pass(pt_scene* S, const pt_render_params* p, const pt_motion_params* m
     int rc = guide_render_dev(p, &rd, &traversal, &npix);
     if (rc) return rc;
     if (npix == 0 || (!albedo && !normal && !depth && !prim && !motion && !prev_depth)) return PT_OK;
-    DeviceGuard guard;
-    { int grc = guard.enter(S->device); if (grc) return grc; }
+    ENTER_DEVICE(S);
     // host outputs are staged in buffers of this call
     DevBuf<float> d_albedo, d_normal, d_depth, d_motion, d_prev_depth;
     DevBuf<int32_t> d_prim;
@@ -2168,8 +969,7 @@ int trace_rays_call(pt_scene* S, const float* rays, int32_t n, int mode, int tra
     if (!out_prim) return fail(PT_ERR_INVALID_ARG, std::string(fn) + "null out_prim");
     const bool closest = mode == PT_QUERY_CLOSEST;
     if (closest && !out_tuv) return fail(PT_ERR_INVALID_ARG, std::string(fn) + "null out_tuv");
-    DeviceGuard guard;
-    { int grc = guard.enter(S->device); if (grc) return grc; }
+    ENTER_DEVICE(S);
     ptq::QueryDev q{};
     q.n = (uint32_t)n;
     const bool prune = closest && traversal == PT_TRAVERSAL_PRUNED;      // a lane that stops at its first hit has nothing to prune by
@@ -2197,8 +997,7 @@ int guides_async_call(pt_scene* S, const pt_render_params* p, const pt_motion_pa
     if (rc) return rc;
     float *motion = m ? out.motion : nullptr, *prev_depth = m ? out.prev_depth : nullptr;
     if (npix == 0 || (!out.albedo && !out.normal && !out.depth && !out.prim && !motion && !prev_depth)) return PT_OK;
-    DeviceGuard guard;
-    { int grc = guard.enter(S->device); if (grc) return grc; }
+    ENTER_DEVICE(S);
     MotionDev mo{};
     if (m) {
         guide_motion_dev(S, m, &mo);
@@ -2351,8 +1150,7 @@ int temporal_call(const char* fn, bool moments, pt_scene* S, const pt_temporal_p
     if (rc) return rc;
     ptt::Lambda lam{};
     if (adaptive && (rc = adaptive_args(fn, r, lambda, stride, &lam))) return rc;
-    DeviceGuard guard;
-    { int grc = guard.enter(S->device); if (grc) return grc; }
+    ENTER_DEVICE(S);
     pt_temporal_io io = *io_in;
     const Plane planes[] = {{&io.color, nullptr, 3}, {&io.albedo, nullptr, moments ? 3 : 0}, {&io.normal, nullptr, 3},
                             {&io.motion, nullptr, 2}, {&io.prev_depth, nullptr, 1},
@@ -2387,8 +1185,7 @@ int temporal_call(const char* fn, bool moments, pt_scene* S, const pt_temporal_p
 int gradient_call(pt_scene* S, const ptg::Resolved& r, const float* prev_color, const float* resampled, float* lambda_out, int on_device,
                   void* hip_stream) {
     const char* fn = "pt_temporal_gradient";
-    DeviceGuard guard;
-    { int grc = guard.enter(S->device); if (grc) return grc; }
+    ENTER_DEVICE(S);
     const size_t ntiles = (size_t)r.tw * (size_t)r.th;
     int rc;
     if ((rc = S->gr_x[0].ensure(2 * ntiles)) || (rc = S->gr_x[1].ensure(2 * ntiles))) return rc;
@@ -2433,8 +1230,7 @@ int sparse_args(const char* fn, const pt_gradient_params* g, std::initializer_li
 // buffer on the default stream and copied out.
 int gradient_pixels_call(pt_scene* S, const ptg::Resolved& r, uint32_t seed, int32_t* pixels_out, int on_device, void* hip_stream) {
     const char* fn = "pt_gradient_pixels";
-    DeviceGuard guard;
-    { int grc = guard.enter(S->device); if (grc) return grc; }
+    ENTER_DEVICE(S);
     const size_t ntiles = (size_t)r.tw * (size_t)r.th;
     int rc;
     int32_t* d_out = pixels_out;
@@ -2453,8 +1249,7 @@ int gradient_pixels_call(pt_scene* S, const ptg::Resolved& r, uint32_t seed, int
 int gradient_sparse_call(pt_scene* S, const ptg::Resolved& r, const float* prev_color, const int32_t* pixels, const float* resampled,
                          float* lambda_out, int on_device, void* hip_stream) {
     const char* fn = "pt_temporal_gradient_sparse";
-    DeviceGuard guard;
-    { int grc = guard.enter(S->device); if (grc) return grc; }
+    ENTER_DEVICE(S);
     const size_t ntiles = (size_t)r.tw * (size_t)r.th;
     int rc;
     if ((rc = S->gr_x[0].ensure(2 * ntiles)) || (rc = S->gr_x[1].ensure(2 * ntiles))) return rc;
@@ -2480,8 +1275,7 @@ int gradient_sparse_call(pt_scene* S, const ptg::Resolved& r, const float* prev_
 // written over the colour plane of a staged call.
 int denoise_call(const char* fn, pt_scene* S, const ptdn::Resolved& r, ptdn::Frames f, DevBuf<float4>& guide, DevBuf<float4> (&x)[2],
                  DevBuf<float>& staging, int on_device, void* hip_stream) {
-    DeviceGuard guard;
-    { int grc = guard.enter(S->device); if (grc) return grc; }
+    ENTER_DEVICE(S);
     const size_t npix = (size_t)r.width * (size_t)r.height;
     int rc;
     if ((rc = guide.ensure(npix)) || (rc = x[0].ensure(npix)) || (rc = x[1].ensure(npix))) return rc;
@@ -2503,6 +1297,13 @@ int denoise_host_call(const char* fn, const ptdn::Resolved& r, const ptdn::Frame
     return PT_OK;
 }
 
+// Info keys "<prefix>0" .. "<prefix><count - 1>": *value = a[digit]; false: k is no such key.
+bool indexed_key(const std::string& k, const std::string& prefix, int count, const int64_t* a, int64_t* value) {
+    const bool hit = k.size() == prefix.size() + 1 && k.compare(0, prefix.size(), prefix) == 0 && k.back() >= '0' && k.back() < '0' + count;
+    if (hit) *value = a[k.back() - '0'];
+    return hit;
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------------------------------
@@ -2512,96 +1313,6 @@ extern "C" {
 
 int pt_api_version(void) { return PT_API_VERSION; }
 const char* pt_last_error(void) { return g_err.c_str(); }
-
-int pt_scene_create(const pt_scene_desc* desc, pt_scene** out) {
-    if (!out) return fail(PT_ERR_INVALID_ARG, "null output pointer");
-    *out = nullptr;
-    int ndev = 0;
-    hipError_t e = hipGetDeviceCount(&ndev);
-    if (e != hipSuccess || ndev <= 0) return fail(PT_ERR_NO_DEVICE, "no HIP device available: the path tracer has no CPU fallback");
-    pt_scene* S = new pt_scene();
-    auto bail = [&](int rc) { pt_scene_destroy(S); return rc; };
-    if (hipGetDevice(&S->device) != hipSuccess) return bail(fail(PT_ERR_DEVICE, "hipGetDevice failed"));
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, S->device) != hipSuccess) return bail(fail(PT_ERR_DEVICE, "hipGetDeviceProperties failed"));
-    S->num_cus = prop.multiProcessorCount;
-    S->lds_per_block_max = prop.sharedMemPerBlock;
-    int rc = validate_and_build(desc, S);
-    if (rc) return bail(rc);
-    *out = S;
-    return PT_OK;
-}
-
-int pt_scene_destroy(pt_scene* S) {
-    if (!S) return PT_OK;
-    DeviceGuard guard;
-    (void)guard.enter(S->device);
-    if (S->last_stream || S->have_timing || S->q_seq) (void)hipDeviceSynchronize();
-    S->drop_query();
-    for (auto& T : S->tree) { T.nodes.release(); T.nodes_oct.release(); } S->drop_slots(); S->prims.release(); S->normals.release(); S->materials.release(); S->emission.release();
-    S->lights.release(); S->sweep_tab.release(); S->accum.release(); S->fb_tmp.release();
-    S->ad_sum.release(); S->ad_mom.release(); S->ad_list[0].release(); S->ad_list[1].release(); S->ad_count.release();
-    S->ad_spp_tmp.release(); S->ad_err_tmp.release();
-    S->dn_guide.release(); S->dn_x[0].release(); S->dn_x[1].release(); S->dn_host.release(); S->tp_host.release();
-    S->vd_guide.release(); S->vd_x[0].release(); S->vd_x[1].release(); S->vd_host.release();
-    S->gr_x[0].release(); S->gr_x[1].release(); S->gr_host.release(); S->px_list.release();
-    S->st_prims.release(); S->prev_prims.release(); S->st_normals.release(); S->st_boxes.release(); S->st_status.release();
-    S->group_of.release(); S->group_tab.release(); S->rest_prims.release(); S->rest_normals.release();
-    for (auto& pl : S->refit_plan) ptf::plan_release(&pl);
-    S->cost_partials.release(); S->cost_dev.release();
-    if (S->cost_host) (void)hipHostFree(S->cost_host);
-    S->cost_host = nullptr;
-    S->drop_events();
-    delete S;
-    return PT_OK;
-}
-
-int pt_scene_update(pt_scene* S, const pt_scene_desc* desc, int flags) {
-    if (!S) return fail(PT_ERR_INVALID_ARG, "pt_scene_update: null scene");
-    if (!desc) return fail(PT_ERR_INVALID_ARG, "pt_scene_update: null scene description");
-    if (flags == 0 || (flags & ~(PT_UPDATE_GEOMETRY | PT_UPDATE_SHADING)))
-        return fail(PT_ERR_INVALID_ARG, "pt_scene_update: flags must be PT_UPDATE_GEOMETRY, PT_UPDATE_SHADING or both");
-    return update_scene(S, desc, flags);
-}
-
-int pt_scene_rebuild(pt_scene* S, int flags) {
-    if (!S) return fail(PT_ERR_INVALID_ARG, "pt_scene_rebuild: null scene");
-    if (flags != 0) return fail(PT_ERR_INVALID_ARG, "pt_scene_rebuild: flags must be 0 (reserved)");
-    DeviceGuard guard;
-    { int grc = guard.enter(S->device); if (grc) return grc; }
-    // frames of this handle that are still in flight, on the caller's streams and on the slots' own, read the scene
-    HIP_TRY(hipDeviceSynchronize());
-    const int rc = rebuild_scene(S);
-    // the handle's own streams do not synchronise with the default stream the kernels above ran on
-    const hipError_t e = hipDeviceSynchronize();
-    if (rc) return rc;
-    HIP_TRY(e);
-    return PT_OK;
-}
-
-int pt_scene_set_groups(pt_scene* S, const int32_t* group_of_shape, int32_t num_groups) {
-    if (!S) return fail(PT_ERR_INVALID_ARG, "pt_scene_set_groups: null scene");
-    if (!group_of_shape) return fail(PT_ERR_INVALID_ARG, "pt_scene_set_groups: null group_of_shape");
-    if (num_groups < 0 || num_groups > (1 << 20)) return fail(PT_ERR_INVALID_ARG, "pt_scene_set_groups: num_groups must be in [0, 2^20]");
-    const int N = S->dev.num_prims;
-    for (int k = 0; k < N; k++)
-        if (group_of_shape[k] < -1 || group_of_shape[k] >= num_groups)
-            return fail(PT_ERR_INVALID_ARG, "pt_scene_set_groups: group_of_shape[" + std::to_string(k) + "] is not in [-1, num_groups)");
-    DeviceGuard guard;
-    { int grc = guard.enter(S->device); if (grc) return grc; }
-    int rc = S->group_of.ensure((size_t)N);
-    if (rc) return rc;
-    S->have_groups = false;                              // a copy that fails leaves no assignment, not half of one
-    HIP_TRY(hipMemcpy(S->group_of.p, group_of_shape, (size_t)N * sizeof(int32_t), hipMemcpyHostToDevice));
-    S->num_groups = num_groups;
-    S->have_groups = true;
-    return PT_OK;
-}
-
-int pt_scene_transform(pt_scene* S, const pt_transform* transforms, int32_t num_groups) {
-    if (!S) return fail(PT_ERR_INVALID_ARG, "pt_scene_transform: null scene");
-    return transform_scene(S, transforms, num_groups);
-}
 
 int pt_transform_geometry_host(const pt_transform* t, int32_t n, const float* positions, const float* normals, float* positions_out,
                                float* normals_out) {
@@ -2651,8 +1362,7 @@ int pt_render(pt_scene* S, const pt_render_params* p, float* fb, int fb_on_devic
     if (rc) return rc;
     if (p->width <= 0) return fail(PT_ERR_INVALID_ARG, "width must be positive");
     const size_t n = (size_t)rows.count * (size_t)p->width * 3;
-    DeviceGuard guard;
-    { int grc = guard.enter(S->device); if (grc) return grc; }
+    ENTER_DEVICE(S);
     if ((rc = S->fb_tmp.ensure(n))) return rc;
     rc = launch_render(S, p, S->fb_tmp.p, 0, nullptr);
     if (rc) return rc;
@@ -2680,8 +1390,7 @@ int pt_render_pixels(pt_scene* S, const pt_render_params* p, const int32_t* pixe
     for (int32_t k = 0; k < n; k++)
         if (pixels[k] < 0 || (int64_t)pixels[k] >= frame)
             return fail(PT_ERR_INVALID_ARG, pre + "pixels[" + std::to_string(k) + "] = " + std::to_string(pixels[k]) + " is outside the frame");
-    DeviceGuard guard;
-    { int grc = guard.enter(S->device); if (grc) return grc; }
+    ENTER_DEVICE(S);
     int rc;
     if ((rc = S->px_list.ensure((size_t)n)) || (rc = S->fb_tmp.ensure((size_t)n * 3))) return rc;
     HIP_TRY(hipMemcpy(S->px_list.p, pixels, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice));
@@ -2719,8 +1428,7 @@ int pt_render_adaptive(pt_scene* S, const pt_render_params* p, const pt_adaptive
         const double mid = 0.5 * (zlo + zhi);
         (std::erfc(mid / std::sqrt(2.0)) > pv ? zlo : zhi) = mid;
     }
-    DeviceGuard guard;
-    { int grc = guard.enter(S->device); if (grc) return grc; }
+    ENTER_DEVICE(S);
     S->info_adaptive_rounds = 0;
     pt_render_params pr = *p;
     pr.stream_stride = p->stream_stride > 0 ? p->stream_stride : (int32_t)max_spp;
@@ -2987,8 +1695,7 @@ int pt_get_counters(pt_scene* S, pt_counters* out) {
 int pt_get_frame_times(pt_scene* S, int max_frames, double* kernel_ms, double* resolve_ms, int* n_out) {
     if (!S || !kernel_ms || !resolve_ms || !n_out || max_frames < 0) return fail(PT_ERR_INVALID_ARG, "bad argument");
     *n_out = 0;
-    DeviceGuard guard;
-    { int grc = guard.enter(S->device); if (grc) return grc; }
+    ENTER_DEVICE(S);
     HIP_TRY(hipStreamSynchronize(S->last_stream));
     const uint64_t have = std::min<uint64_t>(S->frame_seq, S->frames.size());
     const int n = (int)std::min<uint64_t>(have, (uint64_t)max_frames);
@@ -3083,19 +1790,17 @@ int pt_scene_get_info(pt_scene* S, const char* key, int64_t* value) {
     else if (k == "top_nodes") *value = make_plan(S, next).top_count;     // make_plan's count even on kernel 3, whose make_plan_q caches another
     else if (k == "device") *value = S->device;
     else if (k == "sweep_on_device") *value = S->sweep_on_device;         // the internal tree was built on the GPU (pt_sweep_build.hip)
-    else if (k.rfind("create_us", 0) == 0 && k.size() == 10 && k[9] >= '0' && k[9] <= '6') *value = S->create_us[k[9] - '0'];
+    else if (indexed_key(k, "create_us", 7, S->create_us, value) || indexed_key(k, "update_us", 4, S->update_us, value) ||
+             indexed_key(k, "transform_us", 4, S->transform_us, value) || indexed_key(k, "rebuild_us", 4, S->rebuild_us, value)) {}   // stage times (pt_scene.h)
     else if (k == "prev_geometry") *value = S->have_prev ? 1 : 0;         // records from before the last geometry update are kept (pt_render_guides)
     else if (k == "updates") *value = S->updates;                         // successful pt_scene_update calls so far
-    else if (k.rfind("update_us", 0) == 0 && k.size() == 10 && k[9] >= '0' && k[9] <= '3') *value = S->update_us[k[9] - '0'];
     else if (k == "groups") *value = S->have_groups ? S->num_groups : 0;  // groups of the assignment pt_scene_set_groups made (0: none)
     else if (k == "rest_geometry") *value = S->have_rest ? 1 : 0;         // a snapshot of the rest records is held (pt_scene_transform)
     else if (k == "transforms") *value = S->transforms;                   // successful pt_scene_transform calls so far
-    else if (k.rfind("transform_us", 0) == 0 && k.size() == 13 && k[12] >= '0' && k[12] <= '3') *value = S->transform_us[k[12] - '0'];
     else if (k == "rebuilds") *value = S->rebuilds;                       // successful pt_scene_rebuild calls so far, a policy's included
     else if (k == "rebuilds_auto") *value = S->rebuilds_auto;             // ... those that option rebuild_at_permille made
     else if (k == "rebuild_adopted") *value = S->rebuild_adopted;         // the last one adopted its tree (1) or kept the one it had (0)
     else if (k == "rebuild_cost_permille") *value = S->rebuild_cost_permille;   // the last candidate's probe ratio (as fast_tree_cost_permille)
-    else if (k.rfind("rebuild_us", 0) == 0 && k.size() == 11 && k[10] >= '0' && k[10] <= '3') *value = S->rebuild_us[k[10] - '0'];
     else if (k == "tree_cost0_bits" || k == "tree_cost1_bits") {
         // option tree_cost: the fp64 bit pattern of tree 0's / 1's cost after the last refit (0: no such tree, nothing measured)
         const int t = k[9] - '0';
@@ -3141,7 +1846,7 @@ int pt_scene_get_info(pt_scene* S, const char* key, int64_t* value) {
             if (rc) return rc;
             v = c[4 + idx];
         } else {                                          // launch timeline / histograms
-            { int grc = guard.enter(S->device); if (grc) return grc; }
+            if (int grc = guard.enter(S->device)) return grc;
             HIP_TRY(hipStreamSynchronize(S->last_stream));
             if (S->cur().ctl.p) HIP_TRY(hipMemcpy(&v, S->counters() + kTimelineBase + (idx - 8), sizeof v, hipMemcpyDeviceToHost));
         }
@@ -3225,74 +1930,10 @@ int pt_debug_math_host(int op, const float* x, const float* y, float* out0, floa
     return PT_OK;
 }
 
-int pt_bvh_build_sweep(const pt_scene_desc* d, pt_bvh_node* out_nodes, int32_t* out_root, int32_t* out_depth, double* out_build_ms) {
-    if (!d || !out_nodes || !out_root) return fail(PT_ERR_INVALID_ARG, "bad argument");
-    const int N = d->num_shapes;
-    if (N <= 0 || !d->nodes || d->num_nodes != 2 * N - 1) return fail(PT_ERR_BAD_SCENE, "needs the leaf boxes of a 2*num_shapes-1 node pool");
-    std::vector<float> boxes((size_t)N * 6);
-    std::vector<char> seen(N, 0);
-    for (int k = 0; k < d->num_nodes; k++) {
-        const pt_bvh_node& nd = d->nodes[k];
-        if (nd.prim == -1) continue;
-        if (nd.prim < 0 || nd.prim >= N || seen[nd.prim]) return fail(PT_ERR_BAD_SCENE, "leaves must cover every shape exactly once");
-        seen[nd.prim] = 1;
-        std::memcpy(&boxes[(size_t)nd.prim * 6], nd.bmin, 12);
-        std::memcpy(&boxes[(size_t)nd.prim * 6 + 3], nd.bmax, 12);
-    }
-    for (int i = 0; i < N; i++)
-        if (!seen[i]) return fail(PT_ERR_BAD_SCENE, "leaves must cover every shape exactly once");
-    for (float v : boxes)
-        if (!std::isfinite(v)) return fail(PT_ERR_BAD_SCENE, "leaf box is not finite");
-    const auto t0 = std::chrono::steady_clock::now();
-    std::vector<pt_bvh_node> nodes;
-    int32_t root = 0, depth = 0;
-    try {
-        pts::build_sweep_tree(boxes.data(), N, nodes, &root, &depth);
-    } catch (const std::exception& e) {
-        return fail(PT_ERR_DEVICE, std::string("pt_bvh_build_sweep: ") + e.what());
-    }
-    std::memcpy(out_nodes, nodes.data(), nodes.size() * sizeof(pt_bvh_node));
-    *out_root = root;
-    if (out_depth) *out_depth = depth;
-    if (out_build_ms) *out_build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    return PT_OK;
-}
-
-int pt_bvh_build_sweep_device(const pt_scene_desc* d, pt_bvh_node* out_nodes, int32_t* out_root, int32_t* out_depth, double* out_build_ms) {
-    if (!d || !out_nodes || !out_root) return fail(PT_ERR_INVALID_ARG, "bad argument");
-    const int N = d->num_shapes;
-    if (N <= 0 || !d->nodes || d->num_nodes != 2 * N - 1) return fail(PT_ERR_BAD_SCENE, "needs the leaf boxes of a 2*num_shapes-1 node pool");
-    std::vector<float> boxes((size_t)N * 6);
-    std::vector<char> seen(N, 0);
-    for (int k = 0; k < d->num_nodes; k++) {
-        const pt_bvh_node& nd = d->nodes[k];
-        if (nd.prim == -1) continue;
-        if (nd.prim < 0 || nd.prim >= N || seen[nd.prim]) return fail(PT_ERR_BAD_SCENE, "leaves must cover every shape exactly once");
-        seen[nd.prim] = 1;
-        std::memcpy(&boxes[(size_t)nd.prim * 6], nd.bmin, 12);
-        std::memcpy(&boxes[(size_t)nd.prim * 6 + 3], nd.bmax, 12);
-    }
-    for (int i = 0; i < N; i++)
-        if (!seen[i]) return fail(PT_ERR_BAD_SCENE, "leaves must cover every shape exactly once");
-    for (float v : boxes)
-        if (!std::isfinite(v)) return fail(PT_ERR_BAD_SCENE, "leaf box is not finite");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(PT_ERR_NO_DEVICE, "no HIP device available");
-    std::vector<pt_bvh_node> nodes;
-    int32_t root = 0, depth = 0;
-    int rc = pts::sweep_build_device(boxes.data(), N, nodes, &root, &depth, out_build_ms);
-    if (rc) return rc;
-    std::memcpy(out_nodes, nodes.data(), nodes.size() * sizeof(pt_bvh_node));
-    *out_root = root;
-    if (out_depth) *out_depth = depth;
-    return PT_OK;
-}
-
 int pt_debug_intersect(pt_scene* S, const float* rays, int n, int traversal, float* out_tuv, int32_t* out_prim) {
     if (!S || !rays || !out_tuv || !out_prim || n < 0) return fail(PT_ERR_INVALID_ARG, "bad argument");
     if (n == 0) return PT_OK;
-    DeviceGuard guard;
-    { int grc = guard.enter(S->device); if (grc) return grc; }
+    ENTER_DEVICE(S);
     DevBuf<float> dr, dt;
     DevBuf<int32_t> dp, dn;
     int rc;

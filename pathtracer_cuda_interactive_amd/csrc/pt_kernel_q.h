@@ -121,7 +121,7 @@ __device__ __forceinline__ uint32_t q_claim(lds_u32* head_tail, uint32_t want, u
 
 // The 22 words of a path.  a0..a3: the closest hit (t, u, v, primitive) on the way to shading; 1/d (and nothing) on the way
 // to traversal.  depth_flags: bits 0..15 bounces so far (the ray in flight is a camera ray iff 0), bit 31 = trace this ray on
-// the caller's tree in reference order (1/d not finite, pt_api.hip: validate_and_build).
+// the caller's tree in reference order (1/d not finite, pt_scene_life.hip: validate_and_build).
 struct QPath {
     ptm::V3 org, dir;
     float a0, a1, a2, a3;

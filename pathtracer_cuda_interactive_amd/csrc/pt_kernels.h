@@ -700,7 +700,7 @@ __global__ __launch_bounds__(kBlock) void aov_kernel(SceneDev scn, RenderDev rp,
     write_guides<MOTION>(sv, rp, r, h, k, albedo, normal, depth, prim, mo);
 }
 
-// Inner-node visits of a fixed set of probe rays through the tree `scn` points at (pt_api.hip: validate_and_build chooses
+// Inner-node visits of a fixed set of probe rays through the tree `scn` points at (pt_scene_life.hip: validate_and_build chooses
 // between the caller's tree and the internal one by this count).  Ray k starts on primitive hash(k) mod N — its centroid,
 // or the point of a sphere facing the direction — and leaves into a uniform direction: the shape of a segment after a bounce.
 // Both trees in one launch: blockIdx.y picks the tree and its counter (two launches of 128 blocks each ran one after the other

@@ -1,6 +1,6 @@
 // pt_leaf_sweep.h — the leaf sweep of trace_kernel_v2_sweep (pt_kernels.h): which leaves a ray tests, found without a tree.
 //
-// On the internal tree exact traversal tests a leaf if and only if the ray hits the leaf's own box (pt_api.hip,
+// On the internal tree exact traversal tests a leaf if and only if the ray hits the leaf's own box (pt_scene_life.hip,
 // validate_and_build: the slab test is monotone in the box and every box contains its children's).  The tree is one way to
 // find that set; for a scene of a few dozen primitives it is cheaper to test every DISTINCT leaf box once when the segment
 // starts, at the width of the scheduler phase.  Leaves whose boxes are equal bit for bit (the two triangles of an axis-aligned

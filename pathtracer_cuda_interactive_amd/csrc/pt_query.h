@@ -26,7 +26,7 @@
 // first ranges plus one per wave that finds the end: a 1280x960 frame on 4,096 waves is 19,000 adds, a fifth of a millisecond
 // if nothing else took time (on a scene as small as cbox nothing else does).
 //
-// Every launch needs a counter of its own; the handle keeps a ring of kQueryRing of them (pt_api.hip).
+// Every launch needs a counter of its own; the handle keeps a ring of kQueryRing of them (pt_scene.h).
 #pragma once
 
 #include "pt_kernels.h"

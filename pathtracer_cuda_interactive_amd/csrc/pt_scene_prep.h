@@ -17,7 +17,7 @@ int tie_tables_device(const pt_bvh_node* pool_dev, int num_nodes, int root, cons
 
 
 // ---- a node pool (bvh.cuh:7-15: one node per leaf and per inner node, children by index) re-laid on the device -------------
-// What pt_api.hip's convert_tree does on the host, for pools that are already in device memory: validation (caller's trees),
+// What pt_scene_life.hip's convert_tree does on the host, for pools that are already in device memory: validation (caller's trees),
 // the DFS pre-order of the inner nodes — for the library's own tree with the child that needs the shallower stack first
 // (Strahler numbers) —, the most-visited top of the tree renumbered to the front, 64-B DNodes carrying both child boxes.
 struct RelayResult {

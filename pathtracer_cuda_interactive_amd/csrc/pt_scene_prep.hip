@@ -169,7 +169,7 @@ __device__ __forceinline__ double relay_area(const pt_bvh_node& b) {
     const double x = (double)b.bmax[0] - b.bmin[0], y = (double)b.bmax[1] - b.bmin[1], z = (double)b.bmax[2] - b.bmin[2];
     return 2.0 * (x * y + y * z + z * x);
 }
-// The `want` inner nodes with the largest boxes, parents before children (pt_api.hip: convert_tree has the argument): the host
+// The `want` inner nodes with the largest boxes, parents before children (pt_scene_life.hip: convert_tree has the argument): the host
 // pops a max-heap of (area, -pre-order position) — a total order, so the sequence of picks is simply "the largest entry of the
 // frontier, `want` times".  One wave: the frontier sits unsorted in LDS, every pick is a 64-lane argmax over it (at most `want` + 1
 // entries), lanes 0 and 1 fetch the picked node's two children in one round trip (an entry carries its children's indices), the

@@ -200,7 +200,7 @@ __global__ void lift_level_kernel(DNode* __restrict__ nodes, const int32_t* __re
 }
 // ONE workgroup: levels top_level .. 1, a barrier between them (the stores of a level and the loads of the next are this
 // workgroup's own, on one CU).  N > 0: the leaf pass first, from the staged records, nothing written unless every record and
-// every box is finite.  nodes_oct: the 8 octant tables at the end (pt_api.hip: upload_tree — octant bit k set <=> the two planes of axis k
+// every box is finite.  nodes_oct: the 8 octant tables at the end (pt_scene_life.hip: upload_tree — octant bit k set <=> the two planes of axis k
 // trade places).
 __global__ __launch_bounds__(kThreads) void refit_top_kernel(DNode* __restrict__ nodes, DNode* __restrict__ nodes_oct, int num_nodes,
                                                              const int32_t* __restrict__ parent_slot, const int32_t* __restrict__ leaf_slot,

@@ -69,7 +69,7 @@ inline bool build_sweep_layout(const SweepGroup* groups, int count, const DNode*
         if (node >= (uint32_t)num_nodes || (rest != 0 && rest != kSweepBoxBytes)) return false;
         const float* box = rest ? nodes[node].rmin : nodes[node].lmin;             // min[3] then max[3], contiguous
         for (uint32_t o = 0; o < 8; o++) {
-            // octant bit a set <=> 1/d[a] < 0: the near plane of axis a is the box's max (pt_api.hip: upload_tree)
+            // octant bit a set <=> 1/d[a] < 0: the near plane of axis a is the box's max (pt_scene_life.hip: upload_tree)
             float nf[6];
             for (int a = 0; a < 3; a++) {
                 const bool neg = (o >> a) & 1u;

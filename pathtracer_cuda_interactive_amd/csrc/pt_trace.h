@@ -201,7 +201,7 @@ __device__ __forceinline__ void visit_node(const float4 a, const float4 b, const
     // fixed_order (wave-uniform; the internal tree only, where exact traversal may visit in ANY order — rays whose answer
     // depends on it are rerun on the caller's tree): left first.  The builder puts the child that needs the SHALLOWER stack
     // on the left, which bounds the stack by the tree's Strahler number, <= log2(leaves) + 1, however deep the tree is
-    // (pt_api.hip: convert_tree).
+    // (pt_scene_life.hip: convert_tree).
     const bool left_first = S::kLeftFirst || fixed_order || ltn < rtn;
     const bool both = hl && hr;
     const int32_t next = (hl && (!hr || left_first)) ? L : R;
@@ -405,7 +405,7 @@ __device__ __forceinline__ Hit intersect(const SceneView& sv, const Ray& ray, in
 
 // The same closest hit — ties and all — traversed on ANOTHER tree over the same leaf boxes (`sv`): ties on t are settled in
 // the caller's visit order inside leaf_step (ref_visits_first), and a ray with a zero direction component is traced on the
-// caller's tree (`sv_ref`) instead (pt_api.hip: validate_and_build has the argument).  The trace kernel inlines the same three steps into its
+// caller's tree (`sv_ref`) instead (pt_scene_life.hip: validate_and_build has the argument).  The trace kernel inlines the same three steps into its
 // scheduler; this run-to-completion form serves pt_debug_intersect.  `rerun` reports that the reference order was needed.
 // PRUNE: the opt-in pruned traversal takes the same tree and the same tie handling (launch_render), its reruns are exact.
 template <bool PRUNE = false>

@@ -126,7 +126,7 @@
                 const ptm::V3 inv = ptm::mk(ptm::rcp_exact(ray.dir.x), ptm::rcp_exact(ray.dir.y), ptm::rcp_exact(ray.dir.z));
                 tv.best.t = FLT_MAX; tv.best.u = 0.0f; tv.best.v = 0.0f; tv.best.prim = -1;
                 // 1/d infinite on an axis: 0 * inf in the slab test is outside the argument that lets the leaf boxes alone decide
-                // (pt_api.hip: validate_and_build) -> the reference-order rerun in the next phase, no candidates
+                // (pt_scene_life.hip: validate_and_build) -> the reference-order rerun in the next phase, no candidates
                 tv.redo = !(__builtin_isfinite(inv.x) && __builtin_isfinite(inv.y) && __builtin_isfinite(inv.z));
                 if (!tv.redo) {
                     // the lane's octant box table, in LDS's 32-bit address space, read front to back: two groups per
@@ -175,7 +175,7 @@
         // ---- burst: N_LEAF leaf tests.  A lane goes on inside the group it took up last (pend: the link of the record just
         // tested), else it takes up the first group whose hit bit is set: groups in table order, a group's primitives in ascending
         // order.  That is not the order of the tree kernel, and need not be: exact traversal on the internal tree may test the
-        // leaves in ANY order (pt_api.hip: validate_and_build) — the set of leaves tested is the set whose box the ray hits,
+        // leaves in ANY order (pt_scene_life.hip: validate_and_build) — the set of leaves tested is the set whose box the ray hits,
         // the closest hit is the minimum over that set, and where two of them tie on t the leaf test asks the caller's tree
         // which one the reference visits first (ref_visits_first), a question of the two primitives alone, not of which was
         // tested first.

@@ -218,7 +218,7 @@
                 ptd::trav_begin(sv, ray, tv, stack);
                 if (!(NEE && in_shadow)) n_segs++;          // "segments" = intersect() calls; shadow rays are not counted
                 // 1/d infinite on an axis: 0 * inf in the slab test is outside the argument that lets another tree stand in
-                // for the caller's (pt_api.hip: validate_and_build) -> straight to the reference-order rerun
+                // for the caller's (pt_scene_life.hip: validate_and_build) -> straight to the reference-order rerun
                 if (fbk && !(__builtin_isfinite(tv.inv.x) && __builtin_isfinite(tv.inv.y) && __builtin_isfinite(tv.inv.z))) {
                     tv.redo = true;
                     tv.cur = DONE;

@@ -1,4 +1,4 @@
-// Host side, scene creation only: the library's internal tree over the caller's LEAF boxes (pt_api.hip: validate_and_build
+// Host side, scene creation only: the library's internal tree over the caller's LEAF boxes (pt_scene_life.hip: validate_and_build
 // explains why any tree over the same leaf boxes gives the reference's result).
 //
 // Exact traversal never prunes (scene.h:258-297), so a ray pays for every inner box it touches and the tree is the whole

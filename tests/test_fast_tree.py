@@ -1,4 +1,4 @@
-"""Exact traversal on the library's internal tree (pt_api.hip: validate_and_build / which_tree).
+"""Exact traversal on the library's internal tree (pt_scene_life.hip: validate_and_build; pt_api.hip: which_tree).
 
 The reference's intersect() (scene.h:246-301) never prunes: a leaf is tested iff the ray passes the box test of every node
 on the way down.  Where every box contains its children's boxes the slab test is monotone in the box, so that is: iff the

@@ -773,6 +773,13 @@ int pt_bvh_build_sweep_device(const pt_scene_desc* desc, pt_bvh_node* out_nodes,
  *                   tests a leaf iff the ray hits the leaf's own box (see "fast_tree"), so the same leaves are tested and the
  *                   frame is the same, bit for bit.  0 = always the tree.  A handle whose geometry was updated keeps to the
  *                   tree.  Info "leaf_sweep" reports the last launch; node visits ("stats") always count the tree's.
+ *   "sweep_pairs"   1 (default) a "leaf_sweep" launch tests its groups two by two in an order made at pt_scene_create: two
+ *                   groups whose boxes have the same interval on an axis (both floats equal bit for bit; -0.0 is not +0.0)
+ *                   share that axis's slab products, and where the interval is flat (min == max) one product serves as near
+ *                   and far of both (csrc/pt_sweep_pairs.h).  0 = the groups in the order the tree lists them, every pair
+ *                   computed in full.  The same operations on the same operands either way: the same bits.  Info
+ *                   "sweep_share_pairs", "sweep_flat_pairs" (each also with _x, _y, _z for one axis) and "sweep_general_pairs"
+ *                   report the pairs of each kind a sweep launch of the handle runs under the option as it stands.
  *   "octants"       1 (default) keep 8 ray-octant node tables in LDS for very small scenes, 0 = one table
  *   "fast_tree"     1 (default) traversal (exact and pruned) on the library's INTERNAL tree where pt_scene_create kept one,
  *                   0 = on the caller's tree.  Same image either way, bit for bit: the reference never prunes, so a leaf is tested iff the
@@ -827,6 +834,7 @@ int pt_bvh_build_sweep_device(const pt_scene_desc* desc, pt_bvh_node* out_nodes,
  * register bank filled 64 at a time: trace_kernel_v2 on LDS-resident scenes of triangles with diffuse materials),
  * "reg_stack" (1 = that kernel kept its traversal stack in a register, see option "reg_stack"; "lds_bytes" of such a launch has no
  * stack columns), "leaf_sweep" (1 = that kernel found its leaves by the box sweep, see option "leaf_sweep"), "sweep_boxes",
+ * "sweep_share_pairs", "sweep_flat_pairs", "sweep_general_pairs" (see option "sweep_pairs"),
  * "frames_in_flight", "sweep_on_device" (the internal tree was built on the GPU), "query_chunk" (ray indices a wave of the query
  * kernel reserves per atomic), "query_grid" (blocks of the last query launch), "query_guides" (the last pt_render_guides_async
  * ran on the refilling kernel: 1, or the one-shot kernel: 0),

@@ -17,6 +17,7 @@
 #include "pt_path_bank.h"
 #include "pt_path_index.h"
 #include "pt_sweep_layout.h"
+#include "pt_sweep_pairs.h"
 #include "pt_temporal.h"
 #include "pt_trace.h"
 
@@ -370,7 +371,8 @@ __global__ __launch_bounds__(kBlock, (kBlock > 256 ? 1 : MINW)) void trace_kerne
 // testing every group's box when a segment starts instead of walking the tree.  Same leaves tested, same closest hit, same
 // frame.  A third text rather than a flag of the body above: what that body compiles to for every other instantiation stays
 // as it is.  The sweep's tables (pt_sweep_layout.h) come behind the arguments every trace kernel takes (SweepKernelArgs, for
-// offsetof) as a pointer and the group count, and are staged into the node region of the tree kernel's LdsPlan.
+// offsetof) as a pointer, the group count, the pitch of the box tables and the pairs per class of the sweep loop
+// (pt_sweep_pairs.h), and are staged into the node region of the tree kernel's LdsPlan.
 // PT_SWEEP_LEAF_STEPS: leaf tests per iteration between two scheduler checks; PT_SWEEP_THRESH: lanes that must be able to make
 // progress for a scheduler phase to run (-D: A/B libraries).  A phase carries the whole sweep whatever its width, so it pays to
 // wait for a fuller one than the tree kernel's 40: cbox 640x480x64 at 1.669 / 1.649 / 1.693 ms per frame with 40 / 48 / 56, and
@@ -382,9 +384,10 @@ __global__ __launch_bounds__(kBlock, (kBlock > 256 ? 1 : MINW)) void trace_kerne
 #define PT_SWEEP_THRESH 48
 #endif
 struct SweepLayoutDev {
-    const unsigned char* tab;       // box tables, then slot records (build_sweep_layout), global memory
+    const unsigned char* tab;       // box tables in class order (build_sweep_pair_tables), then slot records (build_sweep_layout), global memory
     uint32_t groups;                // 1 .. kSweepMaxBoxes
-    uint32_t pad;
+    uint32_t box_pitch;             // sweep_pairs_pitch(classes)
+    SweepPairClasses classes;       // pairs per class of the sweep loop (pt_sweep_pairs.h), scalars
 };
 struct SweepKernelArgs {
     SceneDev scn; RenderDev rp; LdsPlan lp; float4* samples; uint32_t* work_counter; unsigned long long* counters; SweepLayoutDev sweep;
@@ -425,7 +428,7 @@ __device__ __forceinline__ ptd::SceneView make_sweep_view(const SceneDev& scn, c
     sv.materials = reinterpret_cast<const DMaterial*>(smem + lp.mats_off);
     sv.emission = reinterpret_cast<const DEmission*>(smem + lp.emis_off);
     sv.node_stride = kLdsNodeStride;
-    sv.oct_stride = sweep_box_pitch(sweep.groups);
+    sv.oct_stride = sweep.box_pitch;
     sv.lights = scn.lights;
     sv.num_emission = scn.num_emission;
     sv.root_ref = scn.root_ref;
@@ -433,6 +436,41 @@ __device__ __forceinline__ ptd::SceneView make_sweep_view(const SceneDev& scn, c
     sv.ref_nodes = scn.ref_nodes; sv.ref_path = scn.ref_path; sv.ref_anc = scn.ref_anc; sv.ref_levels = scn.ref_levels;
     sv.bg = ptm::mk(scn.bg[0], scn.bg[1], scn.bg[2]);
     return sv;
+}
+
+// The sweep loop over `count` pairs that share axis AX (pt_sweep_pairs.h: SHARE_a, or SHARE_FLAT_a with FLAT), reading the lane's
+// octant table from `bx` on and shifting two hit bits per pair into h; returns the pointer behind the class.  The box test is
+// visit_node<false, true>'s — tn = max(max(x, y), z) over the near products, tf = min(min(x, y), z) over the far ones, hit where
+// tf >= max(0, tn) — with the shared axis's products, the same v_sub_f32 and v_mul_f32 on the same operands, formed once for
+// both boxes (FLAT: one product is near and far).  The hit word and its s_nop are the general pair's (pt_trace_sweep_body.h).
+typedef float SweepF2 __attribute__((ext_vector_type(2)));
+typedef const __attribute__((address_space(3))) SweepF2* SweepLdsF2;
+template <int A> __device__ __forceinline__ float sweep_axis(const ptm::V3& v) { return A == 0 ? v.x : A == 1 ? v.y : v.z; }
+template <int AX, bool FLAT>
+__device__ __forceinline__ SweepLdsF2 sweep_shared_pairs(SweepLdsF2 bx, uint32_t count, const ptm::V3& o, const ptm::V3& inv, uint32_t& h) {
+    constexpr int B = AX == 0 ? 1 : 0, C = AX == 2 ? 1 : 2;
+    const float oa = sweep_axis<AX>(o), ia = sweep_axis<AX>(inv), ob = sweep_axis<B>(o), ib = sweep_axis<B>(inv), oc = sweep_axis<C>(o), ic = sweep_axis<C>(inv);
+#pragma clang loop vectorize(disable) interleave(disable) unroll(disable)
+    for (uint32_t k = count; k != 0; k--) {
+        const SweepF2 s = bx[0], an = bx[1], af = bx[2], bn = bx[3], bf = bx[4];
+        bx += 5;
+        float na[3], fa[3], nb[3], fb[3];
+        na[AX] = (s.x - oa) * ia;
+        fa[AX] = FLAT ? na[AX] : (s.y - oa) * ia;
+        nb[AX] = na[AX]; fb[AX] = fa[AX];
+        na[B] = (an.x - ob) * ib; na[C] = (an.y - oc) * ic; fa[B] = (af.x - ob) * ib; fa[C] = (af.y - oc) * ic;
+        nb[B] = (bn.x - ob) * ib; nb[C] = (bn.y - oc) * ic; fb[B] = (bf.x - ob) * ib; fb[C] = (bf.y - oc) * ic;
+        const float tfa = ptm::fmin2(ptm::fmin2(fa[0], fa[1]), fa[2]), tna = ptm::fmax2(0.0f, ptm::fmax2(ptm::fmax2(na[0], na[1]), na[2]));
+        const float tfb = ptm::fmin2(ptm::fmin2(fb[0], fb[1]), fb[2]), tnb = ptm::fmax2(0.0f, ptm::fmax2(ptm::fmax2(nb[0], nb[1]), nb[2]));
+        unsigned long long mb;
+        asm("v_cmp_ge_f32_e32 vcc, %2, %3\n\t"
+            "v_cmp_ge_f32_e64 %1, %4, %5\n\t"
+            "s_nop 0\n\t"
+            "v_addc_co_u32_e32 %0, vcc, %0, %0, vcc\n\t"
+            "v_addc_co_u32_e64 %0, vcc, %0, %0, %1"
+            : "+v"(h), "=&s"(mb) : "v"(tfa), "v"(tna), "v"(tfb), "v"(tnb) : "vcc");
+    }
+    return bx;
 }
 
 template <int MINW>

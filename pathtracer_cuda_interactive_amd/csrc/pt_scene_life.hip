@@ -17,6 +17,7 @@
 #include "pt_scene_transform.h"
 #include "pt_transform.h"
 #include "pt_sweep_layout.h"
+#include "pt_sweep_pairs.h"
 
 namespace {
 using namespace ptkc;
@@ -366,18 +367,33 @@ bool probe_wins(const unsigned long long v[2]) { return v[1] * 100ull < v[0] * 9
 
 // The leaf sweep's groups of equal leaf boxes (pt_leaf_sweep.h) and its tables (pt_sweep_layout.h) from an internal tree as the
 // host built it; prims: the N <= kSweepMaxPrims records on the host.  groups = 0: none; sweep.count stays 0 where a launch
-// would not admit them.
-int make_sweep_tables(const TreeHost& fast, const DPrim* prims, int N, SweepTable& sweep, int& sweep_groups, DevBuf<unsigned char>& sweep_tab) {
+// would not admit them.  The tables are made twice: in the groups' own order with every pair general (sweep_tab), and in the
+// pair-class order of pt_sweep_pairs.h (sweep_tab_pairs, classes), which option "sweep_pairs" chooses between at a launch.
+int make_sweep_tables(const TreeHost& fast, const DPrim* prims, int N, SweepTable& sweep, int& sweep_groups, DevBuf<unsigned char>& sweep_tab,
+                      DevBuf<unsigned char>& sweep_tab_pairs, SweepPairClasses& classes) {
     sweep = SweepTable{};
     sweep_groups = 0;
+    classes = SweepPairClasses{};
     SweepGroup groups[kSweepMaxPrims];
     const int n = build_sweep_groups(fast.nodes.data(), (int)fast.nodes.size(), N, kLdsNodeStride, groups);
     if (n > 0) {
         sweep_groups = n;
         std::vector<unsigned char> tab(n <= kSweepMaxBoxes ? sweep_layout_bytes((uint32_t)n, (uint32_t)N) : 0);
-        if (n <= kSweepMaxBoxes && build_sweep_layout(groups, n, fast.nodes.data(), (int)fast.nodes.size(), kLdsNodeStride, prims, N, tab.data())) {
+        SweepGroup paired[kSweepMaxBoxes];
+        int perm[kSweepMaxBoxes];
+        SweepPairClasses cls{};
+        std::vector<unsigned char> tab_pairs(tab.size());
+        const DNode* nodes = fast.nodes.data();
+        const int num_nodes = (int)fast.nodes.size();
+        if (n <= kSweepMaxBoxes && build_sweep_layout(groups, n, nodes, num_nodes, kLdsNodeStride, prims, N, tab.data()) &&
+            build_sweep_pairs(groups, n, nodes, num_nodes, kLdsNodeStride, paired, perm, &cls) &&
+            build_sweep_layout(paired, n, nodes, num_nodes, kLdsNodeStride, prims, N, tab_pairs.data()) &&
+            build_sweep_pair_tables(paired, n, cls, nodes, num_nodes, kLdsNodeStride, tab_pairs.data())) {
             if (int rc = sweep_tab.ensure(tab.size())) return rc;
+            if (int rc = sweep_tab_pairs.ensure(tab_pairs.size())) return rc;
             HIP_TRY(hipMemcpy(sweep_tab.p, tab.data(), tab.size(), hipMemcpyHostToDevice));
+            HIP_TRY(hipMemcpy(sweep_tab_pairs.p, tab_pairs.data(), tab_pairs.size(), hipMemcpyHostToDevice));
+            classes = cls;
             sweep.count = (uint32_t)n;
             std::copy(groups, groups + n, sweep.g);
         }
@@ -592,7 +608,7 @@ int validate_and_build(const pt_scene_desc* d, pt_scene* S) {
     // 8: the leaf sweep's groups of equal leaf boxes (pt_leaf_sweep.h), from the internal tree as the host built it
     S->sweep = SweepTable{}; S->sweep_groups = 0;
     if (S->have_fast && !c.cand.on_device && !S->fast_is_callers_topology && N <= kSweepMaxPrims &&
-        (rc = make_sweep_tables(c.cand.host, c.prims.data(), N, S->sweep, S->sweep_groups, S->sweep_tab)))
+        (rc = make_sweep_tables(c.cand.host, c.prims.data(), N, S->sweep, S->sweep_groups, S->sweep_tab, S->sweep_tab_pairs, S->sweep_classes)))
         return rc;
     // complete from here on: trace kernels run on the handle's own streams (FrameSlot), which do not synchronise with this one
     HIP_TRY(hipDeviceSynchronize());
@@ -694,6 +710,7 @@ int adopt_staged(pt_scene* S, const char* who, bool tri_only, int64_t* us_plan, 
     S->tri_only = tri_only;
     S->sweep_groups = 0; S->sweep.count = 0;     // leaf boxes that were equal need not be any more: back to the tree
     S->sweep_tab.release();                      // (no frame is in flight: the update synchronised before it wrote)
+    S->sweep_tab_pairs.release(); S->sweep_classes = SweepPairClasses{};
     *us_refit = clock.lap();
     return PT_OK;
 }
@@ -735,7 +752,7 @@ int rebuild_scene(pt_scene* S) {
     // ---- what goes with an adopted tree: its refit plan where the handle has refitted before (the next update does not pay for
     // it), the box sweep of a small scene under create's admission rules, its cost where telemetry is on
     ptf::Plan plan;
-    SweepTable sweep{}; int sweep_groups = 0; DevBuf<unsigned char> sweep_tab;
+    SweepTable sweep{}; int sweep_groups = 0; DevBuf<unsigned char> sweep_tab, sweep_tab_pairs; SweepPairClasses sweep_classes{};
     double cost = 0.0;
     if (adopt) {
         if (S->refit_plan[1].built && (rc = ptf::plan_build(cand.tree.nodes.p, cand.tree.num_nodes, N, &plan))) return rc;
@@ -743,7 +760,7 @@ int rebuild_scene(pt_scene* S) {
         if (!cand.on_device && N <= kSweepMaxPrims) {
             std::vector<DPrim> prims((size_t)N);
             HIP_TRY(hipMemcpy(prims.data(), S->prims.p, prims.size() * sizeof(DPrim), hipMemcpyDeviceToHost));
-            if ((rc = make_sweep_tables(cand.host, prims.data(), N, sweep, sweep_groups, sweep_tab))) return rc;
+            if ((rc = make_sweep_tables(cand.host, prims.data(), N, sweep, sweep_groups, sweep_tab, sweep_tab_pairs, sweep_classes))) return rc;
         }
         if (S->cost_on()) {
             if ((rc = ensure_cost(S)) || (rc = enqueue_cost(S, cand.tree, 3))) return rc;
@@ -759,6 +776,7 @@ int rebuild_scene(pt_scene* S) {
         plan_guard.p = &plan;
         S->sweep = sweep; S->sweep_groups = sweep_groups;
         S->sweep_tab.swap(sweep_tab);
+        S->sweep_tab_pairs.swap(sweep_tab_pairs); S->sweep_classes = sweep_classes;
         S->cfg_fn = S->q_cfg_fn = nullptr;            // stack and LDS needs follow the tree: the next launch asks again
         if (S->cost_on()) { S->cost_ref[1] = S->cost_now[1] = cost; S->cost_have_ref[1] = true; }
     } else if (S->cost_have_ref[1] && S->cost_now[1] > 0.0) {

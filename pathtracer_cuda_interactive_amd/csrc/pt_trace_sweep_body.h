@@ -13,8 +13,9 @@
     typedef const __attribute__((address_space(3))) unsigned char* LdsBytes;
     typedef float f2v __attribute__((ext_vector_type(2)));
     typedef const __attribute__((address_space(3))) f2v* LdsF2;
-    const uint32_t n_groups = sweep.groups;                        // 1 .. kSweepMaxBoxes, the loop's only scalar input
-    const uint32_t box_pitch = sweep_box_pitch(n_groups);
+    const uint32_t n_groups = sweep.groups;                        // 1 .. kSweepMaxBoxes
+    const uint32_t box_pitch = sweep.box_pitch;
+    const uint64_t cls_bits = __builtin_bit_cast(uint64_t, sweep.classes);    // the sweep loops' trip counts, a byte each, in two scalars
     const ptd::SceneView sv = make_sweep_view(scn, lp, sweep, smem);
     const ptd::lds_f4v* slots = (const ptd::lds_f4v*)(smem + lp.nodes_off + sweep_slots_off(n_groups));
 
@@ -147,9 +148,26 @@
                     // and nothing inserts them inside an asm statement: a pair interleaves its two compares and adds and needs
                     // one s_nop, the odd group alone waits two.
                     uint32_t h = 0;
+                    // the pairs that share an axis interval come first, class by class (pt_sweep_pairs.h): the shared axis's
+                    // products once per pair, records of 10 floats; a class the scene does not have costs its scalar branch.
+                    // The counts are taken out of their two words HERE, by scalar instructions: the empty statement keeps the
+                    // compiler from holding eight counts and eight "is zero" masks in scalar registers across the main loop,
+                    // which it has not got (they overflowed into the lanes of a vector register, one more than the kernel has).
+                    uint32_t cls_lo = (uint32_t)cls_bits, cls_hi = (uint32_t)(cls_bits >> 32);
+                    asm volatile("" : "+s"(cls_lo), "+s"(cls_hi));
+                    SweepPairClasses cls;
+                    cls.flat[0] = (uint8_t)cls_lo; cls.flat[1] = (uint8_t)(cls_lo >> 8); cls.flat[2] = (uint8_t)(cls_lo >> 16);
+                    cls.share[0] = (uint8_t)(cls_lo >> 24); cls.share[1] = (uint8_t)cls_hi; cls.share[2] = (uint8_t)(cls_hi >> 8);
+                    cls.general = (uint8_t)(cls_hi >> 16); cls.single = (uint8_t)(cls_hi >> 24);
+                    bx = sweep_shared_pairs<0, true>(bx, cls.flat[0], o, inv, h);
+                    bx = sweep_shared_pairs<1, true>(bx, cls.flat[1], o, inv, h);
+                    bx = sweep_shared_pairs<2, true>(bx, cls.flat[2], o, inv, h);
+                    bx = sweep_shared_pairs<0, false>(bx, cls.share[0], o, inv, h);
+                    bx = sweep_shared_pairs<1, false>(bx, cls.share[1], o, inv, h);
+                    bx = sweep_shared_pairs<2, false>(bx, cls.share[2], o, inv, h);
                     // (the loop vectoriser would pair the groups up into packed fp32, which issues at half rate)
 #pragma clang loop vectorize(disable) interleave(disable) unroll(disable)
-                    for (uint32_t k = n_groups >> 1; k != 0; k--) {
+                    for (uint32_t k = cls.general; k != 0; k--) {
                         const f2v a0 = bx[0], a1 = bx[1], a2 = bx[2], b0 = bx[3], b1 = bx[4], b2 = bx[5];
                         bx += 6;
                         float tfa, tna, tfb, tnb;
@@ -163,7 +181,7 @@
                             "v_addc_co_u32_e64 %0, vcc, %0, %0, %1"
                             : "+v"(h), "=&s"(mb) : "v"(tfa), "v"(tna), "v"(tfb), "v"(tnb) : "vcc");
                     }
-                    if (n_groups & 1u) {                                                // an odd count: the last group alone
+                    if (cls.single) {                                             // an odd count: the last group alone
                         float tf, tn0;
                         box_sides(bx[0], bx[1], bx[2], tf, tn0);
                         asm("v_cmp_ge_f32_e32 vcc, %1, %2\n\ts_nop 1\n\tv_addc_co_u32_e32 %0, vcc, %0, %0, vcc" : "+v"(h) : "v"(tf), "v"(tn0) : "vcc");

@@ -780,6 +780,16 @@ int pt_bvh_build_sweep_device(const pt_scene_desc* desc, pt_bvh_node* out_nodes,
  *                   computed in full.  The same operations on the same operands either way: the same bits.  Info
  *                   "sweep_share_pairs", "sweep_flat_pairs" (each also with _x, _y, _z for one axis) and "sweep_general_pairs"
  *                   report the pairs of each kind a sweep launch of the handle runs under the option as it stands.
+ *   "sweep_families" under "sweep_pairs" 1: 1 (default) one more kind of record stands in front of the pairs
+ *                   (csrc/pt_sweep_families.h): PAIR2, two groups with the same interval on TWO axes (each of them flat or
+ *                   not), both axes computed once.  Which groups go into which record is chosen at pt_scene_create (and
+ *                   again by pt_scene_rebuild) so that a count of the sweep's vector instructions is smallest; never above
+ *                   the count of the pairs alone.  0 = the pairs alone, exactly as before the records existed (A/B runs,
+ *                   tests).  The same bits under either value.  Info "sweep_pair2_records" reports the records of a sweep
+ *                   launch under the options as they stand, and "sweep_valu_model" that count (general pair 35, pair
+ *                   sharing an axis 31, flat 29, single 17, PAIR2 27 / 25 / 23 with 0 / 1 / 2 flat axes).  In
+ *                   "sweep_share_pairs" and "sweep_flat_pairs" a PAIR2 counts as one pair (flat where one of its axes is);
+ *                   with _x, _y, _z it counts under each of the two axes it shares.
  *   "octants"       1 (default) keep 8 ray-octant node tables in LDS for very small scenes, 0 = one table
  *   "fast_tree"     1 (default) traversal (exact and pruned) on the library's INTERNAL tree where pt_scene_create kept one,
  *                   0 = on the caller's tree.  Same image either way, bit for bit: the reference never prunes, so a leaf is tested iff the
@@ -835,6 +845,7 @@ int pt_bvh_build_sweep_device(const pt_scene_desc* desc, pt_bvh_node* out_nodes,
  * "reg_stack" (1 = that kernel kept its traversal stack in a register, see option "reg_stack"; "lds_bytes" of such a launch has no
  * stack columns), "leaf_sweep" (1 = that kernel found its leaves by the box sweep, see option "leaf_sweep"), "sweep_boxes",
  * "sweep_share_pairs", "sweep_flat_pairs", "sweep_general_pairs" (see option "sweep_pairs"),
+ * "sweep_pair2_records", "sweep_valu_model" (see option "sweep_families"),
  * "frames_in_flight", "sweep_on_device" (the internal tree was built on the GPU), "query_chunk" (ray indices a wave of the query
  * kernel reserves per atomic), "query_grid" (blocks of the last query launch), "query_guides" (the last pt_render_guides_async
  * ran on the refilling kernel: 1, or the one-shot kernel: 0),

@@ -377,12 +377,11 @@ void launch_trace(const pt_scene* S, const TraceChoice& c, const TraceEntry& e, 
         hipLaunchKernelGGL(reinterpret_cast<TraceFnQ>(fn), dim3(grid), dim3(c.block_threads), lp.total, stream, S->dev, rd, lp, qp,
                            samples, S->work_counter(), S->counters());
     else if (c.sweep) {
-        // option "sweep_pairs": the tables in pair-class order, or in the groups' own order with every pair general
-        const bool pairs = S->opt_sweep_pairs && S->sweep_tab_pairs.p;
-        const SweepPairClasses cls = pairs ? S->sweep_classes : sweep_pairs_none(S->sweep.count);
+        // options "sweep_pairs", "sweep_families": the tables in class order, or in the groups' own order with every pair general
+        const SweepClasses cls = S->sweep_classes_now();
         hipLaunchKernelGGL(reinterpret_cast<SweepFn>(fn), dim3(grid), dim3(c.block_threads), lp.total, stream, S->dev, rd, lp,
                            samples, S->work_counter(), S->counters(),
-                           SweepLayoutDev{pairs ? S->sweep_tab_pairs.p : S->sweep_tab.p, S->sweep.count, sweep_pairs_pitch(cls), cls});
+                           SweepLayoutDev{S->sweep_tab_now(), S->sweep.count, sweep_classes_pitch(cls), cls.pairs, cls.fam});
     } else
         hipLaunchKernelGGL(reinterpret_cast<TraceFn>(fn), dim3(grid), dim3(c.block_threads), lp.total, stream, S->dev, rd, lp,
                            samples, S->work_counter(), S->counters());
@@ -1748,6 +1747,7 @@ int pt_scene_set_option(pt_scene* S, const char* key, int64_t value) {
     else if (k == "reg_stack") { if (value != 0 && value != 1) return fail(PT_ERR_INVALID_ARG, "reg_stack must be 0 or 1"); S->opt_reg_stack = value; }
     else if (k == "leaf_sweep") { if (value != 0 && value != 1) return fail(PT_ERR_INVALID_ARG, "leaf_sweep must be 0 or 1"); S->opt_leaf_sweep = value; }
     else if (k == "sweep_pairs") { if (value != 0 && value != 1) return fail(PT_ERR_INVALID_ARG, "sweep_pairs must be 0 or 1"); S->opt_sweep_pairs = value; }
+    else if (k == "sweep_families") { if (value != 0 && value != 1) return fail(PT_ERR_INVALID_ARG, "sweep_families must be 0 or 1"); S->opt_sweep_families = value; }
     else if (k == "query_refill") { if (value < 0 || value > 64) return fail(PT_ERR_INVALID_ARG, "query_refill must be 0 (automatic) .. 64"); S->opt_query_refill = value; }
     else if (k == "query_guides") { if (value < 0 || value > 2) return fail(PT_ERR_INVALID_ARG, "query_guides must be 0 (automatic), 1 or 2"); S->opt_query_guides = value; }
     else if (k == "query_blocks") { if (value < 0 || value > 4096) return fail(PT_ERR_INVALID_ARG, "query_blocks must be 0 (automatic) .. 4096"); S->opt_query_blocks = value; }
@@ -1829,15 +1829,18 @@ int pt_scene_get_info(pt_scene* S, const char* key, int64_t* value) {
     else if (k == "leaf_sweep") *value = S->info_leaf_sweep;              // ... finding its leaves by the box sweep (1: trace_kernel_v2_sweep) or on the tree (0)
     else if (k == "sweep_boxes") *value = S->sweep_groups;                // groups of equal leaf boxes the handle holds for the sweep (0: none)
     else if (k.rfind("sweep_share_pairs", 0) == 0 || k.rfind("sweep_flat_pairs", 0) == 0 || k == "sweep_general_pairs") {
-        // the pair classes a sweep launch of this handle runs under the option "sweep_pairs" as it stands (pt_sweep_pairs.h); 0: no tables
-        const SweepPairClasses c = !S->sweep.count ? SweepPairClasses{} : S->opt_sweep_pairs && S->sweep_tab_pairs.p ? S->sweep_classes : sweep_pairs_none(S->sweep.count);
+        // the classes a sweep launch of this handle runs under the options "sweep_pairs" and "sweep_families" as they stand; 0: no tables.
+        // A PAIR2 is a pair that shares (pt_sweep_families.h: sweep_classes_sharing)
+        const SweepClasses c = S->sweep_classes_now();
         const bool flat = k[6] == 'f';
         const std::string axis = k.substr(flat ? 16 : 17);
-        if (k == "sweep_general_pairs") *value = c.general;
-        else if (axis.empty()) *value = flat ? sweep_pairs_flat(c) : sweep_pairs_shared(c);
-        else if (axis == "_x" || axis == "_y" || axis == "_z") *value = (flat ? c.flat : c.share)[axis[1] - 'x'];
+        if (k == "sweep_general_pairs") *value = c.pairs.general;
+        else if (axis.empty()) *value = sweep_classes_sharing(c, flat, -1);
+        else if (axis == "_x" || axis == "_y" || axis == "_z") *value = sweep_classes_sharing(c, flat, axis[1] - 'x');
         else return fail(PT_ERR_INVALID_ARG, "unknown info key " + k);
     }
+    else if (k == "sweep_pair2_records") *value = sweep_pair2_records(S->sweep_classes_now().fam);      // PAIR2 records of that launch
+    else if (k == "sweep_valu_model") *value = sweep_valu_model(S->sweep_classes_now());                // the count model's VALU of its sweep loops
     else if (k == "reg_stack") *value = S->info_reg_stack;                // ... with the traversal stack in a register (1) or in LDS / global memory (0)
     else if (k == "block_threads") *value = S->info_kernel == 3 ? kQBlock : kBlock;
     else if (k == "frames_in_flight") *value = S->opt_frames_in_flight;

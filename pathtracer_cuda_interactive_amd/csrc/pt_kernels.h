@@ -17,6 +17,7 @@
 #include "pt_path_bank.h"
 #include "pt_path_index.h"
 #include "pt_sweep_layout.h"
+#include "pt_sweep_families.h"
 #include "pt_sweep_pairs.h"
 #include "pt_temporal.h"
 #include "pt_trace.h"
@@ -386,8 +387,9 @@ __global__ __launch_bounds__(kBlock, (kBlock > 256 ? 1 : MINW)) void trace_kerne
 struct SweepLayoutDev {
     const unsigned char* tab;       // box tables in class order (build_sweep_pair_tables), then slot records (build_sweep_layout), global memory
     uint32_t groups;                // 1 .. kSweepMaxBoxes
-    uint32_t box_pitch;             // sweep_pairs_pitch(classes)
+    uint32_t box_pitch;             // sweep_classes_pitch of the two below
     SweepPairClasses classes;       // pairs per class of the sweep loop (pt_sweep_pairs.h), scalars
+    SweepFamilyClasses fam;         // records per PAIR2 class in front of them (pt_sweep_families.h), read from the kernel arguments inside the phase
 };
 struct SweepKernelArgs {
     SceneDev scn; RenderDev rp; LdsPlan lp; float4* samples; uint32_t* work_counter; unsigned long long* counters; SweepLayoutDev sweep;
@@ -469,6 +471,43 @@ __device__ __forceinline__ SweepLdsF2 sweep_shared_pairs(SweepLdsF2 bx, uint32_t
             "v_addc_co_u32_e32 %0, vcc, %0, %0, vcc\n\t"
             "v_addc_co_u32_e64 %0, vcc, %0, %0, %1"
             : "+v"(h), "=&s"(mb) : "v"(tfa), "v"(tna), "v"(tfb), "v"(tnb) : "vcc");
+    }
+    return bx;
+}
+
+// The two compares of a pair of boxes and the hit word's two adds with carry (pt_trace_sweep_body.h has the account of the s_nop).
+__device__ __forceinline__ void sweep_shift_in_two(uint32_t& h, float tfa, float tna, float tfb, float tnb) {
+    unsigned long long mb;
+    asm("v_cmp_ge_f32_e32 vcc, %2, %3\n\t"
+        "v_cmp_ge_f32_e64 %1, %4, %5\n\t"
+        "s_nop 0\n\t"
+        "v_addc_co_u32_e32 %0, vcc, %0, %0, vcc\n\t"
+        "v_addc_co_u32_e64 %0, vcc, %0, %0, %1"
+        : "+v"(h), "=&s"(mb) : "v"(tfa), "v"(tna), "v"(tfb), "v"(tnb) : "vcc");
+}
+
+// The sweep loop over `count` PAIR2 records (pt_sweep_families.h): two boxes with the same interval on both axes other than U,
+// FB / FC: the lower / upper of those is flat.  Each shared axis's products once for both boxes, a flat one's once in all; the
+// same v_sub_f32 and v_mul_f32 on the same operands as the general pair, minima and maxima in its axis order.
+template <int U, bool FB, bool FC>
+__device__ __forceinline__ SweepLdsF2 sweep_pair2(SweepLdsF2 bx, uint32_t count, const ptm::V3& o, const ptm::V3& inv, uint32_t& h) {
+    constexpr int B = U == 0 ? 1 : 0, C = U == 2 ? 1 : 2;
+    const float ou = sweep_axis<U>(o), iu = sweep_axis<U>(inv), ob = sweep_axis<B>(o), ib = sweep_axis<B>(inv), oc = sweep_axis<C>(o), ic = sweep_axis<C>(inv);
+#pragma clang loop vectorize(disable) interleave(disable) unroll(disable)
+    for (uint32_t k = count; k != 0; k--) {
+        const SweepF2 sb = bx[0], sc = bx[1], au = bx[2], bu = bx[3];
+        bx += 4;
+        float na[3], fa[3], nb[3], fb[3];
+        na[B] = (sb.x - ob) * ib;
+        fa[B] = FB ? na[B] : (sb.y - ob) * ib;
+        na[C] = (sc.x - oc) * ic;
+        fa[C] = FC ? na[C] : (sc.y - oc) * ic;
+        nb[B] = na[B]; fb[B] = fa[B]; nb[C] = na[C]; fb[C] = fa[C];
+        na[U] = (au.x - ou) * iu; fa[U] = (au.y - ou) * iu;
+        nb[U] = (bu.x - ou) * iu; fb[U] = (bu.y - ou) * iu;
+        const float tfa = ptm::fmin2(ptm::fmin2(fa[0], fa[1]), fa[2]), tna = ptm::fmax2(0.0f, ptm::fmax2(ptm::fmax2(na[0], na[1]), na[2]));
+        const float tfb = ptm::fmin2(ptm::fmin2(fb[0], fb[1]), fb[2]), tnb = ptm::fmax2(0.0f, ptm::fmax2(ptm::fmax2(nb[0], nb[1]), nb[2]));
+        sweep_shift_in_two(h, tfa, tna, tfb, tnb);
     }
     return bx;
 }

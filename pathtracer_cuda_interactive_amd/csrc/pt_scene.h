@@ -16,6 +16,7 @@
 #include "pt_internal.h"
 #include "pt_layout.h"
 #include "pt_leaf_sweep.h"
+#include "pt_sweep_families.h"
 #include "pt_sweep_pairs.h"
 #include "pt_scene_refit.h"
 
@@ -266,6 +267,7 @@ struct pt_scene {
     int64_t opt_reg_stack = 1;      // 1 = register traversal stack where it applies (choose_trace), 0 = always the LDS stack
     int64_t opt_leaf_sweep = 1;     // 1 = leaves found by the box sweep where it applies (choose_trace), 0 = always the tree
     int64_t opt_sweep_pairs = 1;    // 1 = the sweep's groups paired by shared axis intervals (pt_sweep_pairs.h), 0 = table order, every pair general
+    int64_t opt_sweep_families = 1; // under sweep_pairs 1: 1 = PAIR2 records in front of the pairs (pt_sweep_families.h), 0 = the pairs alone
     // the groups of equal leaf boxes of tree[1] (pt_leaf_sweep.h), made at scene creation where the tree was built on the host
     // and the scene has at most 64 primitives.  sweep_groups = 0: none (also after a geometry update: boxes that were equal need
     // not be any more); it may exceed what a launch admits, sweep.count then stays 0.
@@ -274,9 +276,16 @@ struct pt_scene {
     // what a sweep launch stages in place of the octant node tables (pt_sweep_layout.h: box tables, then slot records), made
     // and uploaded with sweep.count, dropped with it
     DevBuf<unsigned char> sweep_tab;
-    // the same of the groups in pair-class order (pt_sweep_pairs.h), which option "sweep_pairs" 1 launches; sweep_tab is option 0's
-    DevBuf<unsigned char> sweep_tab_pairs;
-    SweepPairClasses sweep_classes{};
+    // the same of the groups in class order, which option "sweep_pairs" 1 launches (sweep_tab is option 0's), one per value of
+    // option "sweep_families": [0] the pair classes alone (pt_sweep_pairs.h), [1] PAIR2 records in front (pt_sweep_families.h)
+    DevBuf<unsigned char> sweep_tab_pairs[2];
+    SweepClasses sweep_classes[2] = {};
+    // the classes a sweep launch runs under the options as they stand, and their table; all zero / null: no tables
+    SweepClasses sweep_classes_now() const {
+        if (!sweep.count) return SweepClasses{};
+        return opt_sweep_pairs && sweep_tab_pairs[opt_sweep_families].p ? sweep_classes[opt_sweep_families] : sweep_classes_of_pairs(sweep_pairs_none(sweep.count));
+    }
+    const unsigned char* sweep_tab_now() const { return opt_sweep_pairs && sweep_tab_pairs[opt_sweep_families].p ? sweep_tab_pairs[opt_sweep_families].p : sweep_tab.p; }
     // info of last launch
     // wall time of pt_scene_create's stages, microseconds: [0] total [1] primitive records [2] caller's tree checked and re-laid
     // [3] internal tree built [4] ... re-laid [5] uploads + probe [6] tie tables; built_on_device: the sweep ran on the GPU

@@ -17,6 +17,7 @@
 #include "pt_scene_transform.h"
 #include "pt_transform.h"
 #include "pt_sweep_layout.h"
+#include "pt_sweep_families.h"
 #include "pt_sweep_pairs.h"
 
 namespace {
@@ -368,12 +369,13 @@ bool probe_wins(const unsigned long long v[2]) { return v[1] * 100ull < v[0] * 9
 // The leaf sweep's groups of equal leaf boxes (pt_leaf_sweep.h) and its tables (pt_sweep_layout.h) from an internal tree as the
 // host built it; prims: the N <= kSweepMaxPrims records on the host.  groups = 0: none; sweep.count stays 0 where a launch
 // would not admit them.  The tables are made twice: in the groups' own order with every pair general (sweep_tab), and in the
-// pair-class order of pt_sweep_pairs.h (sweep_tab_pairs, classes), which option "sweep_pairs" chooses between at a launch.
+// class order (sweep_tab_pairs, classes), once per value of option "sweep_families" (pt_sweep_families.h; [0]: the pair classes
+// of pt_sweep_pairs.h alone); options "sweep_pairs" and "sweep_families" choose among them at a launch.
 int make_sweep_tables(const TreeHost& fast, const DPrim* prims, int N, SweepTable& sweep, int& sweep_groups, DevBuf<unsigned char>& sweep_tab,
-                      DevBuf<unsigned char>& sweep_tab_pairs, SweepPairClasses& classes) {
+                      DevBuf<unsigned char> (&sweep_tab_pairs)[2], SweepClasses (&classes)[2]) {
     sweep = SweepTable{};
     sweep_groups = 0;
-    classes = SweepPairClasses{};
+    for (SweepClasses& c : classes) c = SweepClasses{};
     SweepGroup groups[kSweepMaxPrims];
     const int n = build_sweep_groups(fast.nodes.data(), (int)fast.nodes.size(), N, kLdsNodeStride, groups);
     if (n > 0) {
@@ -381,19 +383,25 @@ int make_sweep_tables(const TreeHost& fast, const DPrim* prims, int N, SweepTabl
         std::vector<unsigned char> tab(n <= kSweepMaxBoxes ? sweep_layout_bytes((uint32_t)n, (uint32_t)N) : 0);
         SweepGroup paired[kSweepMaxBoxes];
         int perm[kSweepMaxBoxes];
-        SweepPairClasses cls{};
-        std::vector<unsigned char> tab_pairs(tab.size());
+        SweepClasses cls[2] = {};
+        std::vector<unsigned char> tab_pairs[2];
         const DNode* nodes = fast.nodes.data();
         const int num_nodes = (int)fast.nodes.size();
-        if (n <= kSweepMaxBoxes && build_sweep_layout(groups, n, nodes, num_nodes, kLdsNodeStride, prims, N, tab.data()) &&
-            build_sweep_pairs(groups, n, nodes, num_nodes, kLdsNodeStride, paired, perm, &cls) &&
-            build_sweep_layout(paired, n, nodes, num_nodes, kLdsNodeStride, prims, N, tab_pairs.data()) &&
-            build_sweep_pair_tables(paired, n, cls, nodes, num_nodes, kLdsNodeStride, tab_pairs.data())) {
+        bool ok = n <= kSweepMaxBoxes && build_sweep_layout(groups, n, nodes, num_nodes, kLdsNodeStride, prims, N, tab.data());
+        for (int m = 0; ok && m < 2; m++) {
+            tab_pairs[m].resize(tab.size());
+            ok = build_sweep_families(groups, n, nodes, num_nodes, kLdsNodeStride, m, paired, perm, &cls[m]) &&
+                 build_sweep_layout(paired, n, nodes, num_nodes, kLdsNodeStride, prims, N, tab_pairs[m].data()) &&
+                 build_sweep_family_tables(paired, n, cls[m], nodes, num_nodes, kLdsNodeStride, tab_pairs[m].data());
+        }
+        if (ok) {
             if (int rc = sweep_tab.ensure(tab.size())) return rc;
-            if (int rc = sweep_tab_pairs.ensure(tab_pairs.size())) return rc;
             HIP_TRY(hipMemcpy(sweep_tab.p, tab.data(), tab.size(), hipMemcpyHostToDevice));
-            HIP_TRY(hipMemcpy(sweep_tab_pairs.p, tab_pairs.data(), tab_pairs.size(), hipMemcpyHostToDevice));
-            classes = cls;
+            for (int m = 0; m < 2; m++) {
+                if (int rc = sweep_tab_pairs[m].ensure(tab_pairs[m].size())) return rc;
+                HIP_TRY(hipMemcpy(sweep_tab_pairs[m].p, tab_pairs[m].data(), tab_pairs[m].size(), hipMemcpyHostToDevice));
+                classes[m] = cls[m];
+            }
             sweep.count = (uint32_t)n;
             std::copy(groups, groups + n, sweep.g);
         }
@@ -710,7 +718,7 @@ int adopt_staged(pt_scene* S, const char* who, bool tri_only, int64_t* us_plan, 
     S->tri_only = tri_only;
     S->sweep_groups = 0; S->sweep.count = 0;     // leaf boxes that were equal need not be any more: back to the tree
     S->sweep_tab.release();                      // (no frame is in flight: the update synchronised before it wrote)
-    S->sweep_tab_pairs.release(); S->sweep_classes = SweepPairClasses{};
+    for (int m = 0; m < 2; m++) { S->sweep_tab_pairs[m].release(); S->sweep_classes[m] = SweepClasses{}; }
     *us_refit = clock.lap();
     return PT_OK;
 }
@@ -752,7 +760,7 @@ int rebuild_scene(pt_scene* S) {
     // ---- what goes with an adopted tree: its refit plan where the handle has refitted before (the next update does not pay for
     // it), the box sweep of a small scene under create's admission rules, its cost where telemetry is on
     ptf::Plan plan;
-    SweepTable sweep{}; int sweep_groups = 0; DevBuf<unsigned char> sweep_tab, sweep_tab_pairs; SweepPairClasses sweep_classes{};
+    SweepTable sweep{}; int sweep_groups = 0; DevBuf<unsigned char> sweep_tab, sweep_tab_pairs[2]; SweepClasses sweep_classes[2] = {};
     double cost = 0.0;
     if (adopt) {
         if (S->refit_plan[1].built && (rc = ptf::plan_build(cand.tree.nodes.p, cand.tree.num_nodes, N, &plan))) return rc;
@@ -776,7 +784,7 @@ int rebuild_scene(pt_scene* S) {
         plan_guard.p = &plan;
         S->sweep = sweep; S->sweep_groups = sweep_groups;
         S->sweep_tab.swap(sweep_tab);
-        S->sweep_tab_pairs.swap(sweep_tab_pairs); S->sweep_classes = sweep_classes;
+        for (int m = 0; m < 2; m++) { S->sweep_tab_pairs[m].swap(sweep_tab_pairs[m]); S->sweep_classes[m] = sweep_classes[m]; }
         S->cfg_fn = S->q_cfg_fn = nullptr;            // stack and LDS needs follow the tree: the next launch asks again
         if (S->cost_on()) { S->cost_ref[1] = S->cost_now[1] = cost; S->cost_have_ref[1] = true; }
     } else if (S->cost_have_ref[1] && S->cost_now[1] > 0.0) {

@@ -159,6 +159,33 @@
                     cls.flat[0] = (uint8_t)cls_lo; cls.flat[1] = (uint8_t)(cls_lo >> 8); cls.flat[2] = (uint8_t)(cls_lo >> 16);
                     cls.share[0] = (uint8_t)(cls_lo >> 24); cls.share[1] = (uint8_t)cls_hi; cls.share[2] = (uint8_t)(cls_hi >> 8);
                     cls.general = (uint8_t)(cls_hi >> 16); cls.single = (uint8_t)(cls_hi >> 24);
+                    // the PAIR2 records in front of them (pt_sweep_families.h): their counts are read from the kernel's arguments here, a
+                    // word for four classes, so that they hold no register across the main loop; a word of zeros is one branch
+                    {
+                        typedef const __attribute__((address_space(4))) uint32_t* KernargWords;
+                        KernargWords fw = (KernargWords)((const __attribute__((address_space(4))) unsigned char*)__builtin_amdgcn_kernarg_segment_ptr() +
+                                                         offsetof(SweepKernelArgs, sweep) + offsetof(SweepLayoutDev, fam));
+                        asm volatile("" : "+s"(fw));
+                        const uint32_t f0 = fw[0], f1 = fw[1], f2 = fw[2];
+                        if (f0) {
+                            bx = sweep_pair2<0, false, false>(bx, f0 & 0xffu, o, inv, h);
+                            bx = sweep_pair2<0, true, false>(bx, (f0 >> 8) & 0xffu, o, inv, h);
+                            bx = sweep_pair2<0, false, true>(bx, (f0 >> 16) & 0xffu, o, inv, h);
+                            bx = sweep_pair2<0, true, true>(bx, f0 >> 24, o, inv, h);
+                        }
+                        if (f1) {
+                            bx = sweep_pair2<1, false, false>(bx, f1 & 0xffu, o, inv, h);
+                            bx = sweep_pair2<1, true, false>(bx, (f1 >> 8) & 0xffu, o, inv, h);
+                            bx = sweep_pair2<1, false, true>(bx, (f1 >> 16) & 0xffu, o, inv, h);
+                            bx = sweep_pair2<1, true, true>(bx, f1 >> 24, o, inv, h);
+                        }
+                        if (f2) {
+                            bx = sweep_pair2<2, false, false>(bx, f2 & 0xffu, o, inv, h);
+                            bx = sweep_pair2<2, true, false>(bx, (f2 >> 8) & 0xffu, o, inv, h);
+                            bx = sweep_pair2<2, false, true>(bx, (f2 >> 16) & 0xffu, o, inv, h);
+                            bx = sweep_pair2<2, true, true>(bx, f2 >> 24, o, inv, h);
+                        }
+                    }
                     bx = sweep_shared_pairs<0, true>(bx, cls.flat[0], o, inv, h);
                     bx = sweep_shared_pairs<1, true>(bx, cls.flat[1], o, inv, h);
                     bx = sweep_shared_pairs<2, true>(bx, cls.flat[2], o, inv, h);

@@ -395,6 +395,7 @@ struct SweepKernelArgs {
     SceneDev scn; RenderDev rp; LdsPlan lp; float4* samples; uint32_t* work_counter; unsigned long long* counters; SweepLayoutDev sweep;
 };
 static_assert(offsetof(SweepKernelArgs, rp) == offsetof(TraceKernelArgs, rp), "reload_render_args reads rp at TraceKernelArgs' offset");
+static_assert(offsetof(SweepLayoutDev, fam) + 16 <= sizeof(SweepLayoutDev), "step (3) reads the three PAIR2 count words as one load of four: the fourth must lie inside the argument");
 
 // make_scene_view<2> for the sweep kernel: the node region of the plan takes the box tables as they are and the slot records
 // with their edges made here (sweep_stage_record); prims, normals, materials and emission are staged where every kernel has
@@ -440,40 +441,34 @@ __device__ __forceinline__ ptd::SceneView make_sweep_view(const SceneDev& scn, c
     return sv;
 }
 
-// The sweep loop over `count` pairs that share axis AX (pt_sweep_pairs.h: SHARE_a, or SHARE_FLAT_a with FLAT), reading the lane's
-// octant table from `bx` on and shifting two hit bits per pair into h; returns the pointer behind the class.  The box test is
-// visit_node<false, true>'s — tn = max(max(x, y), z) over the near products, tf = min(min(x, y), z) over the far ones, hit where
-// tf >= max(0, tn) — with the shared axis's products, the same v_sub_f32 and v_mul_f32 on the same operands, formed once for
-// both boxes (FLAT: one product is near and far).  The hit word and its s_nop are the general pair's (pt_trace_sweep_body.h).
+// The sweep's record stream (step (3) of pt_trace_sweep_body.h).  An octant's table is ONE run of records in class order, so at
+// every point "the next 32 bytes at bx" are the first four 8-byte pairs of whichever record comes next, of whatever class:
+// PAIR2's whole record, a sharing pair's first four pairs of five, a general pair's first four of six, the single's three and
+// one more.  Those four pairs are the WINDOW: eight registers, one instance of them live across all class loops.  A body
+//   - forms all its differences out of the window (and out of its tail, below) into other registers,
+//   - then reads the 32 bytes behind its own record into the window,
+//   - then does its multiplies, minima and maxima, compares and the hit word,
+// so the next record's LDS round trip runs under this record's arithmetic, across a loop's exit as well as inside it, and the
+// wait in front of a turn's first v_sub_f32 is for reads the body before it issued.  The TAIL of a record is what the window
+// does not hold (a sharing pair's 5th pair, a general pair's 5th and 6th): the body reads it itself at entry, in front of the
+// window's differences, and takes its differences last.  An empty class is skipped and the window stays what it is: the bytes
+// at bx.  The body that runs last reads 32 bytes it does not use: sweep_stream_end (pt_sweep_families.h) bounds them.
+// The scheduling barriers pin that order (left to itself the compiler computes in place and reads at the top of a turn);
+// they add no instruction.  No float operation differs from the loops without a window: v_sub_f32 then v_mul_f32 on the same
+// operands, minima and maxima in the same axis order.
 typedef float SweepF2 __attribute__((ext_vector_type(2)));
 typedef const __attribute__((address_space(3))) SweepF2* SweepLdsF2;
-template <int A> __device__ __forceinline__ float sweep_axis(const ptm::V3& v) { return A == 0 ? v.x : A == 1 ? v.y : v.z; }
-template <int AX, bool FLAT>
-__device__ __forceinline__ SweepLdsF2 sweep_shared_pairs(SweepLdsF2 bx, uint32_t count, const ptm::V3& o, const ptm::V3& inv, uint32_t& h) {
-    constexpr int B = AX == 0 ? 1 : 0, C = AX == 2 ? 1 : 2;
-    const float oa = sweep_axis<AX>(o), ia = sweep_axis<AX>(inv), ob = sweep_axis<B>(o), ib = sweep_axis<B>(inv), oc = sweep_axis<C>(o), ic = sweep_axis<C>(inv);
-#pragma clang loop vectorize(disable) interleave(disable) unroll(disable)
-    for (uint32_t k = count; k != 0; k--) {
-        const SweepF2 s = bx[0], an = bx[1], af = bx[2], bn = bx[3], bf = bx[4];
-        bx += 5;
-        float na[3], fa[3], nb[3], fb[3];
-        na[AX] = (s.x - oa) * ia;
-        fa[AX] = FLAT ? na[AX] : (s.y - oa) * ia;
-        nb[AX] = na[AX]; fb[AX] = fa[AX];
-        na[B] = (an.x - ob) * ib; na[C] = (an.y - oc) * ic; fa[B] = (af.x - ob) * ib; fa[C] = (af.y - oc) * ic;
-        nb[B] = (bn.x - ob) * ib; nb[C] = (bn.y - oc) * ic; fb[B] = (bf.x - ob) * ib; fb[C] = (bf.y - oc) * ic;
-        const float tfa = ptm::fmin2(ptm::fmin2(fa[0], fa[1]), fa[2]), tna = ptm::fmax2(0.0f, ptm::fmax2(ptm::fmax2(na[0], na[1]), na[2]));
-        const float tfb = ptm::fmin2(ptm::fmin2(fb[0], fb[1]), fb[2]), tnb = ptm::fmax2(0.0f, ptm::fmax2(ptm::fmax2(nb[0], nb[1]), nb[2]));
-        unsigned long long mb;
-        asm("v_cmp_ge_f32_e32 vcc, %2, %3\n\t"
-            "v_cmp_ge_f32_e64 %1, %4, %5\n\t"
-            "s_nop 0\n\t"
-            "v_addc_co_u32_e32 %0, vcc, %0, %0, vcc\n\t"
-            "v_addc_co_u32_e64 %0, vcc, %0, %0, %1"
-            : "+v"(h), "=&s"(mb) : "v"(tfa), "v"(tna), "v"(tfb), "v"(tnb) : "vcc");
-    }
-    return bx;
+struct SweepWindow { SweepF2 p0, p1, p2, p3; };
+// reads the window `pairs` 8-byte pairs behind bx and returns that pointer; the empty statement keeps the add behind the reads
+// (in front of them it takes a copy of the pointer)
+__device__ __forceinline__ SweepLdsF2 sweep_window_read(SweepWindow& w, SweepLdsF2 bx, int pairs) {
+    __builtin_amdgcn_sched_barrier(0);
+    w.p0 = bx[pairs]; w.p1 = bx[pairs + 1]; w.p2 = bx[pairs + 2]; w.p3 = bx[pairs + 3];
+    __builtin_amdgcn_sched_barrier(0);
+    asm volatile("" : "+v"(bx));
+    return bx + pairs;
 }
+template <int A> __device__ __forceinline__ float sweep_axis(const ptm::V3& v) { return A == 0 ? v.x : A == 1 ? v.y : v.z; }
 
 // The two compares of a pair of boxes and the hit word's two adds with carry (pt_trace_sweep_body.h has the account of the s_nop).
 __device__ __forceinline__ void sweep_shift_in_two(uint32_t& h, float tfa, float tna, float tfb, float tnb) {
@@ -486,25 +481,59 @@ __device__ __forceinline__ void sweep_shift_in_two(uint32_t& h, float tfa, float
         : "+v"(h), "=&s"(mb) : "v"(tfa), "v"(tna), "v"(tfb), "v"(tnb) : "vcc");
 }
 
+// The sweep loop over `count` pairs that share axis AX (pt_sweep_pairs.h: SHARE_a, or SHARE_FLAT_a with FLAT), the window `w`
+// holding the first four pairs of the record at `bx`; shifts two hit bits per pair into h and returns the pointer behind the
+// class, the window read there.  The box test is visit_node<false, true>'s — tn = max(max(x, y), z) over the near products,
+// tf = min(min(x, y), z) over the far ones, hit where tf >= max(0, tn) — with the shared axis's products, the same v_sub_f32
+// and v_mul_f32 on the same operands, formed once for both boxes (FLAT: one product is near and far).
+template <int AX, bool FLAT>
+__device__ __forceinline__ SweepLdsF2 sweep_shared_pairs(SweepLdsF2 bx, SweepWindow& w, uint32_t count, const ptm::V3& o, const ptm::V3& inv, uint32_t& h) {
+    constexpr int B = AX == 0 ? 1 : 0, C = AX == 2 ? 1 : 2;
+    const float oa = sweep_axis<AX>(o), ia = sweep_axis<AX>(inv), ob = sweep_axis<B>(o), ib = sweep_axis<B>(inv), oc = sweep_axis<C>(o), ic = sweep_axis<C>(inv);
+#pragma clang loop vectorize(disable) interleave(disable) unroll(disable)
+    for (uint32_t k = count; k != 0; k--) {
+        const SweepF2 bf = bx[4];                                   // the tail: B's far planes
+        __builtin_amdgcn_sched_barrier(0);
+        const float d_sn = w.p0.x - oa, d_sf = FLAT ? 0.0f : w.p0.y - oa;
+        const float d_anb = w.p1.x - ob, d_anc = w.p1.y - oc, d_afb = w.p2.x - ob, d_afc = w.p2.y - oc;
+        const float d_bnb = w.p3.x - ob, d_bnc = w.p3.y - oc;
+        const float d_bfb = bf.x - ob, d_bfc = bf.y - oc;
+        bx = sweep_window_read(w, bx, 5);
+        float na[3], fa[3], nb[3], fb[3];
+        na[AX] = d_sn * ia;
+        fa[AX] = FLAT ? na[AX] : d_sf * ia;
+        nb[AX] = na[AX]; fb[AX] = fa[AX];
+        na[B] = d_anb * ib; na[C] = d_anc * ic; fa[B] = d_afb * ib; fa[C] = d_afc * ic;
+        nb[B] = d_bnb * ib; nb[C] = d_bnc * ic; fb[B] = d_bfb * ib; fb[C] = d_bfc * ic;
+        const float tfa = ptm::fmin2(ptm::fmin2(fa[0], fa[1]), fa[2]), tna = ptm::fmax2(0.0f, ptm::fmax2(ptm::fmax2(na[0], na[1]), na[2]));
+        const float tfb = ptm::fmin2(ptm::fmin2(fb[0], fb[1]), fb[2]), tnb = ptm::fmax2(0.0f, ptm::fmax2(ptm::fmax2(nb[0], nb[1]), nb[2]));
+        sweep_shift_in_two(h, tfa, tna, tfb, tnb);
+    }
+    return bx;
+}
+
 // The sweep loop over `count` PAIR2 records (pt_sweep_families.h): two boxes with the same interval on both axes other than U,
 // FB / FC: the lower / upper of those is flat.  Each shared axis's products once for both boxes, a flat one's once in all; the
-// same v_sub_f32 and v_mul_f32 on the same operands as the general pair, minima and maxima in its axis order.
+// same v_sub_f32 and v_mul_f32 on the same operands as the general pair, minima and maxima in its axis order.  The record is
+// the window, no tail.
 template <int U, bool FB, bool FC>
-__device__ __forceinline__ SweepLdsF2 sweep_pair2(SweepLdsF2 bx, uint32_t count, const ptm::V3& o, const ptm::V3& inv, uint32_t& h) {
+__device__ __forceinline__ SweepLdsF2 sweep_pair2(SweepLdsF2 bx, SweepWindow& w, uint32_t count, const ptm::V3& o, const ptm::V3& inv, uint32_t& h) {
     constexpr int B = U == 0 ? 1 : 0, C = U == 2 ? 1 : 2;
     const float ou = sweep_axis<U>(o), iu = sweep_axis<U>(inv), ob = sweep_axis<B>(o), ib = sweep_axis<B>(inv), oc = sweep_axis<C>(o), ic = sweep_axis<C>(inv);
 #pragma clang loop vectorize(disable) interleave(disable) unroll(disable)
     for (uint32_t k = count; k != 0; k--) {
-        const SweepF2 sb = bx[0], sc = bx[1], au = bx[2], bu = bx[3];
-        bx += 4;
+        const float d_nb = w.p0.x - ob, d_fb = FB ? 0.0f : w.p0.y - ob;
+        const float d_nc = w.p1.x - oc, d_fc = FC ? 0.0f : w.p1.y - oc;
+        const float d_anu = w.p2.x - ou, d_afu = w.p2.y - ou, d_bnu = w.p3.x - ou, d_bfu = w.p3.y - ou;
+        bx = sweep_window_read(w, bx, 4);
         float na[3], fa[3], nb[3], fb[3];
-        na[B] = (sb.x - ob) * ib;
-        fa[B] = FB ? na[B] : (sb.y - ob) * ib;
-        na[C] = (sc.x - oc) * ic;
-        fa[C] = FC ? na[C] : (sc.y - oc) * ic;
+        na[B] = d_nb * ib;
+        fa[B] = FB ? na[B] : d_fb * ib;
+        na[C] = d_nc * ic;
+        fa[C] = FC ? na[C] : d_fc * ic;
         nb[B] = na[B]; fb[B] = fa[B]; nb[C] = na[C]; fb[C] = fa[C];
-        na[U] = (au.x - ou) * iu; fa[U] = (au.y - ou) * iu;
-        nb[U] = (bu.x - ou) * iu; fb[U] = (bu.y - ou) * iu;
+        na[U] = d_anu * iu; fa[U] = d_afu * iu;
+        nb[U] = d_bnu * iu; fb[U] = d_bfu * iu;
         const float tfa = ptm::fmin2(ptm::fmin2(fa[0], fa[1]), fa[2]), tna = ptm::fmax2(0.0f, ptm::fmax2(ptm::fmax2(na[0], na[1]), na[2]));
         const float tfb = ptm::fmin2(ptm::fmin2(fb[0], fb[1]), fb[2]), tnb = ptm::fmax2(0.0f, ptm::fmax2(ptm::fmax2(nb[0], nb[1]), nb[2]));
         sweep_shift_in_two(h, tfa, tna, tfb, tnb);

@@ -394,6 +394,12 @@ int make_sweep_tables(const TreeHost& fast, const DPrim* prims, int N, SweepTabl
                  build_sweep_layout(paired, n, nodes, num_nodes, kLdsNodeStride, prims, N, tab_pairs[m].data()) &&
                  build_sweep_family_tables(paired, n, cls[m], nodes, num_nodes, kLdsNodeStride, tab_pairs[m].data());
         }
+        // every table a launch can choose must hold the kernel's record stream, its read past the last record included
+        // (pt_sweep_families.h: sweep_stream_fits).  A table is at most its pitch long and a scene has a primitive, so the end
+        // is at most 32 bytes into the first slot record: a table that fails this is a bug in the layout, not a scene to decline
+        if (ok && !(sweep_stream_fits(sweep_classes_of_pairs(sweep_pairs_none((uint32_t)n)), (uint32_t)n, (uint32_t)N) &&
+                    sweep_stream_fits(cls[0], (uint32_t)n, (uint32_t)N) && sweep_stream_fits(cls[1], (uint32_t)n, (uint32_t)N)))
+            return pt_fail(PT_ERR_UNSUPPORTED, "sweep tables: the record stream would read past the staged sweep region");
         if (ok) {
             if (int rc = sweep_tab.ensure(tab.size())) return rc;
             HIP_TRY(hipMemcpy(sweep_tab.p, tab.data(), tab.size(), hipMemcpyHostToDevice));

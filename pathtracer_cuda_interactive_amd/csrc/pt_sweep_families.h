@@ -80,6 +80,22 @@ PT_SWEEP_HD uint32_t sweep_classes_pitch(const SweepClasses& c) {
                                  kSweepPairFloats * c.pairs.general + kSweepSingleFloats * c.pairs.single);
     return bytes + (((bytes / 8u) & 1u) ? 0u : 8u);
 }
+// The end of what the kernel's record stream reads (pt_kernels.h: SweepWindow), as an offset into the staged sweep region: one
+// past the furthest byte.  The stream reads a window of kSweepWindowBytes at the start of a table and behind every record but
+// the single, whether a record follows or not, so the furthest read is octant 7's, behind its last pair record: into the single
+// and 8 bytes past it, or 32 bytes past the table's records.  Those bytes are the table's padding and the head of the slot
+// records staged behind the tables (sweep_slots_off); nothing uses them.  sweep_stream_fits is the checked property.
+constexpr uint32_t kSweepWindowBytes = 32;
+PT_SWEEP_HD uint32_t sweep_stream_end(const SweepClasses& c) {
+    const uint32_t pair_bytes = 4u * (kSweepPair2Floats * sweep_pair2_records(c.fam) +
+                                      kSweepSharedPairFloats * (sweep_pairs_shared(c.pairs) + sweep_pairs_flat(c.pairs)) +
+                                      kSweepPairFloats * c.pairs.general);
+    return 7u * sweep_classes_pitch(c) + pair_bytes + kSweepWindowBytes;
+}
+// The stream stays inside the region a block stages for `groups` groups and `num_prims` slot records.
+PT_SWEEP_HD bool sweep_stream_fits(const SweepClasses& c, uint32_t groups, uint32_t num_prims) {
+    return sweep_stream_end(c) <= sweep_layout_bytes(groups, num_prims);
+}
 // The count model: VALU instructions of the sweep loops over these classes.
 PT_SWEEP_HD uint32_t sweep_valu_model(const SweepClasses& c) {
     uint32_t n = 0;

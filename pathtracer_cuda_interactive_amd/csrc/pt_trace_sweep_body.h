@@ -124,24 +124,35 @@
             // (3) start the next segment (scene.h:247-256): the box sweep
             n_segs += (uint32_t)__popcll(__ballot(idle && alive));
             if (idle && alive) {
+                // The record stream (pt_kernels.h: SweepWindow) starts here, in front of the reciprocals: the lane's octant is the
+                // sign bits of d — a lane that sweeps has a finite 1/d, whose sign is d's; a lane that does not takes the rerun
+                // and never reads h, and every octant's table is inside the staged region — so the first record's four pairs
+                // and the PAIR2 counts (one scalar load of the kernel's arguments, a word for four classes; they hold no scalar
+                // register outside this step) are under way while the three reciprocals are formed.  One wait behind them takes
+                // both: no scalar load is outstanding while the stream runs, so its waits can count LDS reads in order.
+                const uint32_t oct = (__builtin_bit_cast(uint32_t, ray.dir.x) >> 31) | ((__builtin_bit_cast(uint32_t, ray.dir.y) >> 31) << 1) |
+                                     ((__builtin_bit_cast(uint32_t, ray.dir.z) >> 31) << 2);
+                LdsF2 bx = (LdsF2)((LdsBytes)smem + lp.nodes_off + oct * box_pitch);
+                SweepWindow win;
+                bx = sweep_window_read(win, bx, 0);
+                typedef uint32_t FamWords __attribute__((ext_vector_type(4), aligned(4)));
+                typedef const volatile __attribute__((address_space(4))) FamWords* KernargFamWords;
+                KernargFamWords fw = (KernargFamWords)((const __attribute__((address_space(4))) unsigned char*)__builtin_amdgcn_kernarg_segment_ptr() +
+                                                       offsetof(SweepKernelArgs, sweep) + offsetof(SweepLayoutDev, fam));
+                asm volatile("" : "+s"(fw));
+                const FamWords fam = *fw;                              // three words and the struct's padding
+                uint32_t f0 = fam.x, f1 = fam.y, f2 = fam.z;
+                __builtin_amdgcn_sched_barrier(0);
                 const ptm::V3 inv = ptm::mk(ptm::rcp_exact(ray.dir.x), ptm::rcp_exact(ray.dir.y), ptm::rcp_exact(ray.dir.z));
+                asm volatile("" : "+s"(f0), "+s"(f1), "+s"(f2));
                 tv.best.t = FLT_MAX; tv.best.u = 0.0f; tv.best.v = 0.0f; tv.best.prim = -1;
                 // 1/d infinite on an axis: 0 * inf in the slab test is outside the argument that lets the leaf boxes alone decide
                 // (pt_scene_life.hip: validate_and_build) -> the reference-order rerun in the next phase, no candidates
                 tv.redo = !(__builtin_isfinite(inv.x) && __builtin_isfinite(inv.y) && __builtin_isfinite(inv.z));
                 if (!tv.redo) {
-                    // the lane's octant box table, in LDS's 32-bit address space, read front to back: two groups per
-                    // iteration, no table of offsets or masks, one hit bit per group shifted in (hits = 2 * hits + hit)
-                    const uint32_t oct = (inv.x < 0.0f ? 1u : 0u) | (inv.y < 0.0f ? 2u : 0u) | (inv.z < 0.0f ? 4u : 0u);
-                    LdsF2 bx = (LdsF2)((LdsBytes)smem + lp.nodes_off + oct * box_pitch);
+                    // the lane's octant box table, in LDS's 32-bit address space, read front to back through the window: two
+                    // groups per record, no table of offsets or masks, one hit bit per group shifted in (hits = 2 * hits + hit)
                     const ptm::V3 o = ray.org;
-                    // visit_node<false, true>: the same operations on the same operands (near.xy | near.z far.x | far.yz);
-                    // the two sides of the compare that decides a group: tf >= max(0, tn)
-                    auto box_sides = [&](const f2v p0, const f2v p1, const f2v p2, float& tf, float& tn0) {
-                        const float tn = ptm::fmax2(ptm::fmax2((p0.x - o.x) * inv.x, (p0.y - o.y) * inv.y), (p1.x - o.z) * inv.z);
-                        tf = ptm::fmin2(ptm::fmin2((p1.y - o.x) * inv.x, (p2.x - o.y) * inv.y), (p2.y - o.z) * inv.z);
-                        tn0 = ptm::fmax2(0.0f, tn);
-                    };
                     // h = 2 * h + hit as the compare and ONE add-with-carry, h + h + the compare's lane mask, where the compiler's
                     // own choice is a select per group and a shift and an or per pair (2.5 per group on top of the compare).
                     // gfx950 wants two wait states between a vector instruction that writes a lane mask and one that reads it,
@@ -159,58 +170,53 @@
                     cls.flat[0] = (uint8_t)cls_lo; cls.flat[1] = (uint8_t)(cls_lo >> 8); cls.flat[2] = (uint8_t)(cls_lo >> 16);
                     cls.share[0] = (uint8_t)(cls_lo >> 24); cls.share[1] = (uint8_t)cls_hi; cls.share[2] = (uint8_t)(cls_hi >> 8);
                     cls.general = (uint8_t)(cls_hi >> 16); cls.single = (uint8_t)(cls_hi >> 24);
-                    // the PAIR2 records in front of them (pt_sweep_families.h): their counts are read from the kernel's arguments here, a
-                    // word for four classes, so that they hold no register across the main loop; a word of zeros is one branch
-                    {
-                        typedef const __attribute__((address_space(4))) uint32_t* KernargWords;
-                        KernargWords fw = (KernargWords)((const __attribute__((address_space(4))) unsigned char*)__builtin_amdgcn_kernarg_segment_ptr() +
-                                                         offsetof(SweepKernelArgs, sweep) + offsetof(SweepLayoutDev, fam));
-                        asm volatile("" : "+s"(fw));
-                        const uint32_t f0 = fw[0], f1 = fw[1], f2 = fw[2];
-                        if (f0) {
-                            bx = sweep_pair2<0, false, false>(bx, f0 & 0xffu, o, inv, h);
-                            bx = sweep_pair2<0, true, false>(bx, (f0 >> 8) & 0xffu, o, inv, h);
-                            bx = sweep_pair2<0, false, true>(bx, (f0 >> 16) & 0xffu, o, inv, h);
-                            bx = sweep_pair2<0, true, true>(bx, f0 >> 24, o, inv, h);
-                        }
-                        if (f1) {
-                            bx = sweep_pair2<1, false, false>(bx, f1 & 0xffu, o, inv, h);
-                            bx = sweep_pair2<1, true, false>(bx, (f1 >> 8) & 0xffu, o, inv, h);
-                            bx = sweep_pair2<1, false, true>(bx, (f1 >> 16) & 0xffu, o, inv, h);
-                            bx = sweep_pair2<1, true, true>(bx, f1 >> 24, o, inv, h);
-                        }
-                        if (f2) {
-                            bx = sweep_pair2<2, false, false>(bx, f2 & 0xffu, o, inv, h);
-                            bx = sweep_pair2<2, true, false>(bx, (f2 >> 8) & 0xffu, o, inv, h);
-                            bx = sweep_pair2<2, false, true>(bx, (f2 >> 16) & 0xffu, o, inv, h);
-                            bx = sweep_pair2<2, true, true>(bx, f2 >> 24, o, inv, h);
-                        }
+                    // the PAIR2 records in front of them (pt_sweep_families.h); a word of zeros is one branch
+                    if (f0) {
+                        bx = sweep_pair2<0, false, false>(bx, win, f0 & 0xffu, o, inv, h);
+                        bx = sweep_pair2<0, true, false>(bx, win, (f0 >> 8) & 0xffu, o, inv, h);
+                        bx = sweep_pair2<0, false, true>(bx, win, (f0 >> 16) & 0xffu, o, inv, h);
+                        bx = sweep_pair2<0, true, true>(bx, win, f0 >> 24, o, inv, h);
                     }
-                    bx = sweep_shared_pairs<0, true>(bx, cls.flat[0], o, inv, h);
-                    bx = sweep_shared_pairs<1, true>(bx, cls.flat[1], o, inv, h);
-                    bx = sweep_shared_pairs<2, true>(bx, cls.flat[2], o, inv, h);
-                    bx = sweep_shared_pairs<0, false>(bx, cls.share[0], o, inv, h);
-                    bx = sweep_shared_pairs<1, false>(bx, cls.share[1], o, inv, h);
-                    bx = sweep_shared_pairs<2, false>(bx, cls.share[2], o, inv, h);
+                    if (f1) {
+                        bx = sweep_pair2<1, false, false>(bx, win, f1 & 0xffu, o, inv, h);
+                        bx = sweep_pair2<1, true, false>(bx, win, (f1 >> 8) & 0xffu, o, inv, h);
+                        bx = sweep_pair2<1, false, true>(bx, win, (f1 >> 16) & 0xffu, o, inv, h);
+                        bx = sweep_pair2<1, true, true>(bx, win, f1 >> 24, o, inv, h);
+                    }
+                    if (f2) {
+                        bx = sweep_pair2<2, false, false>(bx, win, f2 & 0xffu, o, inv, h);
+                        bx = sweep_pair2<2, true, false>(bx, win, (f2 >> 8) & 0xffu, o, inv, h);
+                        bx = sweep_pair2<2, false, true>(bx, win, (f2 >> 16) & 0xffu, o, inv, h);
+                        bx = sweep_pair2<2, true, true>(bx, win, f2 >> 24, o, inv, h);
+                    }
+                    bx = sweep_shared_pairs<0, true>(bx, win, cls.flat[0], o, inv, h);
+                    bx = sweep_shared_pairs<1, true>(bx, win, cls.flat[1], o, inv, h);
+                    bx = sweep_shared_pairs<2, true>(bx, win, cls.flat[2], o, inv, h);
+                    bx = sweep_shared_pairs<0, false>(bx, win, cls.share[0], o, inv, h);
+                    bx = sweep_shared_pairs<1, false>(bx, win, cls.share[1], o, inv, h);
+                    bx = sweep_shared_pairs<2, false>(bx, win, cls.share[2], o, inv, h);
+                    // the general pair, visit_node<false, true>: the same operations on the same operands (near.xy | near.z far.x |
+                    // far.yz per box); the window is box A and B's near.xy, the tail the rest of B
                     // (the loop vectoriser would pair the groups up into packed fp32, which issues at half rate)
 #pragma clang loop vectorize(disable) interleave(disable) unroll(disable)
                     for (uint32_t k = cls.general; k != 0; k--) {
-                        const f2v a0 = bx[0], a1 = bx[1], a2 = bx[2], b0 = bx[3], b1 = bx[4], b2 = bx[5];
-                        bx += 6;
-                        float tfa, tna, tfb, tnb;
-                        box_sides(a0, a1, a2, tfa, tna);
-                        box_sides(b0, b1, b2, tfb, tnb);
-                        unsigned long long mb;
-                        asm("v_cmp_ge_f32_e32 vcc, %2, %3\n\t"
-                            "v_cmp_ge_f32_e64 %1, %4, %5\n\t"
-                            "s_nop 0\n\t"
-                            "v_addc_co_u32_e32 %0, vcc, %0, %0, vcc\n\t"
-                            "v_addc_co_u32_e64 %0, vcc, %0, %0, %1"
-                            : "+v"(h), "=&s"(mb) : "v"(tfa), "v"(tna), "v"(tfb), "v"(tnb) : "vcc");
+                        const f2v b1 = bx[4], b2 = bx[5];
+                        __builtin_amdgcn_sched_barrier(0);
+                        const float d_anx = win.p0.x - o.x, d_any = win.p0.y - o.y, d_anz = win.p1.x - o.z;
+                        const float d_afx = win.p1.y - o.x, d_afy = win.p2.x - o.y, d_afz = win.p2.y - o.z;
+                        const float d_bnx = win.p3.x - o.x, d_bny = win.p3.y - o.y, d_bnz = b1.x - o.z;
+                        const float d_bfx = b1.y - o.x, d_bfy = b2.x - o.y, d_bfz = b2.y - o.z;
+                        bx = sweep_window_read(win, bx, 6);
+                        const float tna = ptm::fmax2(0.0f, ptm::fmax2(ptm::fmax2(d_anx * inv.x, d_any * inv.y), d_anz * inv.z));
+                        const float tfa = ptm::fmin2(ptm::fmin2(d_afx * inv.x, d_afy * inv.y), d_afz * inv.z);
+                        const float tnb = ptm::fmax2(0.0f, ptm::fmax2(ptm::fmax2(d_bnx * inv.x, d_bny * inv.y), d_bnz * inv.z));
+                        const float tfb = ptm::fmin2(ptm::fmin2(d_bfx * inv.x, d_bfy * inv.y), d_bfz * inv.z);
+                        sweep_shift_in_two(h, tfa, tna, tfb, tnb);
                     }
-                    if (cls.single) {                                             // an odd count: the last group alone
-                        float tf, tn0;
-                        box_sides(bx[0], bx[1], bx[2], tf, tn0);
+                    if (cls.single) {                                             // an odd count: the last group alone, three pairs of the window
+                        const float tn = ptm::fmax2(ptm::fmax2((win.p0.x - o.x) * inv.x, (win.p0.y - o.y) * inv.y), (win.p1.x - o.z) * inv.z);
+                        const float tf = ptm::fmin2(ptm::fmin2((win.p1.y - o.x) * inv.x, (win.p2.x - o.y) * inv.y), (win.p2.y - o.z) * inv.z);
+                        const float tn0 = ptm::fmax2(0.0f, tn);
                         asm("v_cmp_ge_f32_e32 vcc, %1, %2\n\ts_nop 1\n\tv_addc_co_u32_e32 %0, vcc, %0, %0, vcc" : "+v"(h) : "v"(tf), "v"(tn0) : "vcc");
                     }
                     hits = sweep_hits_align(h, n_groups);

@@ -293,8 +293,9 @@ int pt_transform_sphere_host(const pt_transform* t, const float* center, float r
  * caller's / the internal tree's cost after the last refit (0: no tree, nothing measured); "tree_cost0_permille" /
  * "tree_cost1_permille" = (int64)(1000.0 * now / reference + 0.5), the reference being the cost of the boxes as they stood
  * before the first refit after the option was set; 1000 before any refit.  An adopted rebuild makes the new tree's cost the
- * internal tree's reference, one that was not adopted makes the current cost the reference.  pt_host_tree_cost (pt_host.h) is
- * the host twin.  Option "rebuild_at_permille" (default 0 = never, else >= 1001; implies the telemetry): a successful
+ * internal tree's reference, one that was not adopted makes the current cost the reference.  Switching the telemetry off (both
+ * options 0) forgets its references and costs: switched on again it starts as on a new handle, the keys read 0 / 1000 and the
+ * next refit takes its references from the boxes as they stand then.  pt_host_tree_cost (pt_host.h) is the host twin.  Option "rebuild_at_permille" (default 0 = never, else >= 1001; implies the telemetry): a successful
  * pt_scene_update(PT_UPDATE_GEOMETRY) or pt_scene_transform whose "tree_cost1_permille" is at or above the value rebuilds inside
  * the same call, after the refit and before the closing synchronise ("update_us0" / "transform_us0" include it).  A rebuild that
  * fails there does not fail the update; "rebuilds_auto" counts the ones that succeeded. */

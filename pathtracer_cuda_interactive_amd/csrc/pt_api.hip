@@ -1751,10 +1751,12 @@ int pt_scene_set_option(pt_scene* S, const char* key, int64_t value) {
     else if (k == "query_refill") { if (value < 0 || value > 64) return fail(PT_ERR_INVALID_ARG, "query_refill must be 0 (automatic) .. 64"); S->opt_query_refill = value; }
     else if (k == "query_guides") { if (value < 0 || value > 2) return fail(PT_ERR_INVALID_ARG, "query_guides must be 0 (automatic), 1 or 2"); S->opt_query_guides = value; }
     else if (k == "query_blocks") { if (value < 0 || value > 4096) return fail(PT_ERR_INVALID_ARG, "query_blocks must be 0 (automatic) .. 4096"); S->opt_query_blocks = value; }
-    else if (k == "tree_cost") { if (value != 0 && value != 1) return fail(PT_ERR_INVALID_ARG, "tree_cost must be 0 or 1"); S->opt_tree_cost = value; }
-    else if (k == "rebuild_at_permille") {
-        if (value != 0 && value < 1001) return fail(PT_ERR_INVALID_ARG, "rebuild_at_permille must be 0 (never) or at least 1001");
-        S->opt_rebuild_at = value;
+    else if (k == "tree_cost" || k == "rebuild_at_permille") {
+        if (k == "tree_cost" && value != 0 && value != 1) return fail(PT_ERR_INVALID_ARG, "tree_cost must be 0 or 1");
+        if (k == "rebuild_at_permille" && value != 0 && value < 1001) return fail(PT_ERR_INVALID_ARG, "rebuild_at_permille must be 0 (never) or at least 1001");
+        const bool was_on = S->cost_on();
+        (k == "tree_cost" ? S->opt_tree_cost : S->opt_rebuild_at) = value;
+        if (!was_on && S->cost_on()) S->cost_forget();    // switched on: references are taken anew (include/pt_api.h)
     }
     else return fail(PT_ERR_INVALID_ARG, "unknown option " + k);
     return PT_OK;

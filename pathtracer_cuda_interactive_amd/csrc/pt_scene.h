@@ -161,6 +161,19 @@ struct pt_scene {
     double cost_ref[2] = {0.0, 0.0}, cost_now[2] = {0.0, 0.0};
     bool cost_have_ref[2] = {false, false}, cost_pending_ref[2] = {false, false}, cost_pending_now[2] = {false, false};
     bool cost_on() const { return opt_tree_cost != 0 || opt_rebuild_at != 0; }
+    // The telemetry starts afresh whenever it is switched on: what was measured before it went off belongs to boxes, perhaps to
+    // a tree, that refits and rebuilds without it have since replaced.
+    void cost_forget() {
+        for (int t = 0; t < 2; t++) {
+            cost_ref[t] = cost_now[t] = 0.0;
+            cost_have_ref[t] = false;
+        }
+        cost_drop_pending();
+    }
+    // A refused refit leaves the handle as it was: what it had enqueued is not collected by a later call.
+    void cost_drop_pending() {
+        for (int t = 0; t < 2; t++) cost_pending_ref[t] = cost_pending_now[t] = false;
+    }
     bool tri_only = false;           // the scene holds no sphere
     bool diffuse_only = false;       // every material is DIFFUSE
     // scratch

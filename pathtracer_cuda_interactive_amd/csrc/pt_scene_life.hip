@@ -793,7 +793,7 @@ int rebuild_scene(pt_scene* S) {
         for (int m = 0; m < 2; m++) { S->sweep_tab_pairs[m].swap(sweep_tab_pairs[m]); S->sweep_classes[m] = sweep_classes[m]; }
         S->cfg_fn = S->q_cfg_fn = nullptr;            // stack and LDS needs follow the tree: the next launch asks again
         if (S->cost_on()) { S->cost_ref[1] = S->cost_now[1] = cost; S->cost_have_ref[1] = true; }
-    } else if (S->cost_have_ref[1] && S->cost_now[1] > 0.0) {
+    } else if (S->cost_on() && S->cost_have_ref[1] && S->cost_now[1] > 0.0) {
         S->cost_ref[1] = S->cost_now[1];              // no better tree to be had of these boxes: a policy waits for the next drift
     }
     us[3] = clock.lap();
@@ -848,7 +848,7 @@ int update_scene(pt_scene* S, const pt_scene_desc* d, int flags) {
         if ((rc = ensure_staging(S))) return rc;
         if ((rc = ptp::prims_device(&dg, S->st_prims.p, S->st_normals.p, &has_sphere))) return rc;
         us_records = clock.lap();
-        if ((rc = adopt_staged(S, "pt_scene_update", !has_sphere, &us_plan, &us_refit))) return rc;
+        if ((rc = adopt_staged(S, "pt_scene_update", !has_sphere, &us_plan, &us_refit))) { S->cost_drop_pending(); return rc; }
         S->have_rest = false;                        // the next pt_scene_transform starts from these records
         rebuild_by_policy(S);
     }
@@ -904,7 +904,7 @@ int transform_scene(pt_scene* S, const pt_transform* transforms, int32_t num_gro
         return rc;
     us_records = clock.lap();
     int64_t us_plan = 0;
-    if ((rc = adopt_staged(S, "pt_scene_transform", S->tri_only, &us_plan, &us_refit))) return rc;
+    if ((rc = adopt_staged(S, "pt_scene_transform", S->tri_only, &us_plan, &us_refit))) { S->cost_drop_pending(); return rc; }
     rebuild_by_policy(S);
     // the handle's own streams do not synchronise with the default stream the kernels above ran on
     HIP_TRY(hipDeviceSynchronize());

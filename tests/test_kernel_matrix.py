@@ -8,6 +8,7 @@ import ctypes as C
 import os
 from collections import Counter
 
+import adaptive_reference
 import numpy as np
 import pytest
 from conftest import assert_bit_equal, assert_work_counters, random_scene
@@ -233,7 +234,7 @@ def _pruned_bound(img, want, what):
 
 @pytest.mark.gpu
 def test_every_compiled_trace_kernel_matches_the_oracle(oracle):
-    from test_adaptive import _oracle_groups, _stop_reference
+    from test_adaptive import _oracle_groups
     from pathtracer_cuda_interactive_amd import device as dev
 
     compiled = sorted(set(_compiled()), key=lambda v: (plan(v)["scene"], v))
@@ -272,7 +273,7 @@ def test_every_compiled_trace_kernel_matches_the_oracle(oracle):
                     assert c.paths == int(spp.sum()), what
                 if pl["traversal"] == PT_TRAVERSAL_EXACT:
                     if pl["adaptive"]:
-                        _check_adaptive(oracle, d, p, img, spp, samples, key, flags, what, _oracle_groups, _stop_reference)
+                        _check_adaptive(oracle, d, p, img, spp, samples, key, flags, what, _oracle_groups)
                     else:
                         if (key, flags) not in exact:
                             exact[(key, flags)] = oracle.render(d, p)
@@ -342,7 +343,7 @@ def _with_spp(p, spp, traversal=None):
     return q
 
 
-def _check_adaptive(oracle, d, p, img, spp, samples, key, flags, what, oracle_groups, stop_reference):
+def _check_adaptive(oracle, d, p, img, spp, samples, key, flags, what, oracle_groups):
     """An exact adaptive call: spp_map as the stopping rule gives it on the oracle's samples, the image as the oracle's at
     each pixel's own sample count."""
     if (key, flags) not in samples:
@@ -353,9 +354,10 @@ def _check_adaptive(oracle, d, p, img, spp, samples, key, flags, what, oracle_gr
             q = p.copy()
             q.spp, q.sample_offset, q.stream_stride = 1, k, A_MAX
             s[:, k], _ = oracle.render_pixels(d, q, xy)
-        samples[(key, flags)] = stop_reference(s, A_SPP, A_BATCH, A_MAX, A_ERROR, A_MIN_LUM)
-    n_ref, _, near = samples[(key, flags)]
-    ok = near > 1e-9                                   # pixels whose err is not within rounding of the target
+        # render_adaptive's default p_value reaches the library as float32(0.05)
+        samples[(key, flags)] = adaptive_reference.expected(s, A_SPP, A_BATCH, A_MAX, A_ERROR, A_MIN_LUM, np.float32(0.05))
+    E = samples[(key, flags)]
+    n_ref, ok = E.n, E.decided                         # pixels whose count the bracketed quantile leaves no doubt about
     assert ok.sum() >= 0.95 * ok.size, what
     got = spp.reshape(-1)
     assert (got[ok] == n_ref[ok]).all(), f"{what}: spp_map differs from the stopping rule at {np.nonzero(got[ok] != n_ref[ok])[0][:5]}"

@@ -791,6 +791,15 @@ int pt_bvh_build_sweep_device(const pt_scene_desc* desc, pt_bvh_node* out_nodes,
  *                   sharing an axis 31, flat 29, single 17, PAIR2 27 / 25 / 23 with 0 / 1 / 2 flat axes).  In
  *                   "sweep_share_pairs" and "sweep_flat_pairs" a PAIR2 counts as one pair (flat where one of its axes is);
  *                   with _x, _y, _z it counts under each of the two axes it shares.
+ *   "sweep_self_skip" 1 (default) a "leaf_sweep" launch leaves out leaf tests that cannot keep a hit: a bounce that starts on a
+ *                   triangle whose group has a box flat on an axis (an axis-aligned wall), with the new origin's coordinate on
+ *                   that axis equal to the plane's as floats, does not test the triangles of that plane: the group it left
+ *                   and every other group flat on the same axis at the same coordinate (csrc/pt_sweep_skip.h has the
+ *                   argument: such a test computes t = +-0 or NaN and is rejected whatever the direction).  Camera rays and
+ *                   origins off the plane by as little as one ulp test every group the sweep hits.  0 = every group the
+ *                   sweep hits is tested (A/B runs, tests).  The same bits under either value.  Info "sweep_skip_groups"
+ *                   reports the groups that can be skipped under the options as they stand, "sweep_skip_planes" the
+ *                   distinct planes (axis, coordinate) they lie on; both 0 under option 0 or without sweep tables.
  *   "octants"       1 (default) keep 8 ray-octant node tables in LDS for very small scenes, 0 = one table
  *   "fast_tree"     1 (default) traversal (exact and pruned) on the library's INTERNAL tree where pt_scene_create kept one,
  *                   0 = on the caller's tree.  Same image either way, bit for bit: the reference never prunes, so a leaf is tested iff the
@@ -847,6 +856,7 @@ int pt_bvh_build_sweep_device(const pt_scene_desc* desc, pt_bvh_node* out_nodes,
  * stack columns), "leaf_sweep" (1 = that kernel found its leaves by the box sweep, see option "leaf_sweep"), "sweep_boxes",
  * "sweep_share_pairs", "sweep_flat_pairs", "sweep_general_pairs" (see option "sweep_pairs"),
  * "sweep_pair2_records", "sweep_valu_model" (see option "sweep_families"),
+ * "sweep_skip_groups", "sweep_skip_planes" (see option "sweep_self_skip"),
  * "frames_in_flight", "sweep_on_device" (the internal tree was built on the GPU), "query_chunk" (ray indices a wave of the query
  * kernel reserves per atomic), "query_grid" (blocks of the last query launch), "query_guides" (the last pt_render_guides_async
  * ran on the refilling kernel: 1, or the one-shot kernel: 0),

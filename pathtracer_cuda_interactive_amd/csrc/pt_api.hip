@@ -184,7 +184,8 @@ int choose_trace(const pt_scene* S, int traversal, bool nee, bool listed, TraceC
     // The sweep's own tables (pt_sweep_layout.h) go where that plan has the octant node tables: a launch whose tables do not fit
     // there takes the tree (a binary tree over 3 primitives or more always leaves the room).
     c.sweep = S->opt_leaf_sweep && leaf_sweep_on(c.reg_stack, exact, c.stats, c.res, S->dev.num_prims, (int)S->sweep.count) &&
-              S->sweep_tab.p && sweep_layout_fits(S->sweep.count, (uint32_t)S->dev.num_prims, (uint32_t)T.num_nodes, kLdsNodeStride);
+              S->sweep_tab.p && sweep_layout_fits(S->sweep.count, (uint32_t)S->dev.num_prims, (uint32_t)T.num_nodes, kLdsNodeStride) &&
+              S->sweep_skip.p && sweep_skip_fits(S->sweep.count, (uint32_t)S->dev.num_prims, (uint32_t)T.num_nodes, kLdsNodeStride);
     c.block_threads = c.family == 3 ? kQBlock : kBlock;
     c.feed_waves = c.family == 3 ? kQS : kBlock / 64;
     c.redo_lanes = c.family == 3 ? kQS * 64 : kBlock;            // kernel 3: its S-waves rerun
@@ -377,11 +378,12 @@ void launch_trace(const pt_scene* S, const TraceChoice& c, const TraceEntry& e, 
         hipLaunchKernelGGL(reinterpret_cast<TraceFnQ>(fn), dim3(grid), dim3(c.block_threads), lp.total, stream, S->dev, rd, lp, qp,
                            samples, S->work_counter(), S->counters());
     else if (c.sweep) {
-        // options "sweep_pairs", "sweep_families": the tables in class order, or in the groups' own order with every pair general
+        // options "sweep_pairs", "sweep_families": the tables in class order, or in the groups' own order with every pair general;
+        // option "sweep_self_skip": the skip table in that order, or the one of zeros
         const SweepClasses cls = S->sweep_classes_now();
         hipLaunchKernelGGL(reinterpret_cast<SweepFn>(fn), dim3(grid), dim3(c.block_threads), lp.total, stream, S->dev, rd, lp,
                            samples, S->work_counter(), S->counters(),
-                           SweepLayoutDev{S->sweep_tab_now(), S->sweep.count, sweep_classes_pitch(cls), cls.pairs, cls.fam});
+                           SweepLayoutDev{S->sweep_tab_now(), S->sweep.count, sweep_classes_pitch(cls), cls.pairs, cls.fam, S->sweep_skip_now()});
     } else
         hipLaunchKernelGGL(reinterpret_cast<TraceFn>(fn), dim3(grid), dim3(c.block_threads), lp.total, stream, S->dev, rd, lp,
                            samples, S->work_counter(), S->counters());
@@ -1748,6 +1750,7 @@ int pt_scene_set_option(pt_scene* S, const char* key, int64_t value) {
     else if (k == "leaf_sweep") { if (value != 0 && value != 1) return fail(PT_ERR_INVALID_ARG, "leaf_sweep must be 0 or 1"); S->opt_leaf_sweep = value; }
     else if (k == "sweep_pairs") { if (value != 0 && value != 1) return fail(PT_ERR_INVALID_ARG, "sweep_pairs must be 0 or 1"); S->opt_sweep_pairs = value; }
     else if (k == "sweep_families") { if (value != 0 && value != 1) return fail(PT_ERR_INVALID_ARG, "sweep_families must be 0 or 1"); S->opt_sweep_families = value; }
+    else if (k == "sweep_self_skip") { if (value != 0 && value != 1) return fail(PT_ERR_INVALID_ARG, "sweep_self_skip must be 0 or 1"); S->opt_sweep_self_skip = value; }
     else if (k == "query_refill") { if (value < 0 || value > 64) return fail(PT_ERR_INVALID_ARG, "query_refill must be 0 (automatic) .. 64"); S->opt_query_refill = value; }
     else if (k == "query_guides") { if (value < 0 || value > 2) return fail(PT_ERR_INVALID_ARG, "query_guides must be 0 (automatic), 1 or 2"); S->opt_query_guides = value; }
     else if (k == "query_blocks") { if (value < 0 || value > 4096) return fail(PT_ERR_INVALID_ARG, "query_blocks must be 0 (automatic) .. 4096"); S->opt_query_blocks = value; }
@@ -1843,6 +1846,8 @@ int pt_scene_get_info(pt_scene* S, const char* key, int64_t* value) {
     }
     else if (k == "sweep_pair2_records") *value = sweep_pair2_records(S->sweep_classes_now().fam);      // PAIR2 records of that launch
     else if (k == "sweep_valu_model") *value = sweep_valu_model(S->sweep_classes_now());                // the count model's VALU of its sweep loops
+    else if (k == "sweep_skip_groups") *value = S->sweep_skip_info_now().groups;     // groups a bounce can skip under the options as they stand (pt_sweep_skip.h)
+    else if (k == "sweep_skip_planes") *value = S->sweep_skip_info_now().planes;     // ... and the distinct planes they lie on
     else if (k == "reg_stack") *value = S->info_reg_stack;                // ... with the traversal stack in a register (1) or in LDS / global memory (0)
     else if (k == "block_threads") *value = S->info_kernel == 3 ? kQBlock : kBlock;
     else if (k == "frames_in_flight") *value = S->opt_frames_in_flight;

@@ -18,6 +18,7 @@
 #include "pt_path_index.h"
 #include "pt_sweep_layout.h"
 #include "pt_sweep_families.h"
+#include "pt_sweep_skip.h"
 #include "pt_sweep_pairs.h"
 #include "pt_temporal.h"
 #include "pt_trace.h"
@@ -377,7 +378,9 @@ __global__ __launch_bounds__(kBlock, (kBlock > 256 ? 1 : MINW)) void trace_kerne
 // PT_SWEEP_LEAF_STEPS: leaf tests per iteration between two scheduler checks; PT_SWEEP_THRESH: lanes that must be able to make
 // progress for a scheduler phase to run (-D: A/B libraries).  A phase carries the whole sweep whatever its width, so it pays to
 // wait for a fuller one than the tree kernel's 40: cbox 640x480x64 at 1.669 / 1.649 / 1.693 ms per frame with 40 / 48 / 56, and
-// 1.706 / 1.669 / 1.698 / 1.679 with 3 / 4 / 5 / 6 leaf steps at 40 (profiles/r12_sweep_layout.log §7).
+// 1.706 / 1.669 / 1.698 / 1.679 with 3 / 4 / 5 / 6 leaf steps at 40 (profiles/r12_sweep_layout.log §7).  Measured again with the
+// skip word (pt_sweep_skip.h: about three tests per segment): 1.425 at 4 / 48 against 1.462 at 3 / 48, 1.500 at 3 / 40 and
+// 1.435 at 4 / 40 (profiles/r18_self_skip.log §5).
 #ifndef PT_SWEEP_LEAF_STEPS
 #define PT_SWEEP_LEAF_STEPS 4
 #endif
@@ -390,6 +393,7 @@ struct SweepLayoutDev {
     uint32_t box_pitch;             // sweep_classes_pitch of the two below
     SweepPairClasses classes;       // pairs per class of the sweep loop (pt_sweep_pairs.h), scalars
     SweepFamilyClasses fam;         // records per PAIR2 class in front of them (pt_sweep_families.h), read from the kernel arguments inside the phase
+    const unsigned char* skip;      // the skip table in the order of `tab` (pt_sweep_skip.h), or one of zeros: kSweepSkipTableBytes of global memory
 };
 struct SweepKernelArgs {
     SceneDev scn; RenderDev rp; LdsPlan lp; float4* samples; uint32_t* work_counter; unsigned long long* counters; SweepLayoutDev sweep;
@@ -417,6 +421,8 @@ __device__ __forceinline__ ptd::SceneView make_sweep_view(const SceneDev& scn, c
         d[1] = make_float4(r.v[4], r.v[5], r.v[6], r.v[7]);
         d[2] = make_float4(r.v[8], c.y, c.z, c.w);
     }
+    // the skip entries behind the slot records, still inside the node region (pt_sweep_skip.h: sweep_skip_fits)
+    stage_to_lds(smem + lp.nodes_off + sweep_skip_off(sweep.groups, (uint32_t)scn.num_prims), sweep.skip, sweep_skip_bytes((uint32_t)scn.num_prims));
     stage_to_lds(smem + lp.prims_off, scn.prims, (uint32_t)scn.num_prims * sizeof(DPrim));
     stage_to_lds(smem + lp.normals_off, scn.normals, (uint32_t)scn.num_prims * sizeof(DNormals));
     stage_to_lds(smem + lp.mats_off, scn.materials, (uint32_t)scn.num_materials * sizeof(DMaterial));

@@ -17,6 +17,7 @@
 #include "pt_layout.h"
 #include "pt_leaf_sweep.h"
 #include "pt_sweep_families.h"
+#include "pt_sweep_skip.h"
 #include "pt_sweep_pairs.h"
 #include "pt_scene_refit.h"
 
@@ -299,6 +300,14 @@ struct pt_scene {
         return opt_sweep_pairs && sweep_tab_pairs[opt_sweep_families].p ? sweep_classes[opt_sweep_families] : sweep_classes_of_pairs(sweep_pairs_none(sweep.count));
     }
     const unsigned char* sweep_tab_now() const { return opt_sweep_pairs && sweep_tab_pairs[opt_sweep_families].p ? sweep_tab_pairs[opt_sweep_families].p : sweep_tab.p; }
+    // the skip tables (pt_sweep_skip.h), made, uploaded and dropped with the tables above: kSweepSkipTableBytes each, [0] all
+    // zero (option "sweep_self_skip" 0), [1] in sweep_tab's group order, [2] and [3] in sweep_tab_pairs[0]'s and [1]'s
+    DevBuf<unsigned char> sweep_skip;
+    SweepSkipInfo sweep_skip_info[3] = {};
+    int64_t opt_sweep_self_skip = 1; // 1 = a bounce skips the leaf tests of the plane it starts on, 0 = every group the sweep hits is tested
+    int sweep_skip_index() const { return !opt_sweep_self_skip ? 0 : opt_sweep_pairs && sweep_tab_pairs[opt_sweep_families].p ? 2 + (int)opt_sweep_families : 1; }
+    const unsigned char* sweep_skip_now() const { return sweep_skip.p ? sweep_skip.p + (size_t)sweep_skip_index() * kSweepSkipTableBytes : nullptr; }
+    SweepSkipInfo sweep_skip_info_now() const { return sweep.count && sweep_skip.p && sweep_skip_index() ? sweep_skip_info[sweep_skip_index() - 1] : SweepSkipInfo{0, 0}; }
     // info of last launch
     // wall time of pt_scene_create's stages, microseconds: [0] total [1] primitive records [2] caller's tree checked and re-laid
     // [3] internal tree built [4] ... re-laid [5] uploads + probe [6] tie tables; built_on_device: the sweep ran on the GPU

@@ -18,6 +18,7 @@
 #include "pt_transform.h"
 #include "pt_sweep_layout.h"
 #include "pt_sweep_families.h"
+#include "pt_sweep_skip.h"
 #include "pt_sweep_pairs.h"
 
 namespace {
@@ -370,12 +371,15 @@ bool probe_wins(const unsigned long long v[2]) { return v[1] * 100ull < v[0] * 9
 // host built it; prims: the N <= kSweepMaxPrims records on the host.  groups = 0: none; sweep.count stays 0 where a launch
 // would not admit them.  The tables are made twice: in the groups' own order with every pair general (sweep_tab), and in the
 // class order (sweep_tab_pairs, classes), once per value of option "sweep_families" (pt_sweep_families.h; [0]: the pair classes
-// of pt_sweep_pairs.h alone); options "sweep_pairs" and "sweep_families" choose among them at a launch.
+// of pt_sweep_pairs.h alone); options "sweep_pairs" and "sweep_families" choose among them at a launch.  Each of the three has
+// its skip table (pt_sweep_skip.h) in its own group order, in sweep_skip behind a table of zeros (option "sweep_self_skip").
 int make_sweep_tables(const TreeHost& fast, const DPrim* prims, int N, SweepTable& sweep, int& sweep_groups, DevBuf<unsigned char>& sweep_tab,
-                      DevBuf<unsigned char> (&sweep_tab_pairs)[2], SweepClasses (&classes)[2]) {
+                      DevBuf<unsigned char> (&sweep_tab_pairs)[2], SweepClasses (&classes)[2], DevBuf<unsigned char>& sweep_skip,
+                      SweepSkipInfo (&skip_info)[3]) {
     sweep = SweepTable{};
     sweep_groups = 0;
     for (SweepClasses& c : classes) c = SweepClasses{};
+    for (SweepSkipInfo& i : skip_info) i = SweepSkipInfo{0, 0};
     SweepGroup groups[kSweepMaxPrims];
     const int n = build_sweep_groups(fast.nodes.data(), (int)fast.nodes.size(), N, kLdsNodeStride, groups);
     if (n > 0) {
@@ -385,14 +389,18 @@ int make_sweep_tables(const TreeHost& fast, const DPrim* prims, int N, SweepTabl
         int perm[kSweepMaxBoxes];
         SweepClasses cls[2] = {};
         std::vector<unsigned char> tab_pairs[2];
+        std::vector<unsigned char> skip(4 * (size_t)kSweepSkipTableBytes, 0);      // [0] stays zero
+        SweepSkipInfo si[3] = {};
         const DNode* nodes = fast.nodes.data();
         const int num_nodes = (int)fast.nodes.size();
-        bool ok = n <= kSweepMaxBoxes && build_sweep_layout(groups, n, nodes, num_nodes, kLdsNodeStride, prims, N, tab.data());
+        bool ok = n <= kSweepMaxBoxes && build_sweep_layout(groups, n, nodes, num_nodes, kLdsNodeStride, prims, N, tab.data()) &&
+                  build_sweep_skip(groups, n, nodes, num_nodes, kLdsNodeStride, prims, N, skip.data() + kSweepSkipTableBytes, &si[0]);
         for (int m = 0; ok && m < 2; m++) {
             tab_pairs[m].resize(tab.size());
             ok = build_sweep_families(groups, n, nodes, num_nodes, kLdsNodeStride, m, paired, perm, &cls[m]) &&
                  build_sweep_layout(paired, n, nodes, num_nodes, kLdsNodeStride, prims, N, tab_pairs[m].data()) &&
-                 build_sweep_family_tables(paired, n, cls[m], nodes, num_nodes, kLdsNodeStride, tab_pairs[m].data());
+                 build_sweep_family_tables(paired, n, cls[m], nodes, num_nodes, kLdsNodeStride, tab_pairs[m].data()) &&
+                 build_sweep_skip(paired, n, nodes, num_nodes, kLdsNodeStride, prims, N, skip.data() + (2 + m) * (size_t)kSweepSkipTableBytes, &si[1 + m]);
         }
         // every table a launch can choose must hold the kernel's record stream, its read past the last record included
         // (pt_sweep_families.h: sweep_stream_fits).  A table is at most its pitch long and a scene has a primitive, so the end
@@ -408,6 +416,9 @@ int make_sweep_tables(const TreeHost& fast, const DPrim* prims, int N, SweepTabl
                 HIP_TRY(hipMemcpy(sweep_tab_pairs[m].p, tab_pairs[m].data(), tab_pairs[m].size(), hipMemcpyHostToDevice));
                 classes[m] = cls[m];
             }
+            if (int rc = sweep_skip.ensure(skip.size())) return rc;
+            HIP_TRY(hipMemcpy(sweep_skip.p, skip.data(), skip.size(), hipMemcpyHostToDevice));
+            std::copy(si, si + 3, skip_info);
             sweep.count = (uint32_t)n;
             std::copy(groups, groups + n, sweep.g);
         }
@@ -622,7 +633,7 @@ int validate_and_build(const pt_scene_desc* d, pt_scene* S) {
     // 8: the leaf sweep's groups of equal leaf boxes (pt_leaf_sweep.h), from the internal tree as the host built it
     S->sweep = SweepTable{}; S->sweep_groups = 0;
     if (S->have_fast && !c.cand.on_device && !S->fast_is_callers_topology && N <= kSweepMaxPrims &&
-        (rc = make_sweep_tables(c.cand.host, c.prims.data(), N, S->sweep, S->sweep_groups, S->sweep_tab, S->sweep_tab_pairs, S->sweep_classes)))
+        (rc = make_sweep_tables(c.cand.host, c.prims.data(), N, S->sweep, S->sweep_groups, S->sweep_tab, S->sweep_tab_pairs, S->sweep_classes, S->sweep_skip, S->sweep_skip_info)))
         return rc;
     // complete from here on: trace kernels run on the handle's own streams (FrameSlot), which do not synchronise with this one
     HIP_TRY(hipDeviceSynchronize());
@@ -725,6 +736,8 @@ int adopt_staged(pt_scene* S, const char* who, bool tri_only, int64_t* us_plan, 
     S->sweep_groups = 0; S->sweep.count = 0;     // leaf boxes that were equal need not be any more: back to the tree
     S->sweep_tab.release();                      // (no frame is in flight: the update synchronised before it wrote)
     for (int m = 0; m < 2; m++) { S->sweep_tab_pairs[m].release(); S->sweep_classes[m] = SweepClasses{}; }
+    S->sweep_skip.release();
+    for (SweepSkipInfo& i : S->sweep_skip_info) i = SweepSkipInfo{0, 0};
     *us_refit = clock.lap();
     return PT_OK;
 }
@@ -766,7 +779,7 @@ int rebuild_scene(pt_scene* S) {
     // ---- what goes with an adopted tree: its refit plan where the handle has refitted before (the next update does not pay for
     // it), the box sweep of a small scene under create's admission rules, its cost where telemetry is on
     ptf::Plan plan;
-    SweepTable sweep{}; int sweep_groups = 0; DevBuf<unsigned char> sweep_tab, sweep_tab_pairs[2]; SweepClasses sweep_classes[2] = {};
+    SweepTable sweep{}; int sweep_groups = 0; DevBuf<unsigned char> sweep_tab, sweep_tab_pairs[2], sweep_skip; SweepClasses sweep_classes[2] = {}; SweepSkipInfo sweep_skip_info[3] = {};
     double cost = 0.0;
     if (adopt) {
         if (S->refit_plan[1].built && (rc = ptf::plan_build(cand.tree.nodes.p, cand.tree.num_nodes, N, &plan))) return rc;
@@ -774,7 +787,7 @@ int rebuild_scene(pt_scene* S) {
         if (!cand.on_device && N <= kSweepMaxPrims) {
             std::vector<DPrim> prims((size_t)N);
             HIP_TRY(hipMemcpy(prims.data(), S->prims.p, prims.size() * sizeof(DPrim), hipMemcpyDeviceToHost));
-            if ((rc = make_sweep_tables(cand.host, prims.data(), N, sweep, sweep_groups, sweep_tab, sweep_tab_pairs, sweep_classes))) return rc;
+            if ((rc = make_sweep_tables(cand.host, prims.data(), N, sweep, sweep_groups, sweep_tab, sweep_tab_pairs, sweep_classes, sweep_skip, sweep_skip_info))) return rc;
         }
         if (S->cost_on()) {
             if ((rc = ensure_cost(S)) || (rc = enqueue_cost(S, cand.tree, 3))) return rc;
@@ -791,6 +804,8 @@ int rebuild_scene(pt_scene* S) {
         S->sweep = sweep; S->sweep_groups = sweep_groups;
         S->sweep_tab.swap(sweep_tab);
         for (int m = 0; m < 2; m++) { S->sweep_tab_pairs[m].swap(sweep_tab_pairs[m]); S->sweep_classes[m] = sweep_classes[m]; }
+        S->sweep_skip.swap(sweep_skip);
+        std::copy(sweep_skip_info, sweep_skip_info + 3, S->sweep_skip_info);
         S->cfg_fn = S->q_cfg_fn = nullptr;            // stack and LDS needs follow the tree: the next launch asks again
         if (S->cost_on()) { S->cost_ref[1] = S->cost_now[1] = cost; S->cost_have_ref[1] = true; }
     } else if (S->cost_on() && S->cost_have_ref[1] && S->cost_now[1] > 0.0) {

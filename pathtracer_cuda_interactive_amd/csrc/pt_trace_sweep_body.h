@@ -3,7 +3,7 @@
 // (pt_leaf_sweep.h, pt_sweep_layout.h): step (3) of the phase tests every distinct leaf box of the scene against the new segment
 // and leaves the lane one hit bit per group; the burst is leaf tests alone, group by group, each group's primitives along the
 // chain of its slot records.  No inner step, no stack, and 1/d is dead once the phase ends.  The block stages the sweep's own
-// tables (box tables, slot records) where the tree kernel stages the 8 octant node tables: the tree is never walked here, and
+// tables (box tables, slot records, skip entries) where the tree kernel stages the 8 octant node tables: the tree is never walked here, and
 // a rerun reads the caller's tree in global memory.  The launches that take it: leaf_sweep_on — residency 2, exact traversal
 // on the internal tree (so scn.fallback is set: ties on t are settled in the caller's visit order and a ray with a non-finite
 // 1/d is traced on the caller's tree), triangles with diffuse materials, no counting, no next-event estimation, no pixel list.
@@ -37,6 +37,7 @@
     tv.best.t = 0; tv.best.u = 0; tv.best.v = 0; tv.best.prim = -1;
     tv.cur = 0; tv.stack_state = 0; tv.node_off = 0; tv.redo = false;
     uint32_t hits = 0;                             // groups whose box this segment hits and that are not yet taken up: group k = bit 31 - k
+                                                   // (between steps (1) and (3) of a phase: the groups a bounce need not test)
     uint32_t pend = 0;                             // the slot to test next inside the group taken up last, 0 = none
     ptm::V3 L = ptm::mk(0, 0, 0), T = ptm::mk(1, 1, 1);
     ptm::Pcg rng;
@@ -81,6 +82,19 @@
                 if (!cont) {
                     samples[my_w] = make_float4(L.x, L.y, L.z, 0.0f);
                     alive = false;
+                } else {
+                    // The bounce starts on the primitive it hit.  Where that primitive's group is flat on an axis and the new
+                    // origin lies on its plane bit for bit, no triangle of that plane can be kept as a hit of the next segment
+                    // (pt_sweep_skip.h has the argument): step (3) takes those groups out of the hit word.  `hits` is zero in
+                    // an idle lane and the sweep accumulates in h, so the skip word waits there; a lane that does not go on
+                    // keeps its zero, a refilled lane (camera ray) never comes by here.
+                    typedef const __attribute__((address_space(3))) uint32_t* LdsWords;
+                    LdsWords e = (LdsWords)((LdsBytes)smem + lp.nodes_off + sweep_skip_off(n_groups, (uint32_t)scn.num_prims) +
+                                            (uint32_t)tv.best.prim * (uint32_t)sizeof(SweepSkipEntry));
+                    const float skip_c = __builtin_bit_cast(float, e[0]);
+                    const uint32_t skip_mask = e[1], skip_axis = e[2];
+                    const float oa = skip_axis == 0u ? ray.org.x : skip_axis == 1u ? ray.org.y : ray.org.z;
+                    hits = oa == skip_c ? skip_mask : 0u;
                 }
             }
             // (2) refill dead lanes out of the wave's path bank (pt_trace_v2_body.h has the account of it)
@@ -219,7 +233,9 @@
                         const float tn0 = ptm::fmax2(0.0f, tn);
                         asm("v_cmp_ge_f32_e32 vcc, %1, %2\n\ts_nop 1\n\tv_addc_co_u32_e32 %0, vcc, %0, %0, vcc" : "+v"(h) : "v"(tf), "v"(tn0) : "vcc");
                     }
-                    hits = sweep_hits_align(h, n_groups);
+                    hits = sweep_hits_align(h, n_groups) & ~hits;         // without the groups of the plane a bounce starts on (step (1))
+                } else {
+                    hits = 0u;                                            // the rerun takes every leaf: the skip word goes unused
                 }
             }
         }
